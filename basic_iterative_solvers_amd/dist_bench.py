@@ -1,7 +1,7 @@
 """bench.py, N > 1: strong scaling of the fused CG on the row-partitioned operator
 (z-slabs), one process per GPU, RCCL over xGMI.  The record's headline streams the CRS value
-array (north_star's CRS SpMV); `compressed_stream` is the same solve with the library's default
-stream format, and `target_512` both on the north-star problem (HPCG 512^3, strong scaling:
+array (north_star's CRS SpMV); with --full, `compressed_stream` is the same solve with the library's
+default stream format, and `target_512` both on the north-star problem (HPCG 512^3, strong scaling:
 every rank generates its z-slab).  --matrix hpcg is the BASELINE metric
 (HPCG 256^3, -cg); --matrix anderson --precond j is BASELINE config 3 (Anderson 256^3,
 Jacobi-preconditioned CG, row-partitioned): shift 0 is the config as named (indefinite: a
@@ -43,6 +43,29 @@ def r0_closed_form(matrix, shift, n1):
     return float(np.sqrt(tot))
 
 
+DUMP_ROWS = 1 << 21  # rows of x that --dump-outputs writes at most (16 MB of float64)
+DUMP_LIMIT = 64 << 20  # bytes that --dump-outputs writes at most
+
+
+def dump_rows(n, cap=DUMP_ROWS, seed=0):
+    """The rows of an n-vector that --dump-outputs writes: None (all of them) up to `cap`, else a fixed sample of `cap` rows
+    drawn with `seed`, in increasing order -- the same rows for the same n in every run."""
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float64, DUMP_LIMIT bytes at most in all."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 KERNELS = ("spmv_rowblock_kernel", "spmv_rowblock_vd_kernel", "spmv_rowmajor_vd_kernel", "spmv_rowmajor_vd_kernel",
            "spmv_sellwin_kernel", "spmv_sellwin_kernel", "spmv_win8_kernel")
 
@@ -52,11 +75,12 @@ class _Env:
     pass
 
 
-def cg_leg(E, args, n1, matrix, precond, shift, steps, warmup, valdict):
+def cg_leg(E, args, n1, matrix, precond, shift, steps, warmup, valdict, dump=None):
     """One partitioned problem, one stream format: generate this rank's z-slab of the n1^3 operator in HBM, build the
     distributed operator, check ||b - A x0|| against the closed form, time `steps` CG iterations between barriers.
     Returns rank 0's record (None elsewhere).  valdict = 0: the CRS value array is streamed (north_star's CRS SpMV),
-    -1: the library's default stream format for the matrix."""
+    -1: the library's default stream format for the matrix.  dump: a directory where rank 0 writes the residual history
+    and x (dump_rows of it, gathered from the ranks) after the timed steps."""
     import torch
     td, ctx, rank, world = E.td, E.ctx, E.rank, E.world
     from . import BisError, Dist, rccl_unique_id
@@ -140,6 +164,14 @@ def cg_leg(E, args, n1, matrix, precond, shift, steps, warmup, valdict):
     launches, spmv_ms = ctx.profile_read()
     comm = d.profile_read()
     iters, conv, hist = cg.status(hist_cap=warmup + steps + 1)
+    if dump:
+        rows, xl = dump_rows(N), x.to_host()
+        part = xl if rows is None else xl[rows[(rows >= row0) & (rows < row1)] - row0]
+        parts = [None] * world
+        td.all_gather_object(parts, part, group=E.host_group)
+        if rank == 0:  # the ranks own increasing row ranges: their parts in rank order are the rows in order
+            write_outputs(dump, {"residual_history": hist, ("x" if rows is None else "x_sample"): np.concatenate(parts)})
+        del xl, part, parts
     col_b, val_b, n_dict, form = d.spmv_stream_info()
     kernel = "spmv_sellmask_kernel" if form >= 4 and col_b == 0 else KERNELS[form]
     streamed = d.spmv_streamed_bytes()
@@ -253,9 +285,11 @@ def run_distributed(args, rank, world, local_rank):
         ctx.lib.bis_set_option(b"tune_placement", int(args.tune_placement))
     headline_valdict = -1 if getattr(args, "headline", "crs") == "default" else 0
     n1 = args.size
-    out = cg_leg(E, args, n1, args.matrix, args.precond, args.shift, args.steps, args.warmup, headline_valdict)
+    full = getattr(args, "full", False)
+    out = cg_leg(E, args, n1, args.matrix, args.precond, args.shift, args.steps, args.warmup, headline_valdict,
+                 dump=getattr(args, "dump_outputs", None))
     extra = {}
-    if headline_valdict == 0:
+    if full and headline_valdict == 0:
         leg = cg_leg(E, args, n1, args.matrix, args.precond, args.shift, min(args.steps, 50), min(args.warmup, 5), -1)
         if rank == 0 and leg["per_rank"][0]["spmv_stream"]["val_bytes"] < 8:
             leg["note"] = "the library's default stream format for this matrix (lossless re-encoding of the CRS arrays, bit-identical y)"
@@ -265,7 +299,7 @@ def run_distributed(args, rank, world, local_rank):
     t512 = getattr(args, "target_size", 0)
     if E.rehearse and t512 == 512:
         t512 = 2 * n1  # a one-GPU rehearsal of the leg (all ranks share cuda:0): same code, a problem that fits beside itself
-    if world > 1 and args.matrix == "hpcg" and t512 > 0 and not getattr(args, "no_target_512", False):
+    if full and world > 1 and args.matrix == "hpcg" and t512 > 0 and not getattr(args, "no_target_512", False):
         info = ctx.device_info()
         slab_bytes = 12.0 * 27 * (t512 ** 3) / world * 1.35 + 8.0 * 12 * (t512 ** 3) / world
         if info["hbm_bytes"] * (0.5 if E.rehearse else 0.85) >= slab_bytes * (world if E.rehearse else 1):

@@ -2,7 +2,7 @@
 """bench.py -- CG iterations/s (+ SpMV GFLOP/s and % of the HBM roofline) on
 the HPCG 27-point operator, the metric BASELINE.json names.
 
-    python bench.py --gpus N --steps K --warmup W [--size 256] [--precond none|j]
+    python bench.py --gpus N --steps K --warmup W [--size 256] [--precond none|j] [--full] [--dump-outputs DIR]
 
 A "step" is one CG iteration (methods/cg.hpp:6-54 + the residual sample of
 :162-166) on synthetic HPCG-`size` (size^3 rows, 27-point, b = 1, x0 = 0.1),
@@ -10,7 +10,14 @@ generated directly in HBM; inputs are resident before the timed region.
 N > 1: one process per GPU (torch.distributed.run), the matrix 1-D
 row-partitioned (z-slabs), strong scaling: the global problem is fixed.
 
-Prints ONE JSON line (rank 0).  The timed region -- `value`, `ms_per_step`,
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `value` (CG iterations/s),
+`ms_per_step`, the `roofline` of the timed SpMV launches and the options in effect.  Everything else below -- the
+streaming yardsticks, the device state, the other stream formats, the CPU legs and parity, `target_512`,
+`config5_spmv*`, `sweeps`, `configs` (and, N > 1, `compressed_stream` and `target_<size>`) -- runs only with --full.
+--dump-outputs DIR writes what the timed steps computed, right after them: DIR/residual_history.npy (||r_k||, warmup
+included) and DIR/x.npy (the iterate; above 2^21 rows DIR/x_sample.npy, a fixed seeded sample of 2^21 rows), float64.
+
+The timed region -- `value`, `ms_per_step`,
 `roofline` -- is the path BASELINE.json's north_star names: CRS SpMV inside the
 CG loop with the CRS value array streamed (8 bytes per non-zero; option
 spmv_valdict = 0), the SpMV launches priced with HIP events recorded on the
@@ -85,7 +92,16 @@ def parse():
     ap.add_argument("--headline", default="crs", choices=["crs", "default"],
                     help="what the timed region streams: crs = the CRS value array (north_star's CRS SpMV; the default), "
                          "default = the library's default format for the matrix (compressed where it applies)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: streaming yardsticks, device state, the other stream formats, "
+                         "CPU baselines + parity, target_512, config5_spmv, sweeps, configs (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64): residual_history, "
+                         "and x (all rows up to 2^21, else x_sample: a fixed seeded sample of 2^21 rows)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def device_state():
@@ -730,25 +746,33 @@ def main():
     t1 = time.perf_counter()
     ctx.profile(False)
     launches, spmv_ms = ctx.profile_read()
-    state_after_timed = device_state()
+    state_after_timed = device_state() if args.full else None
     iters, conv, hist = cg.status(hist_cap=args.warmup + args.steps + 1)
     if iters != args.warmup + args.steps:
         raise SystemExit(f"timed region invalid: {iters} iterations executed, "
                          f"expected {args.warmup + args.steps}")
+    if args.dump_outputs:  # before any other leg re-initialises x
+        from basic_iterative_solvers_amd.dist_bench import dump_rows, write_outputs
+        xh = x.to_host()
+        rows = dump_rows(N)
+        write_outputs(args.dump_outputs, {"residual_history": hist,
+                                          **({"x": xh} if rows is None else {"x_sample": xh[rows]})})
+        del xh
     secs = t1 - t0
     its = args.steps / secs
 
     spmv_avg_s = spmv_ms * 1e-3 / max(launches, 1)
     roof = spmv_roofline(A, spmv_avg_s, launches, args.traffic_json or traffic_file(n1), n1)
-    stream = measured_stream(ctx, N)
-    # the streaming ceiling measured on this box: the library's own triad over N-vectors
-    roof["measured_stream_GBs"] = stream["triad"]
-    roof["measured_copy_GBs"] = stream["copy"]
-    # the read-only stream (the sum of squares of an N-vector: 8 N bytes in, nothing out): the yardstick for a kernel that,
-    # like the SpMV, reads almost everything it moves -- the triad (two reads, one write) understates what reads can reach
-    roof["measured_read_GBs"] = stream["read"]
-    roof["moved_frac_of_measured"] = roof["moved_GBs"] / stream["triad"]
-    roof["moved_frac_of_measured_read"] = roof["moved_GBs"] / stream["read"]
+    if args.full:
+        stream = measured_stream(ctx, N)
+        # the streaming ceiling measured on this box: the library's own triad over N-vectors
+        roof["measured_stream_GBs"] = stream["triad"]
+        roof["measured_copy_GBs"] = stream["copy"]
+        # the read-only stream (the sum of squares of an N-vector: 8 N bytes in, nothing out): the yardstick for a kernel that,
+        # like the SpMV, reads almost everything it moves -- the triad (two reads, one write) understates what reads can reach
+        roof["measured_read_GBs"] = stream["read"]
+        roof["moved_frac_of_measured"] = roof["moved_GBs"] / stream["triad"]
+        roof["moved_frac_of_measured_read"] = roof["moved_GBs"] / stream["read"]
     roof["algorithmic_frac"] = roof["frac"]  # (`frac` prices SURVEY 8d's algorithmic bytes; `moved_frac` the PMC traffic)
     vec_bytes = (80 if args.precond == "j" else 64) * N  # pass B 24 N (+16 N Jacobi), pass C 40 N
     out = {
@@ -769,15 +793,37 @@ def main():
         "cg_frac_of_peak": (12 * nnz + 20 * N + vec_bytes) * its / 1e9 / HBM_PEAK_GBS,
         "residual_r0": r0, "residual_last": float(hist[-1]),
         "roofline": roof,
-        "device_state_after_timed_region": state_after_timed,
     }
+    if args.full:
+        out["device_state_after_timed_region"] = state_after_timed
     cg.free()
     ctx.set_option("spmv_valdict", -1)
-    import numpy as np
     if roof["spmv_stream"]["val_bytes"] == 8:  # the headline once more, priced on the PMC traffic (see crs_value_stream_record)
         out["crs_value_stream"] = crs_value_stream_record({"cg_iterations_per_s": its, "ms_per_step": 1e3 * secs / args.steps,
                                                            "spmv_avg_launch_ms": spmv_avg_s * 1e3, "roofline": roof})
-    if args.headline != "default" and roof["spmv_stream"]["form"] == 6:
+    if args.full:
+        full_legs(args, ctx, out, A, b, x, D, hist, headline_valdict)
+    if tuned:
+        out["placement_tuning"] = tuned
+    A.free(); b.free(); x.free()
+    if D is not None:
+        D.free()
+    if args.full:
+        full_legs_after(args, ctx, out)
+    out["options"] = ctx.options()
+    out["options"]["placement_tuning"] = ("bis_mat_tune_placement: %d trials" % args.tune_placement) if args.tune_placement > 0 else \
+        "bis_mat_tune_placement off; the library's own build-time search on the win8 stream is on (roofline.placement_search; option spmv_win8_tune)"
+    ctx.close()  # (the child processes below get the whole device)
+    if args.full and n1 == 256 and not args.no_configs:
+        out["configs"] = config_legs()
+    print(json.dumps(out), flush=True)
+
+
+def full_legs(args, ctx, out, A, b, x, D, hist, headline_valdict):
+    """--full, on the headline's arrays: the other stream formats of the same loop, the CPU baselines and the parity run."""
+    import numpy as np
+    n1 = args.size
+    if args.headline != "default" and out["roofline"]["spmv_stream"]["form"] == 6:
         leg = cg_leg(ctx, A, b, x, D, min(args.steps, 50), min(args.warmup, 5), args.traffic_json or traffic_file(n1), n1, valdict=0, win8=0)
         h3 = np.array(leg.pop("residual_history"))
         m3 = min(len(h3), len(hist))
@@ -801,7 +847,7 @@ def main():
         cb["topology"] = topo
         out["cpu_baseline"] = cb
         # parity against the CPU path on the same input over the CPU leg's WHOLE history: a fresh GPU run of as many
-        # iterations as the reference made (the timed run above covers only warmup + steps of them)
+        # iterations as the reference made (the timed run covers only warmup + steps of them)
         n_cmp = len(cpu_hist) - 1
         ctx.set_option("spmv_valdict", headline_valdict)
         ctx.init_vector(x, 0.1)
@@ -832,11 +878,11 @@ def main():
             # first touched by the threads that multiply them) on that socket
             cb3, _ = cpu_baseline(n1, args.precond, 0, threads=max(per_socket, cb["cores"]), seconds=5.0, first_touch=True)
             out["cpu_baseline_first_touch"] = cb3
-    if tuned:
-        out["placement_tuning"] = tuned
-    A.free(); b.free(); x.free()
-    if D is not None:
-        D.free()
+
+
+def full_legs_after(args, ctx, out):
+    """--full, after the headline's arrays are freed: the north-star size, config 5's SpMV, the sweeps, the CPU sweep."""
+    n1 = args.size
     if n1 == 256 and not args.no_target_512:
         info = ctx.device_info()
         if info["hbm_bytes"] >= 200e9:
@@ -849,13 +895,6 @@ def main():
         out["sweeps"] = sweep_legs(ctx)
         if not args.no_cpu_baseline:
             out["cpu_baseline_sptrsv"] = cpu_sptrsv_leg()
-    out["options"] = ctx.options()
-    out["options"]["placement_tuning"] = ("bis_mat_tune_placement: %d trials" % args.tune_placement) if args.tune_placement > 0 else \
-        "bis_mat_tune_placement off; the library's own build-time search on the win8 stream is on (roofline.placement_search; option spmv_win8_tune)"
-    ctx.close()  # (the child processes below get the whole device)
-    if n1 == 256 and not args.no_configs:
-        out["configs"] = config_legs()
-    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

@@ -94,3 +94,38 @@ def test_cpu_topology_and_sptrsv_leg():
     assert rec["kind"] in ("reference", "port") and rec["cores"] == 1
     for direction in ("forward", "backward"):
         assert rec[direction]["ms_per_sweep"] > 0 and rec[direction]["sweeps"] >= 2
+
+
+def test_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    """Without --full a run is the headline only; --steps sets the timed steps and must be at least one."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    try:
+        bench.parse()
+    except SystemExit as e:
+        assert e.code != 0
+    else:
+        raise AssertionError("--steps 0 accepted")
+
+
+def test_dump_rows_and_write_outputs(tmp_path):
+    """--dump-outputs: all rows of a short x, a fixed sorted sample of 2^21 rows of a long one, float64 files, 64 MB at most."""
+    from basic_iterative_solvers_amd.dist_bench import DUMP_ROWS, dump_rows, write_outputs
+    assert dump_rows(DUMP_ROWS) is None
+    r1, r2 = dump_rows(3 * DUMP_ROWS), dump_rows(3 * DUMP_ROWS)
+    assert r1.shape == (DUMP_ROWS,) and np.array_equal(r1, r2)
+    assert np.all(np.diff(r1) > 0) and r1[0] >= 0 and r1[-1] < 3 * DUMP_ROWS
+    write_outputs(str(tmp_path / "d"), {"residual_history": [3.0, 2.0, 1.0], "x": np.arange(5, dtype=np.float32)})
+    h, x = np.load(tmp_path / "d" / "residual_history.npy"), np.load(tmp_path / "d" / "x.npy")
+    assert h.dtype == np.float64 and list(h) == [3.0, 2.0, 1.0] and x.dtype == np.float64 and list(x) == [0, 1, 2, 3, 4]
+    try:
+        write_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    except SystemExit:
+        assert not (tmp_path / "big").exists()
+    else:
+        raise AssertionError("more than 64 MB written")

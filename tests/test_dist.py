@@ -59,16 +59,19 @@ def test_partitioned_cg_hip(world, kind, size):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,precond,matrix", [(2, "none", "hpcg"), (3, "j", "hpcg"), (2, "j", "anderson"), (3, "j", "anderson0")])
-def test_bench_multi_gpu_path_rehearsal(world, precond, matrix):
+def test_bench_multi_gpu_path_rehearsal(world, precond, matrix, tmp_path):
     """bench.py --gpus N exactly as the driver launches it (torch.distributed.run, one process
     per rank), on ONE GPU: BIS_BENCH_REHEARSE=1 puts every rank on cuda:0 with the gloo
     transport, so everything of the N > 1 bench except RCCL itself runs -- partition,
-    closed-form residual check, timed loop, max-over-ranks, the JSON line."""
+    closed-form residual check, timed loop, max-over-ranks, the JSON line, the ranks' x
+    gathered for --dump-outputs."""
     import json
+
+    import numpy as np
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--size", "48", "--steps", "6", "--warmup", "2",
-           "--precond", precond, "--target-size", "0"]
+           "--precond", precond, "--target-size", "0", "--full", "--dump-outputs", str(tmp_path)]
     if matrix.startswith("anderson"):  # BASELINE config 3's runner: the conditioned twin and the config as named
         cmd += ["--matrix", "anderson", "--shift", "9" if matrix == "anderson" else "0"]
     env = dict(os.environ, OMP_NUM_THREADS="1", BIS_BENCH_REHEARSE="1")
@@ -92,6 +95,10 @@ def test_bench_multi_gpu_path_rehearsal(world, precond, matrix):
     assert pr[0]["spmv_stream"]["val_bytes"] == 8 and j["roofline"]["algorithmic_bytes_per_launch"] == 12 * j["config"]["nnz"] + 20 * 48 ** 3
     # ... and the library's default (compressed) format for these constant-coefficient / random-diagonal operators is a leg beside it
     assert j["compressed_stream"]["per_rank"][0]["spmv_stream"]["val_bytes"] < 8 and j["compressed_stream"]["value"] > 0
+    # --dump-outputs: the history of the timed run and the whole x, the ranks' rows in order
+    h, x = np.load(tmp_path / "residual_history.npy"), np.load(tmp_path / "x.npy")
+    assert h.shape == (2 + 6 + 1,) and h[0] == j["residual_r0"] and h[-1] == j["residual_last"]
+    assert x.dtype == np.float64 and x.shape == (48 ** 3,) and np.all(np.isfinite(x))
 
 
 @pytest.mark.gpu
@@ -105,7 +112,7 @@ def test_bench_launches_its_own_ranks_and_runs_the_north_star_leg():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--size", "24", "--steps", "4", "--warmup", "1",
-                          "--target-steps", "3"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--target-steps", "3", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
