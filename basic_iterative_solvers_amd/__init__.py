@@ -37,6 +37,7 @@ def load_library():
         _lib.bis_last_error.restype = C.c_char_p
         _lib.bis_ctx_stream.restype = C.c_void_p
         _lib.bis_mat_sweep_kernel.restype = C.c_char_p
+        _lib.bis_mat_spmv_kernel.restype = C.c_char_p
     return _lib
 
 
@@ -413,6 +414,10 @@ class Mat:
     def sweep_kernel(self, backward=False):
         """Name of the kernel the last forward / backward sweep on this triangle ran (bis_mat_sweep_kernel)."""
         return self.ctx.lib.bis_mat_sweep_kernel(self.h, C.c_int(int(backward))).decode()
+
+    def spmv_kernel(self, fused=False):
+        """Name of the kernel (and template instance) the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)."""
+        return self.ctx.lib.bis_mat_spmv_kernel(self.h, C.c_int(int(fused))).decode()
 
     def retune(self):
         """Rebuild everything derived from the CRS arrays (bis_mat_retune): required after writing values in place."""

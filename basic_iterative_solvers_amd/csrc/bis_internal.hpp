@@ -77,7 +77,6 @@ struct bis_options {
     int trsv_batch = -1;   // dependencies polled per round trip (4, 8, 16; -1: by row length)
     int trsv_by_pos = -1;  // 1 (default): sentinel scratch in level order; 0: in row order
     int trsv_one_xcd = -1; // k > 0: sync-free sweeps run on one elected XCD with k workgroups per CU
-    int cg_graph = -1;      // 1: bis_cg_iterate replays one captured iteration as a hipGraph (opt-in, measured no gain)
     int tune_placement = -1; // k > 0: bis_dist_create runs bis_mat_tune_placement(A, k) before it makes the row views
     int spmv_packed32 = -1; // 1: also try the 32-window packed format (opt-in)
     int spmv_lds_pad = -1; // diagnostic: extra dynamic LDS bytes per workgroup (lowers occupancy)
@@ -206,6 +205,7 @@ struct bis_mat {
     struct bis_trsv_chain *chain_fwd = nullptr, *chain_bwd = nullptr;
     bool chain_tried_fwd = false, chain_tried_bwd = false;
     const char *sweep_kernel[2] = {"", ""}; // the kernel the last forward / backward sweep on this triangle ran (bis_mat_sweep_kernel)
+    const char *spmv_kernel[2] = {"", ""};  // the kernel the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \
@@ -332,6 +332,7 @@ void bis_spmv_sellwin_drop(bis_mat *A);
 // window + sliced-ELL form with the 8-byte values streamed (bis_spmv_sell.hip, "win8")
 bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A);
 int bis_spmv_win8_blocks(const bis_mat *A);
+int bis_spmv_win8_rows(const bis_mat *A);
 int64_t bis_spmv_win8_slices(const bis_mat *A);
 int64_t bis_spmv_win8_partials(const bis_mat *A);
 int64_t bis_spmv_win8_bytes(const bis_mat *A);

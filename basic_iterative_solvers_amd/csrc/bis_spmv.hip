@@ -951,6 +951,35 @@ int spmv_variant(const SpmvArgs &a) {
     return (a.pk_mode >= 2 && v % 10 != 0) ? 20 : v; // the lane-permute decodes need the whole wave: branch-free form only
 }
 
+// Names bis_mat_spmv_kernel reports: static strings, built once, so that a launch only stores a pointer.
+// The row-block kernel's instance as launch_by_id picks it: U staged vectors, PK the column stream (WIDE: 32-bit columns,
+// 64-bit x addressing), BR the phase-1 form; or the value-dictionary kernel.
+const char *rowblock_name(int id, const SpmvArgs &a) {
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> v;
+        for (int u : {1, 2, 4})
+            for (int pk = 0; pk < 5; ++pk)
+                for (int br = 0; br < 3; ++br)
+                    v.push_back("spmv_rowblock_kernel U=" + std::to_string(u) + " PK=" + (pk == 4 ? std::string("0 WIDE") : std::to_string(pk)) +
+                                " BR=" + std::to_string(br));
+        return v;
+    }();
+    if (a.vcode && !a.acc_y && !a.vd_rm_only && id == 20 && a.pk_mode == 1) return "spmv_rowblock_vd_kernel";
+    const int u = id / 10 == 1 ? 0 : (id / 10 == 2 ? 1 : 2), br = id % 10;
+    const int pk = a.wide ? 4 : a.pk_mode;
+    return names[(size_t)(u * 5 + pk) * 3 + br].c_str();
+}
+
+// "sellwin fmt=F", "win8 rows=R", "colslab K=k" (F 0..4, R 1..4, k up to 32)
+const char *form_name(int kind, int v) {
+    static const std::vector<std::string> names[3] = {
+        [] { std::vector<std::string> n; for (int i = 0; i <= 4; ++i) n.push_back("sellwin fmt=" + std::to_string(i)); return n; }(),
+        [] { std::vector<std::string> n; for (int i = 0; i <= 4; ++i) n.push_back("win8 rows=" + std::to_string(i)); return n; }(),
+        [] { std::vector<std::string> n; for (int i = 0; i <= 32; ++i) n.push_back("colslab K=" + std::to_string(i)); return n; }()};
+    const std::vector<std::string> &t = names[kind];
+    return t[(size_t)std::max(0, std::min(v, (int)t.size() - 1))].c_str();
+}
+
 } // namespace
 
 // The x-window variant is opt-in (spmv_window=1): measured 1.20-1.33 ms against
@@ -1461,6 +1490,7 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
                            const double *w, int *n_partials, size_t partials_off) {
     if (n_partials) *n_partials = 0;
     if (A->n_rows == 0) return BIS_OK;
+    const char *&ran = const_cast<bis_mat *>(A)->spmv_kernel[w ? 1 : 0]; // (bis_mat_spmv_kernel)
     const bool use_f = w != nullptr && !(A->win_ok && spmv_window_mode()); // fused epilogue: its own table
     const int64_t lds_doubles = (int64_t)(use_f ? A->chunk_f : A->chunk_nnz) + A->max_row_nnz + 8;
     const size_t lds_bytes = sizeof(double) * (size_t)lds_doubles;
@@ -1476,6 +1506,7 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
                                (const int32_t *)A->row_ptr, A->col, A->val, x, y, A->n_rows);
         bis_prof_end(ctx);
         BIS_HIP_CHECK(ctx, hipGetLastError());
+        ran = "spmv_wave_per_row_kernel";
         return BIS_OK;
     }
     const int nb = use_f ? A->n_blocks_f : A->n_blocks, nb8 = (nb + 7) & ~7;
@@ -1498,6 +1529,7 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
         bis_prof_end(ctx);
         BIS_HIP_CHECK(ctx, hipGetLastError());
         if (w && n_partials) *n_partials = nb * 4; // 256-thread workgroups: 4 waves
+        ran = "spmv_window_kernel";
         return BIS_OK;
     }
     SpmvArgs a{A->row_ptr, A->col, A->val, x, y, use_f ? A->blkf_row : A->blk_row,
@@ -1513,22 +1545,22 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
     {
         bool done = false;
         if (bis_status st = launch_sellwin(ctx, A, a, x, y, w ? 1 : 0, w, ctx->partials, partials_off, n_partials, &done)) return st;
-        if (done) return BIS_OK;
+        if (done) { ran = form_name(0, bis_spmv_sellwin_format(A)); return BIS_OK; }
     }
     {
         bool done = false;
         if (bis_status st = launch_rowmajor(ctx, A, a, x, y, w ? 1 : 0, w, ctx->partials, partials_off, n_partials, &done)) return st;
-        if (done) return BIS_OK;
+        if (done) { ran = "spmv_rowmajor_vd_kernel"; return BIS_OK; }
     }
     {
         bool done = false;
         if (bis_status st = launch_win8(ctx, A, a, x, y, w ? 1 : 0, w, ctx->partials, partials_off, n_partials, &done)) return st;
-        if (done) return BIS_OK;
+        if (done) { ran = form_name(1, bis_spmv_win8_rows(A)); return BIS_OK; }
     }
     {
         bool done = false;
         if (bis_status st = launch_colslab(ctx, A, a, x, y, w, partials_off, n_partials, &done)) return st;
-        if (done) return BIS_OK;
+        if (done) { ran = form_name(2, (int)A->colslabs->size()); return BIS_OK; }
     }
     if (bis_opts().spmv_lds_pad > 0) a.lds_bytes += (size_t)bis_opts().spmv_lds_pad;
     bis_prof_begin(ctx);
@@ -1538,6 +1570,7 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
     if (!ok) { ctx->err = "bis_spmv: unknown BIS_SPMV_VARIANT"; return BIS_ERR_INVALID; }
     BIS_HIP_CHECK(ctx, hipGetLastError());
     if (w && n_partials) *n_partials = nb * (fused_threads(spmv_variant(a)) / 64);
+    ran = rowblock_name(spmv_variant(a), a);
     return BIS_OK;
 }
 
@@ -1570,6 +1603,8 @@ bis_status bis_spmv_trsv_level(bis_ctx *ctx, const bis_mat *T, const double *x, 
 }
 
 extern "C" {
+
+const char *bis_mat_spmv_kernel(const bis_mat *A, int fused) { return A ? A->spmv_kernel[fused ? 1 : 0] : ""; }
 
 bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x, double *y) {
     BIS_CTX_OK(ctx);

@@ -1618,6 +1618,7 @@ void bis_spmv_win8_drop(bis_mat *A) {
 }
 
 int bis_spmv_win8_blocks(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->n_blocks : 0; }
+int bis_spmv_win8_rows(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->R : 0; }
 int64_t bis_spmv_win8_slices(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->n_slices : 0; }
 int64_t bis_spmv_win8_partials(const bis_mat *A) { return A->sw8_state == 1 ? (int64_t)A->sw8->n_blocks * 4 : 0; } // fused dot: one per wave
 // bytes of the form's own arrays one launch reads: the stream (with its padding), block headers, slice offsets

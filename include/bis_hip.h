@@ -539,6 +539,13 @@ BIS_API bis_status bis_profile_enable(bis_ctx *ctx, int on);
  * (kernels.hpp:56-58, :90-92). */
 BIS_API bis_status bis_profile_read_sweeps(bis_ctx *ctx, int64_t *sweeps, double *sweep_ms);
 BIS_API const char *bis_mat_sweep_kernel(const bis_mat *T, int backward);
+/* bis_mat_spmv_kernel names the kernel and template instance the last bis_spmv
+ * (fused = 0) or the last SpMV inside bis_cg_iterate (fused = 1) launched for A:
+ * "spmv_rowblock_kernel U=4 PK=1 BR=1", "spmv_rowblock_vd_kernel",
+ * "spmv_rowmajor_vd_kernel", "spmv_window_kernel", "spmv_wave_per_row_kernel",
+ * "sellwin fmt=4", "win8 rows=2", "colslab K=6" (static string; "" before the
+ * first call) -- which of the forced or fallen-back paths actually ran. */
+BIS_API const char *bis_mat_spmv_kernel(const bis_mat *A, int fused);
 BIS_API bis_status bis_profile_read(bis_ctx *ctx, int64_t *spmv_launches,
                                     double *spmv_ms);
 

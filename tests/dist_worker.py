@@ -181,6 +181,10 @@ def main():
         from basic_iterative_solvers_amd.launcher import route_send_lists, setup_rccl, torch_comm_ops
         torch.cuda.set_device(0)
         ctx = Context(0)
+        # optional fourth argument: library options (name=value,...) applied before bis_dist_create
+        for item in filter(None, (sys.argv[4] if len(sys.argv) > 4 else "").split(",")):
+            name, value = item.split("=")
+            ctx.set_option(name, int(value))
         dA = ctx.matrix(A_loc)
         d = Dist(ctx, dA, rank, world, row_starts)
         # the device-side halo plan (only remote entries and boundary rows leave HBM) equals the

@@ -20,10 +20,10 @@ def free_port():
     return p
 
 
-def launch(world, mode, kind, size, timeout=600):
+def launch(world, mode, kind, size, timeout=600, options=""):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "tests", "dist_worker.py"), mode, kind, str(size)]
+           os.path.join(ROOT, "tests", "dist_worker.py"), mode, kind, str(size)] + ([options] if options else [])
     env = dict(os.environ, OMP_NUM_THREADS="1")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
@@ -55,6 +55,13 @@ def test_rccl_negotiation_is_collective(world):
                                              (4, "hpcg", 8), (4, "anderson", 8)])
 def test_partitioned_cg_hip(world, kind, size):
     launch(world, "gpu", kind, size)
+
+
+@pytest.mark.gpu
+def test_partitioned_cg_hip_host_plan_and_placement_tuning():
+    """The partitioned CG with the halo planned on the host (dist_host_plan=1) and the placement tuned before the row
+    views are made (tune_placement=2): the assertions of the GPU cases above."""
+    launch(2, "gpu", "hpcg", 12, options="dist_host_plan=1,tune_placement=2")
 
 
 @pytest.mark.gpu
