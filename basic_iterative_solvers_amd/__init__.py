@@ -38,6 +38,7 @@ def load_library():
         _lib.bis_ctx_stream.restype = C.c_void_p
         _lib.bis_mat_sweep_kernel.restype = C.c_char_p
         _lib.bis_mat_spmv_kernel.restype = C.c_char_p
+        _lib.bis_mat_ilu0_kernel.restype = C.c_char_p
     return _lib
 
 
@@ -418,6 +419,10 @@ class Mat:
     def spmv_kernel(self, fused=False):
         """Name of the kernel (and template instance) the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)."""
         return self.ctx.lib.bis_mat_spmv_kernel(self.h, C.c_int(int(fused))).decode()
+
+    def ilu0_kernel(self):
+        """Name of the elimination kernel that factorised this ILU(0) L factor (bis_mat_ilu0_kernel); "" for other matrices."""
+        return self.ctx.lib.bis_mat_ilu0_kernel(self.h).decode()
 
     def retune(self):
         """Rebuild everything derived from the CRS arrays (bis_mat_retune): required after writing values in place."""

@@ -115,16 +115,26 @@ __global__ __launch_bounds__(256) void ilu0_level_kernel(const RP *__restrict__ 
     if (t >= end) return;
     const int i = perm[t];
     const int64_t s = rp[i], e = rp[i + 1];
+    // A repeated column is ONE value, as in the reference's workspace (one w[j] per column): the copy stored last wins the
+    // scatter -- the sort is stable, so that is the last copy of the group -- and the group's first copy holds the value.
+    for (int64_t p = s + 1; p < e; ++p)
+        if (wcol[p] == wcol[p - 1]) {
+            int64_t g = p - 1;
+            while (g > s && wcol[g - 1] == wcol[p]) --g;
+            wval[g] = wval[p];
+        }
+    int64_t g = s; // first copy of the current column
     for (int64_t p = s; p < e; ++p) {
         const int k = wcol[p];
         if (k >= i) break;
+        if (p == s || wcol[p - 1] != k) g = p;
         const double pivot = U_D[k]; // row k finished in an earlier level
         if (fabs(pivot) < 1e-16) continue;
-        const double factor = wval[p] / pivot;
-        wval[p] = factor;
-        for (int64_t q = ustart[k]; q < (int64_t)rp[k + 1]; ++q) {
+        const double factor = wval[g] / pivot; // a repeated k is eliminated once per copy: divided again the second time
+        wval[g] = factor;
+        for (int64_t q = ustart[k]; q < (int64_t)rp[k + 1]; ++q) { // a repeated j of row k: one update per copy
             const int j = wcol[q];
-            int64_t lo = p + 1, hi = e; // j > k: search the rest of row i
+            int64_t lo = p + 1, hi = e; // j > k: search the rest of row i for the first copy of j
             while (lo < hi) {
                 const int64_t mid = (lo + hi) >> 1;
                 if (wcol[mid] < j) lo = mid + 1; else hi = mid;
@@ -132,9 +142,11 @@ __global__ __launch_bounds__(256) void ilu0_level_kernel(const RP *__restrict__ 
             if (lo < e && wcol[lo] == j && wval[lo] != 0.0) wval[lo] = fma(-factor, wval[q], wval[lo]);
         }
     }
-    double u_diag = dpos[i] >= 0 ? wval[dpos[i]] : 0.0;
+    double u_diag = dpos[i] >= 0 ? wval[dpos[i]] : 0.0; // (dpos: the first copy)
     if (fabs(u_diag) < pivot_tol) u_diag = (u_diag >= 0 ? 1.0 : -1.0) * pivot_repl;
     if (dpos[i] >= 0) wval[dpos[i]] = u_diag;
+    for (int64_t p = s + 1; p < e; ++p) // every copy leaves with the group's value
+        if (wcol[p] == wcol[p - 1]) wval[p] = wval[p - 1];
     U_D[i] = u_diag;
     L_D[i] = 1.0;
 }
@@ -320,8 +332,10 @@ __global__ __launch_bounds__(256, 4) void ilu0_persistent_kernel(const RP *__res
     }
 }
 
-// rows of the sorted copy with a repeated column: the wave-per-row kernel locates ONE entry per column by binary search,
-// the reference's serial loop updates every copy -- such matrices take the lane-per-row kernel
+// rows of the sorted copy with a repeated column: the reference keeps one workspace value per column (the copy stored last
+// wins, a repeated k is eliminated once per copy, a repeated j of a U row updates once per copy, every copy leaves with the
+// shared value).  The lane-per-row kernel reproduces that on the group's first copy; the wave-per-row kernels locate one
+// entry per column and update it from several lanes at once -- such matrices take the lane-per-row kernel
 template <typename RP>
 __global__ __launch_bounds__(256) void dup_check_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ wcol, int64_t n, int *flag) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -381,6 +395,7 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
     st = bis_trsv_level_sets(ctx, Lp, &level_ptr, &perm);
     const bool wave_ok = W->max_row_nnz <= kIluMaxRow && bis_opts().ilu0_wave != 0 && !has_dups;
     bool done = false;
+    const char *ran = wave_ok ? "ilu0_level_wave_kernel" : "ilu0_level_kernel"; // (bis_mat_ilu0_kernel)
     if (st == BIS_OK && wave_ok && bis_opts().ilu0_persistent != 0 && n > 0) {
         // one launch: rows in level order over a resident grid, a flag per finished row (see the kernel)
         const int mr = std::max(W->max_row_nnz, 1);
@@ -406,6 +421,7 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
             if (le != hipSuccess) { ctx->err = std::string("bis_mat_ilu0: ") + hipGetErrorString(le); st = BIS_ERR_HIP; }
             else if (bis_status fs = bis_fault_check(ctx)) st = fs;
             done = true;
+            ran = "ilu0_persistent_kernel";
         } else {
             (void)hipGetLastError();
             hipFree(flag);
@@ -429,6 +445,7 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
     }
     if (st == BIS_OK) st = bis_mat_split_strict_impl(ctx, W, Ls_out, Us_out, nullptr, nullptr, false);
     if (st == BIS_OK) bis_trsv_plan_adopt(*Ls_out, Lp, false); // same pattern: L's forward sweep starts from the levels found above
+    if (st == BIS_OK) (*Ls_out)->ilu0_kernel = ran;
     bis_mat_destroy(ctx, Lp);
     bis_mat_destroy(ctx, Up);
     return cleanup(st);
@@ -437,6 +454,8 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
 } // namespace
 
 extern "C" {
+
+const char *bis_mat_ilu0_kernel(const bis_mat *L_strict) { return L_strict ? L_strict->ilu0_kernel : ""; }
 
 bis_status bis_mat_ilu0(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot_repl,
                         bis_mat **L_strict, bis_mat **U_strict, double *L_D, double *U_D) {

@@ -206,6 +206,7 @@ struct bis_mat {
     bool chain_tried_fwd = false, chain_tried_bwd = false;
     const char *sweep_kernel[2] = {"", ""}; // the kernel the last forward / backward sweep on this triangle ran (bis_mat_sweep_kernel)
     const char *spmv_kernel[2] = {"", ""};  // the kernel the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)
+    const char *ilu0_kernel = "";           // the elimination kernel that made this ILU(0) L factor (bis_mat_ilu0_kernel)
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \

@@ -312,6 +312,10 @@ BIS_API bis_status bis_vec_scatter(bis_ctx *ctx, double *out, const double *in,
 BIS_API bis_status bis_mat_ilu0(bis_ctx *ctx, const bis_mat *A, double pivot_tol,
                                 double pivot_repl, bis_mat **L_strict,
                                 bis_mat **U_strict, double *L_D, double *U_D);
+/* bis_mat_ilu0_kernel names the elimination kernel that factorised the L_strict
+ * returned by bis_mat_ilu0: "ilu0_persistent_kernel", "ilu0_level_wave_kernel"
+ * or "ilu0_level_kernel" (static string; "" for any other matrix). */
+BIS_API const char *bis_mat_ilu0_kernel(const bis_mat *L_strict);
 
 /* ---- the operator surface (kernels.hpp) ------------------------------------ */
 /* spmv / native_spmv, kernels.hpp:22-52: y = A x. */

@@ -232,11 +232,234 @@ def histories_r4(ref, orc):
     return out
 
 
+# ILU(0) on adversarial patterns (--ilu-edges-only): the reference's factor_ILU0_old on inputs the solver matrices never
+# are -- missing, zero, -0.0 and near-tolerance diagonals, empty rows, entries that cancel to 0, unsorted and unsymmetric
+# rows, long rows, rows at the wave kernel's 1024-entry limit, repeated columns, a long dependency chain.  Values are
+# dyadic where the pattern allows (power-of-two pivots, small integers), so that every operation is exact and any correctly
+# rounded implementation -- fma or not -- gives the same bits; `exact` records, per case, whether that held (checked op by
+# op below).  golden_ilu_edges.npz, data only: input CRS, the reference's factors and its ILU(0) apply of a fixed vector.
+ILU_EDGES_MTX = "ilu_dups.mtx"
+
+
+def _rows_crs(rows, n=None):
+    """CRS from rows given as lists of (column, value) in stored order."""
+    n = len(rows) if n is None else n
+    rp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    col = np.array([c for r in rows for c, _ in r], dtype=np.int32)
+    val = np.array([v for r in rows for _, v in r], dtype=np.float64)
+    return CRS(n, rp, col, val)
+
+
+def _band_rows(n, half, diag=8.0):
+    return [[(j, diag if j == i else (-1.0 if (i + j) % 2 else 0.5)) for j in range(max(0, i - half), min(n, i + half + 1))]
+            for i in range(n)]
+
+
+def _two_level(rng, n_src, n_dep, dep_len, src_ulen, extra=None):
+    """Rows 0..n_src-1 ("sources") have no L entries, a power-of-two diagonal and U entries to later columns; the dependent
+    rows after them eliminate against sources only -- every pivot is a power of two and every update exact.  dep_len /
+    src_ulen: row index -> number of L entries / of U entries."""
+    n = n_src + n_dep
+    rows = []
+    for i in range(n_src):
+        k = min(src_ulen(i), n - i - 1)
+        cols = np.sort(rng.choice(np.arange(i + 1, n), size=k, replace=False)) if k else []
+        rows.append([(i, float(2.0 ** int(rng.integers(1, 4))))] + [(int(c), float(rng.integers(-3, 4))) for c in cols])
+    for i in range(n_src, n):
+        k = min(dep_len(i), n_src)
+        cols = np.sort(rng.choice(n_src, size=k, replace=False)) if k else []
+        r = [(int(c), float(rng.integers(-4, 5))) for c in cols] + [(i, 64.0)]
+        if i + 1 < n:
+            r.append((i + 1, 1.0))
+        rows.append(r)
+    return rows
+
+
+def _q(x):
+    """Random values on a grid of 2^-10: as irregular as uniform ones for the factorisation, but they compress."""
+    return np.round(np.asarray(x) * 1024.0) / 1024.0
+
+
+def _random_pattern(rng, n, band, p_far, max_len, p_dup, p_zero, p_tiny):
+    """Unsymmetric, unsorted: a band plus far entries, some repeated columns, explicit zeros, tiny or missing diagonals."""
+    rows = []
+    for i in range(n):
+        k = int(rng.integers(1, max_len + 1))
+        c = set(int(v) for v in rng.integers(max(0, i - band), min(n, i + band + 1), size=k))
+        if rng.random() < p_far:
+            c.add(int(rng.integers(0, n)))
+        c.add(i)
+        r = [(j, float(_q(rng.uniform(-1, 1)))) for j in c]
+        for t, (j, v) in enumerate(r):
+            if j == i:
+                u = rng.random()
+                r[t] = (j, 6.0 + v if u > p_tiny else [1e-9, -1e-9, 0.0, -0.0, 1e-17][int(rng.integers(0, 5))])
+            elif rng.random() < p_zero:
+                r[t] = (j, 0.0)
+        if rng.random() < p_tiny / 2:
+            r = [e for e in r if e[0] != i]  # no diagonal
+        if r and rng.random() < p_dup:
+            r.append((r[int(rng.integers(0, len(r)))][0], float(_q(rng.uniform(-1, 1)))))
+        order = rng.permutation(len(r))
+        rows.append([r[t] for t in order])
+    return rows
+
+
+def ilu_edge_cases():
+    """[(name, CRS)] -- the catalogue, deterministic."""
+    rng = np.random.default_rng(20261016)
+    tol = 1e-8
+    below = float(np.nextafter(tol, 0.0))
+    cases = []
+    add = lambda name, rows, n=None: cases.append((name, _rows_crs(rows, n)))  # noqa: E731
+    # -- pivots: |u_ii| < tol -> sign(u_ii) * repl; the rows that meet them are eliminated against power-of-two pivots
+    add("no_diag", [[(0, 4.0), (1, 1.0)], [(0, 2.0), (2, 1.0)], [(1, 2.0), (2, 8.0)], [(3, 2.0)]])
+    add("zero_diag", [[(0, 4.0), (2, 1.0)], [(1, 0.0), (2, 2.0)], [(0, 1.0), (1, 2.0), (2, 4.0)]])
+    add("negzero_diag", [[(0, 4.0), (1, 2.0)], [(0, 1.0), (1, -0.0)], [(1, 2.0), (2, -0.0)], [(3, 8.0)]])
+    add("tol_diag", [[(0, tol)], [(1, -tol)], [(2, below)], [(3, -below)], [(4, 2.0 * tol)], [(5, -2.0 * tol)],
+                     [(6, 4.0), (7, 2.0)], [(6, 2.0), (7, 1.0)], [(8, 4.0), (9, -2.0)], [(8, 2.0), (9, -1.0)],
+                     [(10, 4.0), (11, 1.0)], [(10, -1.0), (11, -0.25)]])
+    # (row 7: 1 - 0.5 * 2 = +0 -> +repl; row 9: -1 - 0.5 * -2 = +0; row 11: -0.25 + 0.25 * 1 = +0 -- and -0.0 above)
+    add("tiny_diag", [[(0, 1e-17), (1, 1.0)], [(0, 2.0), (1, 4.0)], [(0, -1e-20), (1, 1.0), (2, -1e-300)],
+                      [(2, 4.0), (3, 8.0)]])
+    # -- empty rows: the first, one inside, the last
+    add("empty_rows", [[], [(1, 4.0), (2, 1.0)], [(1, 2.0), (2, 8.0), (4, 1.0)], [], [(2, 1.0), (3, 2.0), (4, 4.0)], []])
+    # -- cancellation: row 3's column 4 becomes exactly 0 after the elimination with row 0, so row 1's update skips it;
+    #    explicit zeros in L and U positions
+    add("cancel_to_zero", [[(0, 4.0), (4, 2.0)], [(1, 2.0), (4, 1.0)], [(2, 8.0), (3, 0.0)],
+                           [(0, 2.0), (1, 2.0), (3, 8.0), (4, 1.0)], [(0, 0.0), (2, 0.0), (4, 16.0)]])
+    # -- unsorted rows: reversed, shuffled (a band of half-width 3; 8 on the diagonal)
+    band = _band_rows(40, 3)
+    add("unsorted_reverse", [list(reversed(r)) for r in band])
+    add("unsorted_shuffled", [[r[t] for t in rng.permutation(len(r))] for r in band])
+    # -- structurally unsymmetric: U rows with columns the dependent row lacks, L entries whose U row is empty
+    add("unsymmetric", [[(0, 4.0), (2, 1.0), (3, 2.0), (5, 1.0)], [(1, 2.0)], [(0, 2.0), (1, 1.0), (2, 8.0)],
+                        [(3, 4.0)], [(1, 4.0), (3, 1.0), (4, 2.0)], [(0, 1.0), (4, 1.0), (5, 4.0)]])
+    # -- long rows: L parts of 63, 64, 65, 128, 129 entries, U rows longer than 64 (multi-chunk sort and wave paths)
+    lens = {200: 63, 201: 64, 202: 65, 203: 128, 204: 129}
+    rows = _two_level(rng, 150, 60, lambda i: lens.get(i, 3), lambda i: 70 if i % 10 == 0 else 2)
+    for i in lens:
+        rows[i] = [rows[i][t] for t in rng.permutation(len(rows[i]))]
+    add("long_rows", rows)
+    # -- the wave kernels' limit: a row of exactly 1024 entries stays on the wave path, 1025 falls to the lane kernel
+    for name, m in (("row_1024", 1024), ("row_1025", 1025)):
+        rows = _two_level(rng, 1100, 20, lambda i: 2, lambda i: 1)
+        rows[1110] = [(int(c), 1.0) for c in range(m - 2)] + [(1110, 64.0), (1111, 1.0)]
+        add(name, rows)
+    # -- repeated columns, each kind in a matrix of its own
+    add("dup_k", [[(0, 4.0), (1, 1.0)], [(0, 2.0), (0, 1.0), (1, 8.0)]])
+    add("dup_diag", [[(0, 4.0), (1, 1.0)], [(0, 2.0), (1, 8.0), (1, 2.0)]])
+    add("dup_diag_via_u", [[(0, 4.0), (2, 1.0)], [(1, 4.0)], [(0, 2.0), (2, 8.0), (2, 1.0)]])
+    add("dup_u", [[(0, 4.0), (2, 1.0), (2, 2.0), (3, 1.0)], [(1, 8.0)], [(2, 8.0), (3, 2.0)],
+                  [(0, 2.0), (2, 4.0), (3, 16.0)]])
+    add("dup_three", [[(0, 2.0), (1, 1.0)], [(1, 4.0), (2, 2.0)], [(0, 1.0), (1, 2.0), (2, 8.0), (1, 4.0), (1, 1.0)],
+                      [(3, 2.0), (1, 1.0), (3, 4.0), (3, 8.0)]])
+    add("dup_nonadjacent", [[(0, 4.0), (2, 4.0)], [(1, 8.0), (3, 1.0)], [(2, 3.25), (0, 2.0), (1, 4.0), (0, 1.0), (3, 0.5)],
+                            [(3, 8.0), (1, 2.0), (2, 4.0), (1, -2.0)]])
+    rows = _two_level(rng, 100, 30, lambda i: 80 if i == 110 else 3, lambda i: 2)
+    rows[110] = rows[110] + [(rows[110][5][0], 2.0), (rows[110][40][0], -1.0)]
+    rows[110] = [rows[110][t] for t in rng.permutation(len(rows[110]))]
+    add("dup_long_row", rows)
+    # -- a long dependency chain: bidiagonal plus random earlier columns (the persistent kernel waits on its flags)
+    n = 2500
+    rows = []
+    for i in range(n):
+        r = {i: 8.0}
+        if i:
+            r[i - 1] = -1.0
+        for c in rng.integers(0, i, size=min(i, 1)) if i else []:
+            r[int(c)] = 0.5
+        if i + 1 < n:
+            r[i + 1] = -1.0
+        rows.append(list(r.items()))
+    add("chain_2500", rows)
+    # -- random-valued versions at a few thousand rows
+    add("rand_unsorted_dups", _random_pattern(rng, 1200, 6, 0.1, 4, 0.05, 0.05, 0.02))
+    add("rand_unsymmetric", _random_pattern(rng, 1200, 40, 0.3, 3, 0.0, 0.02, 0.01))
+    rows = _random_pattern(rng, 1000, 4, 0.0, 3, 0.02, 0.02, 0.01)
+    for i in range(250, 1000, 250):
+        extra = [(int(c), float(_q(rng.uniform(-1, 1)))) for c in rng.choice(i, size=70 + i // 100, replace=False)]
+        rows[i] = rows[i] + extra
+        rows[i - 150] = rows[i - 150] + [(int(c), float(_q(rng.uniform(-1, 1)))) for c in
+                                         rng.choice(np.arange(i - 149, 1000), size=80, replace=False)]
+    add("rand_long_rows", rows)
+    return cases
+
+
+def ilu0_exact(A, pivot_tol=1e-8, pivot_repl=1e-4):
+    """factor_ILU0_old in Python floats, checking every operation for exactness: True if no operation rounded (then
+    fma and mul-then-subtract agree and the factors are the same bits on any correctly rounded implementation)."""
+    from fractions import Fraction as F
+    n = A.n_rows
+    U_rows, U_D = [None] * n, [0.0] * n
+    for i in range(n):
+        w, idx = {}, []
+        for p in range(A.row_ptr[i], A.row_ptr[i + 1]):
+            w[int(A.col[p])] = float(A.val[p])
+            idx.append(int(A.col[p]))
+        idx.sort()
+        for k in idx:
+            if k >= i:
+                break
+            pivot = U_D[k]
+            if abs(pivot) < 1e-16:
+                continue
+            f = w[k] / pivot
+            if F(f) * F(pivot) != F(w[k]):
+                return False
+            w[k] = f
+            for j, u in U_rows[k]:
+                if w.get(j, 0.0) != 0.0:
+                    r = w[j] - f * u
+                    if F(r) != F(w[j]) - F(f) * F(u):
+                        return False
+                    w[j] = r
+        u_diag = w[i] if i in w else 0.0
+        if abs(u_diag) < pivot_tol:
+            u_diag = (1.0 if u_diag >= 0 else -1.0) * pivot_repl
+        U_D[i] = u_diag
+        U_rows[i] = [(j, w[j]) for j in idx if j > i]
+    return True
+
+
+def ilu_edges(ref, orc):
+    cases = ilu_edge_cases()
+    # the host-CLI fixture: a diagonally dominant matrix whose .mtx splits some entries over two lines
+    cases.append(("mtx_dups", ref.read_mtx(os.path.join(HERE, ILU_EDGES_MTX))))
+    d = {"names": np.array([c[0] for c in cases]), "exact": np.zeros(len(cases), dtype=np.int8)}
+    for t, (name, A) in enumerate(cases):
+        n = A.n_rows
+        pack(name + "__A", A, d)
+        Ls, L_D, Us, U_D = ref.factor_ilu0(A)
+        pack(name + "__Ls", Ls, d)
+        pack(name + "__Us", Us, d)
+        d[name + "__LD"], d[name + "__UD"] = L_D, U_D
+        y = _q(np.random.default_rng(1000 + t).uniform(-1, 1, n))
+        d[name + "__y"] = y
+        d[name + "__pc_ilu0"] = ref.apply_preconditioner("ilu0", Ls, Us, None, None, L_D, U_D, y)
+        d["exact"][t] = ilu0_exact(A)
+        # the oracle is the spec the GPU tests use where the reference is absent: it must be the reference
+        oLs, oL_D, oUs, oU_D = orc.factor_ilu0(A)
+        same = all(np.array_equal(a, b) for a, b in ((oLs.row_ptr, Ls.row_ptr), (oLs.col, Ls.col), (oLs.val, Ls.val),
+                                                     (oUs.row_ptr, Us.row_ptr), (oUs.col, Us.col), (oUs.val, Us.val),
+                                                     (oL_D, L_D), (oU_D, U_D)))
+        lens = np.diff(A.row_ptr)
+        print(f"{name}: {n} rows, {A.nnz} nnz, longest row {lens.max(initial=0)}, exact {bool(d['exact'][t])}, "
+              f"oracle == reference {same}", flush=True)
+        assert same, name
+    np.savez_compressed(os.path.join(HERE, "golden_ilu_edges.npz"), **d)
+    return cases
+
+
 def main():
     ref, orc = Ref(), Oracle()
     if "--r4-only" in sys.argv:  # leaves the earlier fixtures as they are
         h = histories_r4(ref, orc)
         print(f"wrote {len(h)} round-4 histories")
+        return
+    if "--ilu-edges-only" in sys.argv:  # leaves the other fixtures as they are
+        c = ilu_edges(ref, orc)
+        print(f"wrote {len(c)} ILU(0) edge cases")
         return
     if "--mid-only" in sys.argv:  # leaves the small fixtures as they are
         h = histories_mid(ref, orc)

@@ -20,6 +20,26 @@ def crs_of(g, prefix):
     return CRS(len(rp) - 1, rp, g[prefix + "_col"], g[prefix + "_val"])
 
 
+def load_ilu_edges():
+    """The ILU(0) edge-case fixture (tests/golden/make_golden.py --ilu-edges-only): {case: dict(A, Ls, Us, L_D, U_D, y,
+    pc_ilu0, exact)} -- input CRS, the reference's factor_ILU0_old factors, its ILU(0) apply of y, and whether every
+    operation of the factorisation is exact (then any correctly rounded implementation gives the same bits)."""
+    g = np.load(os.path.join(GOLDEN, "golden_ilu_edges.npz"))
+    out = {}
+    for name, exact in zip(g["names"], g["exact"]):
+        name = str(name)
+        out[name] = dict(A=crs_of(g, name + "__A"), Ls=crs_of(g, name + "__Ls"), Us=crs_of(g, name + "__Us"),
+                         L_D=g[name + "__LD"], U_D=g[name + "__UD"], y=g[name + "__y"], pc_ilu0=g[name + "__pc_ilu0"],
+                         exact=bool(exact))
+    return out
+
+
+def has_repeated_column(A):
+    """Some row of A holds a column more than once."""
+    return any(len(np.unique(A.col[A.row_ptr[r]:A.row_ptr[r + 1]])) < A.row_ptr[r + 1] - A.row_ptr[r]
+               for r in range(A.n_rows))
+
+
 def load_histories():
     with open(os.path.join(GOLDEN, "histories.json")) as f:
         return json.load(f)

@@ -206,6 +206,19 @@ def test_cli_fem_generator_histories_vs_oracle(oracle, solver, pc):
         assert abs(r["iters"] - o["iters"]) <= 1
 
 
+def test_cli_mtx_with_repeated_entries_bi_ilu0_vs_oracle(oracle):
+    """An .mtx that splits entries over two lines: the reader keeps both (convert_coo_to_crs), the SpMV sums them and
+    ILU(0) takes the later one (factor_ILU0_old scatters the row into one workspace value per column).  The CLI's
+    -bi -p ilu0 history against the reference algorithm on the CRS the reference's reader built (golden_ilu_edges.npz)."""
+    from helpers import load_ilu_edges
+    MATRIX_ARG["ilu_dups"] = os.path.join(GOLDEN, "ilu_dups.mtx")
+    r = run_cli("ilu_dups", "bi", "ilu0", {})
+    o = oracle.solve(load_ilu_edges()["mtx_dups"]["A"], "bi", "ilu0", ilu_real=True)
+    e = dict(hist=[float(v) for v in o["hist"]], iters=o["iters"], converged=o["converged"])
+    assert abs(r["hist"][0] - e["hist"][0]) <= 1e-13 * e["hist"][0]
+    check_history(r, e, "bi")
+
+
 @pytest.mark.parametrize("name,solver,pc", [("hpcg8", "gm", "gs"), ("hpcg8", "cg", "sgs"),
                                             ("anderson8_shift9", "bi", "ilu0"),
                                             ("anderson8_shift9", "gs", "none"),

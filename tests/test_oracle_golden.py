@@ -5,8 +5,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (GOLDEN, GOLDEN_MATS, check_history, crs_of, load_golden,
-                     load_histories, load_histories_mid, load_histories_r4, gen_from_cli_arg, parse_hist_key, relerr)
+from helpers import (GOLDEN, GOLDEN_MATS, check_history, crs_of, has_repeated_column, load_golden, load_histories,
+                     load_histories_mid, load_histories_r4, load_ilu_edges, gen_from_cli_arg, parse_hist_key, relerr)
 from oracle.pyoracle import CRS
 
 KTOL = 1e-13  # kernel-level relative tolerance (SURVEY.md 8d parity gate)
@@ -107,6 +107,52 @@ def test_ilu0_factors_vs_golden(oracle, name):
     out = oracle.apply_preconditioner("ilu0", Ls, Us, g["A_D"], g["A_D_inv"],
                                       L_D, U_D, g["y"])
     assert relerr(out, g["pc_ilu0"]) <= 1e-12
+
+
+_ILU_EDGES = load_ilu_edges()
+
+
+@pytest.mark.parametrize("name", sorted(_ILU_EDGES))
+def test_ilu0_edge_cases_vs_golden(oracle, name):
+    """factor_ILU0_old on the adversarial catalogue (missing / zero / -0.0 / near-tolerance diagonals, empty rows, entries
+    that cancel to 0, unsorted and unsymmetric rows, long rows, repeated columns, a long chain): the oracle, which the
+    GPU tests use as the specification where the reference is absent, is the reference -- patterns and L_D / U_D exactly,
+    values bit for bit where every operation is exact and within 1e-13 elsewhere; the ILU(0) apply within 1e-12."""
+    c = _ILU_EDGES[name]
+    Ls, L_D, Us, U_D = oracle.factor_ilu0(c["A"])
+    for got, want in ((Ls, c["Ls"]), (Us, c["Us"])):
+        assert np.array_equal(got.row_ptr, want.row_ptr) and np.array_equal(got.col, want.col)
+        if c["exact"]:
+            assert np.array_equal(got.val.view(np.uint64), want.val.view(np.uint64))
+        else:
+            assert relerr(got.val, want.val) <= KTOL
+    assert np.array_equal(L_D, c["L_D"]) and np.array_equal(U_D.view(np.uint64), c["U_D"].view(np.uint64))
+    out = oracle.apply_preconditioner("ilu0", Ls, Us, None, None, L_D, U_D, c["y"])
+    assert relerr(out, c["pc_ilu0"]) <= 1e-12
+
+
+def test_mtx_reader_keeps_repeated_entries(oracle):
+    """ilu_dups.mtx splits five entries over two lines: the reader keeps every line (stable sort by row), as the
+    reference's reader built the fixture's CRS."""
+    A = oracle.read_mtx(os.path.join(GOLDEN, "ilu_dups.mtx"))
+    want = _ILU_EDGES["mtx_dups"]["A"]
+    assert np.array_equal(A.row_ptr, want.row_ptr) and np.array_equal(A.col, want.col) and np.array_equal(A.val, want.val)
+    assert has_repeated_column(A) and A.nnz == 100
+
+
+def test_ilu0_edge_catalogue_covers_the_issue():
+    """The catalogue keeps its adversarial content: repeated columns, rows at and past the wave kernels' 1024-entry limit,
+    rows longer than 64, empty rows, missing diagonals, unsorted rows, and cases whose factors are compared bit for bit."""
+    lens = {k: np.diff(c["A"].row_ptr) for k, c in _ILU_EDGES.items()}
+    assert lens["row_1024"].max() == 1024 and lens["row_1025"].max() == 1025
+    assert all(has_repeated_column(_ILU_EDGES[k]["A"]) for k in _ILU_EDGES if k.startswith("dup_") or k == "mtx_dups")
+    assert not any(has_repeated_column(_ILU_EDGES[k]["A"]) for k in ("row_1024", "long_rows", "chain_2500"))
+    assert any(v.max() > 128 for v in lens.values()) and any((v == 0).any() for v in lens.values())
+    assert sum(c["exact"] for c in _ILU_EDGES.values()) >= 10
+    A = _ILU_EDGES["unsorted_reverse"]["A"]
+    assert np.any(np.diff(A.col[A.row_ptr[5]:A.row_ptr[6]]) < 0)
+    A = _ILU_EDGES["no_diag"]["A"]
+    assert 1 not in A.col[A.row_ptr[1]:A.row_ptr[2]]
 
 
 _H = load_histories()
