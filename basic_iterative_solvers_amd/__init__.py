@@ -405,6 +405,14 @@ class Mat:
         self.ctx.lib.bis_mat_win8_tuning(self.h, C.byref(t), C.byref(a), C.byref(b))
         return t.value, a.value, b.value
 
+    def win8_layout(self):
+        """(chunks, explicit chunks, slices, blocks, implied) of the matrix' window + sliced-ELL stream (bis_mat_win8_layout);
+        zeros without one."""
+        ch, ex, sl = C.c_int64(), C.c_int64(), C.c_int64()
+        bl, im = C.c_int(), C.c_int()
+        self.ctx.lib.bis_mat_win8_layout(self.h, C.byref(ch), C.byref(ex), C.byref(sl), C.byref(bl), C.byref(im))
+        return ch.value, ex.value, sl.value, bl.value, bool(im.value)
+
     def colslab_info(self):
         """(K, one-pass ms, K-passes ms): the column slabs the SpMV of this matrix runs on (0: none) and the build-time trial's
         times (bis_mat_colslab_info)."""

@@ -724,14 +724,14 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
     // between two levels of the kernel's time, 13 % apart (HPCG-256: 0.755 / 0.855 ms, constant over time for an allocation,
     // independent of where x and y lie; tools/win8_place2.py, profiles/r05_f_win8_placement.log): candidates are copies of the
     // stream in fresh allocations, the earlier ones held so that the next lands elsewhere; the search ends at the first
-    // candidate the kernel reads at >= 5.9 TB/s (the fast level: 6.0-6.5; the library runs the same search by itself when it
-    // builds the stream -- bis_spmv_sell.hip w8_tune_placement -- so this normally finds the fast level in place).
+    // candidate of the fast level (bis_spmv_win8_fast; the library runs the same search by itself when it builds the
+    // stream -- bis_spmv_sell.hip w8_tune_placement -- so this normally finds the fast level in place).
     if (st == BIS_OK && A->sw8_state == 1 && bis_spmv_win8_stream_bytes(A) > 0) {
         int w8_form = 0;
         if (bis_mat_spmv_stream_info(ctx, A, nullptr, nullptr, nullptr, &w8_form) == BIS_OK && w8_form == 6) {
             const size_t bytes = bis_spmv_win8_stream_bytes(A);
             std::vector<void *> losers;
-            auto fast_enough = [&](double ms) { return (double)bytes / (ms * 1e-3) >= 5.9e12; };
+            auto fast_enough = [&](double ms) { return bis_spmv_win8_fast(A, ms); };
             for (int trial = 0; st == BIS_OK && trial < max_trials && !fast_enough(best); ++trial) {
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)4 << 30)) break; // keep 4 GiB for the caller

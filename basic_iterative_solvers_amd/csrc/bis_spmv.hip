@@ -1651,7 +1651,7 @@ bis_status bis_mat_spmv_stream_info(bis_ctx *ctx, const bis_mat *A, int *col_byt
         }
     }
     if (f == 6) {
-        if (col_bytes) *col_bytes = 2;
+        if (col_bytes) *col_bytes = 2; // (also with implied slots: col_bytes 0 names the row-mask form; bis_mat_win8_layout tells them apart)
         if (val_bytes) *val_bytes = 8;
         if (n_dict) *n_dict = 0;
         if (form) *form = 6;

@@ -58,6 +58,13 @@ struct bis_sellwin {
     unsigned long long *pair_key = nullptr; // fmt 3 / 4: [256] the pairs, ascending (sw_pair_key: column - row, then value code)
     uint16_t *row_of = nullptr;      // win8: [n_blocks * 256 R] row (in its block) of every position of the block's length order
     void *own_codes = nullptr;       // win8: the library's own stream while a debugging caller has redirected `codes` (bis_mat_win8_debug_stream)
+    // win8 with implied slots: ONE buffer (`codes`: placement search and swaps move it whole) = the values, 2048 bytes per chunk,
+    // then at byte w8_desc the [total_chunks + 1] 8-byte chunk descriptors (4 slot bases of the chunk's entries), then at byte
+    // w8_side the [expl_chunks] 512-byte slot records of the chunks of explicit slices; w8_end bytes in all
+    size_t w8_desc = 0, w8_side = 0, w8_end = 0;
+    int64_t *slice_rec = nullptr;     // win8 with implied slots: [n_slices + 1] slot record of each slice's first chunk (exclusive scan)
+    int64_t expl_chunks = 0;          // win8 with implied slots: chunks that keep their slots (total_chunks when the layout is today's)
+    int64_t win_gran_sum = 0;         // win8: granules of all the blocks' windows (x bytes a launch copies into LDS / 64)
     int tune_trials = 0;             // win8: placement tuning at build time (re-allocations tried), the kernel's time on the first
     double tune_first_ms = 0.0, tune_kept_ms = 0.0; // allocation and on the one kept
     int R = 1;                       // rows per lane: a block is 256 R rows
@@ -1253,6 +1260,7 @@ bis_status bis_spmv_sellwin_launch(bis_ctx *ctx, const bis_mat *A, const double 
 namespace {
 
 constexpr int kW8ChunkBytes = 2560;
+constexpr int kW8ValBytes = 2048; // a chunk of the implied-slot layout: its values only
 
 
 constexpr int kW8Runs = 64;     // runs of the window per block at most (header: 2 x 64 words)
@@ -1403,14 +1411,22 @@ __global__ __launch_bounds__(256) void w8_plan_kernel(const RP *__restrict__ row
     if (tid == 0) {
         own_rank[b] = ident ? own_s : -1;
         atomicMax(&status[1], win_gran);
+        atomicAdd(reinterpret_cast<unsigned *>(&status[2]), (unsigned)win_gran);
     }
 }
 
-template <typename RP>
+// The stream, one wave per slice.  PHASE 0: today's layout, 2560-byte chunks [64 x 4 slots][64 x 2 values][64 x 2 values].
+// PHASE 1: classify the slices (no stream written): slice_rec[s] = 0 where slice s is IMPLICIT -- its 64 positions hold real rows
+// of one length, and for every entry j, slot(row, j) - 8 (row - block_row0) (bytes) is the same in all 64 lanes -- else its chunks.
+// PHASE 2 (slice_rec = the exclusive scan of PHASE 1): the implied-slot layout, 2048-byte chunks of values only; an implicit slice's
+// chunk keeps its 4 slot bases (16 bits each, the lane's 8 (row - block_row0) is added modulo 2^16 by the kernel; 1 = a padding
+// entry, slot 0 in every lane) in desc[chunk], an explicit slice's chunk keeps its 512 bytes of slots in side[slice_rec[s] + k].
+template <typename RP, int PHASE>
 __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row_ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
                                                       int64_t n_rows, int R, const int32_t *__restrict__ hdr,
                                                       const int64_t *__restrict__ slice_chunk0, const uint16_t *__restrict__ row_of,
-                                                      unsigned char *__restrict__ stream) {
+                                                      unsigned char *__restrict__ stream, int64_t *__restrict__ slice_rec,
+                                                      uint2 *__restrict__ desc, unsigned char *__restrict__ side) {
     __shared__ int g0s[kW8Runs], rk[kW8Runs];
     __shared__ int nr_s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1426,7 +1442,8 @@ __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row
     for (int rr = 0; rr < R; ++rr) {
         const int64_t slice = ((int64_t)b * 4 + wv) * R + rr;
         const int64_t pos = slice * 64 + lane; // position in the block's length order
-        const int64_t r = (int64_t)b * kSwRows * R + row_of[pos];
+        const int in_block = row_of[pos];
+        const int64_t r = (int64_t)b * kSwRows * R + in_block;
         int64_t rs = 0;
         int len = 0;
         if (r < n_rows) {
@@ -1435,7 +1452,10 @@ __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row
         }
         const int64_t c0 = slice_chunk0[slice];
         const int nch = (int)(slice_chunk0[slice + 1] - c0);
-        for (int c = 0; c < nch; ++c) {
+        bool implicit = false; // (wave-uniform)
+        if (PHASE == 1) implicit = __ballot(r < n_rows && len == __builtin_amdgcn_readfirstlane(len)) == ~0ull;
+        if (PHASE == 2) implicit = slice_rec[slice + 1] == slice_rec[slice];
+        for (int c = 0; c < nch && (PHASE != 1 || implicit); ++c) {
             unsigned cc[4];
             double vv[4];
 #pragma unroll
@@ -1452,14 +1472,30 @@ __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row
                         if (g0s[mid] <= g) lo = mid; else hi = mid - 1;
                     }
                     cc[q] = (unsigned)(2 + (rk[lo] + (g - g0s[lo])) * 8 + (ci & 7)) * 8u; // byte offset of the slot behind the window's base
-                    vv[q] = val[rs + j];
+                    if (PHASE != 1) vv[q] = val[rs + j];
                 }
             }
-            unsigned char *p = stream + (size_t)(c0 + c) * kW8ChunkBytes;
-            *reinterpret_cast<uint2 *>(p + lane * 8) = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
-            *reinterpret_cast<double2 *>(p + 512 + lane * 16) = make_double2(vv[0], vv[1]);
-            *reinterpret_cast<double2 *>(p + 1536 + lane * 16) = make_double2(vv[2], vv[3]);
+            unsigned base[4]; // (implicit slices: one length, so an entry is padding in all lanes or in none)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) base[q] = 4 * c + q < len ? (cc[q] - 8u * (unsigned)in_block) & 0xffffu : 1u;
+            if (PHASE == 1) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (__ballot(base[q] != (unsigned)__builtin_amdgcn_readfirstlane((int)base[q])) != 0ull) implicit = false;
+            } else if (PHASE == 0) {
+                unsigned char *p = stream + (size_t)(c0 + c) * kW8ChunkBytes;
+                *reinterpret_cast<uint2 *>(p + lane * 8) = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
+                *reinterpret_cast<double2 *>(p + 512 + lane * 16) = make_double2(vv[0], vv[1]);
+                *reinterpret_cast<double2 *>(p + 1536 + lane * 16) = make_double2(vv[2], vv[3]);
+            } else {
+                unsigned char *p = stream + (size_t)(c0 + c) * kW8ValBytes;
+                *reinterpret_cast<double2 *>(p + lane * 16) = make_double2(vv[0], vv[1]);
+                *reinterpret_cast<double2 *>(p + 1024 + lane * 16) = make_double2(vv[2], vv[3]);
+                if (!implicit) *reinterpret_cast<uint2 *>(side + (size_t)(slice_rec[slice] + c) * 512 + lane * 8) = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
+                else if (lane == 0) desc[c0 + c] = make_uint2(base[0] | base[1] << 16, base[2] | base[3] << 16);
+            }
         }
+        if (PHASE == 1 && lane == 0) slice_rec[slice] = implicit ? 0 : nch;
     }
 }
 
@@ -1475,6 +1511,21 @@ __device__ __forceinline__ W8Chunk w8_load(const unsigned char *__restrict__ str
     ch.v0 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 512 + lane * 16));
     ch.v1 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 1536 + lane * 16));
     return ch;
+}
+
+// the implied-slot layout: a chunk's values (two non-temporal loads per lane, as above); its slots are loaded by the kernel
+__device__ __forceinline__ void w8_load_values(const unsigned char *__restrict__ stream, int64_t c, int lane, W8Chunk &ch) {
+    const unsigned char *p = stream + (size_t)c * kW8ValBytes;
+    ch.v0 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + lane * 16));
+    ch.v1 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 1024 + lane * 16));
+}
+
+// the slots of a chunk of the implied-slot layout: code = 4 x 16-bit bases, off2 = (8 (row - block_row0)) x 0x10001 in an implicit
+// slice, 0 in an explicit one (whose code holds the slots themselves); per half: (base + off) mod 2^16, 0 where the base is 1 (padding)
+typedef unsigned short w8_v2h __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned w8_imply(unsigned code, unsigned off2) {
+    const unsigned pad = (code & 0x10001u) * 0xffffu;
+    return __builtin_bit_cast(unsigned, __builtin_bit_cast(w8_v2h, code) + __builtin_bit_cast(w8_v2h, off2)) & ~pad;
 }
 
 // acc += v_q * window[slot_q], q = 0..3, products and sums rounded separately (the CRS kernels' arithmetic)
@@ -1496,11 +1547,14 @@ __device__ __forceinline__ void w8_consume(const unsigned char *win, const W8Chu
 // offsets are a prefix sum), walked with a ring of D chunks in flight per lane: the chunk D places ahead is requested as soon
 // as a ring entry has been consumed, so the stream never waits for the arithmetic, and the first D chunks are requested before
 // the window is (they do not need it).  LDS: 16 bytes (the -0.0 slot), then the window.
-template <int MODE, int R, int D>
+// IMPL: the implied-slot layout (w8_fill_kernel PHASE 2): a chunk's 8 slot bytes per lane come from desc[chunk] (the same 8 bytes
+// for every lane: implicit slice) or from its record in side (explicit slice), chosen per chunk by its slice (wave-uniform).
+template <int MODE, int R, int D, bool IMPL>
 __global__ __launch_bounds__(256) void spmv_win8_kernel(
     const double *x, double *__restrict__ y, int64_t n_rows, int64_t n_cols, int n_blocks, int remap_arg, const double *w,
     double *__restrict__ partials, const int *stop, const int32_t *__restrict__ hdr, const int64_t *__restrict__ slice_chunk0,
-    const unsigned char *__restrict__ stream, int x_al16, const int32_t *__restrict__ own_rank, const uint16_t *__restrict__ row_of) {
+    const unsigned char *__restrict__ stream, int x_al16, const int32_t *__restrict__ own_rank, const uint16_t *__restrict__ row_of,
+    const w8_v2u *__restrict__ desc, const unsigned char *__restrict__ side, const int64_t *__restrict__ slice_rec) {
     if (stop && stop[1]) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int b = remap_arg > 0 ? xcd_remap(blockIdx.x, remap_arg)
@@ -1523,9 +1577,39 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
     };
     const int64_t C0 = bnd(0), C1 = bnd(R);
     const int64_t c_last = max(C1 - 1, C0); // (the stream ends with one spare chunk: an empty wave reads it)
+    int64_t e[R]; // slice rr of the wave ends at chunk e[rr] (an empty slice: e[rr] == e[rr - 1])
+#pragma unroll
+    for (int rr = 0; rr < R; ++rr) e[rr] = bnd(rr + 1);
+    // IMPL: the slot record of each slice's first chunk (rec[rr + 1] == rec[rr]: slice rr is implicit), and the lane's slot
+    // offset per slice (0 in an explicit slice)
+    int64_t rec[R + 1];
+    unsigned off2[R];
+    if (IMPL) {
+        const int64_t my_rec = slice_rec[slice0 + min(lane, R)];
+#pragma unroll
+        for (int r = 0; r <= R; ++r) {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(unsigned long long)my_rec, r);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)my_rec >> 32), r);
+            rec[r] = (int64_t)(((unsigned long long)hi << 32) | lo);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) off2[r] = rec[r + 1] == rec[r] ? (unsigned)(rows_of[r] - block_row0) * 0x80008u : 0u;
+    }
+    auto load = [&](int64_t cc) {
+        if (!IMPL) return w8_load(stream, cc, lane);
+        W8Chunk ch;
+        w8_load_values(stream, cc, lane, ch);
+        int64_t rs = 0, re = 0, cs = 0; // chunk cc lies in the wave's slice rr (cc = C0 of an empty wave: in none)
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr)
+            if (cc >= (rr ? e[rr - 1] : C0) && cc < e[rr]) { rs = rec[rr]; re = rec[rr + 1]; cs = rr ? e[rr - 1] : C0; }
+        if (re > rs) ch.code = __builtin_nontemporal_load(reinterpret_cast<const w8_v2u *>(side + (size_t)(rs + cc - cs) * 512 + lane * 8));
+        else ch.code = desc[cc];
+        return ch;
+    };
     W8Chunk ring[D];
 #pragma unroll
-    for (int d = 0; d < D; ++d) ring[d] = w8_load(stream, min(C0 + d, c_last), lane);
+    for (int d = 0; d < D; ++d) ring[d] = load(min(C0 + d, c_last));
     // MODE 1: the dot's operand.  own_rank != nullptr: w is x at the rows' own columns (CG: w = x = p) -- where the block's window
     // holds them side by side (own >= 0) the operand comes from LDS behind the barrier instead of a second global read of p
     double wr[R];
@@ -1568,14 +1652,12 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
     }
     double dot_acc = 0.0; // MODE 1: sum over the wave's slices of y[row] w[row] (one partial per WAVE)
     // the walk over [C0, C1): ring[d] holds chunk c whenever (c - C0) % D == d, so the ring index is a compile-time constant in
-    // the unrolled round; slice rr of the wave ends at chunk e[rr] (an empty slice: e[rr] == e[rr - 1]).  All slice indices
-    // are compile-time constants too (a run-time index put wr[] into scratch memory).
-    int64_t e[R];
-#pragma unroll
-    for (int rr = 0; rr < R; ++rr) e[rr] = bnd(rr + 1);
+    // the unrolled round.  All slice indices are compile-time constants too (a run-time index put wr[] into scratch memory):
+    // cur_off, the slot offset of the slice being summed, follows `next` where a slice ends.
     int64_t c = C0;
     int next = 0; // the slice being summed (wave-uniform)
     double acc = 0.0;
+    unsigned cur_off = IMPL ? off2[0] : 0u;
 #define W8_END_SLICES()                                                                    \
     _Pragma("unroll") for (int rr = 0; rr < R; ++rr)                                       \
         if (rr == next && c == e[rr]) {                                                    \
@@ -1584,14 +1666,19 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
             if (MODE == 1) dot_acc += row < n_rows ? acc * wr[rr] : 0.0;                   \
             acc = 0.0;                                                                     \
             ++next;                                                                        \
+            if (IMPL) cur_off = off2[rr + 1 < R ? rr + 1 : R - 1];                         \
         }
     W8_END_SLICES()
     while (c < C1) { // (wave-uniform)
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             if (c < C1) {
-                const W8Chunk cur = ring[d];
-                ring[d] = w8_load(stream, min(c + D, c_last), lane);
+                W8Chunk cur = ring[d];
+                ring[d] = load(min(c + D, c_last));
+                if (IMPL) {
+                    cur.code.x = w8_imply(cur.code.x, cur_off);
+                    cur.code.y = w8_imply(cur.code.y, cur_off);
+                }
                 w8_consume(lds, cur, acc);
                 ++c;
                 W8_END_SLICES()
@@ -1611,6 +1698,7 @@ void bis_spmv_win8_drop(bis_mat *A) {
     if (A->sw8) {
         if (A->sw8->own_codes) A->sw8->codes = reinterpret_cast<uint32_t *>(A->sw8->own_codes); // (a redirected stream is the caller's memory: never freed here)
         hipFree(A->sw8->hdr); hipFree(A->sw8->slice_chunk0); hipFree(A->sw8->own_rank); hipFree(A->sw8->codes); hipFree(A->sw8->row_of);
+        hipFree(A->sw8->slice_rec);
         delete A->sw8;
         A->sw8 = nullptr;
     }
@@ -1621,14 +1709,37 @@ int bis_spmv_win8_blocks(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->
 int bis_spmv_win8_rows(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->R : 0; }
 int64_t bis_spmv_win8_slices(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->n_slices : 0; }
 int64_t bis_spmv_win8_partials(const bis_mat *A) { return A->sw8_state == 1 ? (int64_t)A->sw8->n_blocks * 4 : 0; } // fused dot: one per wave
-// bytes of the form's own arrays one launch reads: the stream (with its padding), block headers, slice offsets
+bool bis_spmv_win8_implied(const bis_mat *A) { return A->sw8_state == 1 && A->sw8->slice_rec != nullptr; }
+// bytes of the form's own arrays one launch reads: the stream (with its padding), block headers, slice offsets.  The implied-slot
+// layout: 2048 bytes of values per chunk, 8 bytes of slot bases per chunk of an implicit slice, 512 bytes of slots per chunk of an
+// explicit slice, and the slices' slot-record offsets
 int64_t bis_spmv_win8_bytes(const bis_mat *A) {
     if (A->sw8_state != 1) return 0;
-    return A->sw8->total_chunks * (int64_t)kW8ChunkBytes + (int64_t)A->sw8->n_blocks * (8 * kW8Runs + 2 * kSwRows * A->sw8->R) + 8 * (A->sw8->n_slices + 1);
+    const bis_sellwin *sw = A->sw8;
+    const int64_t meta = (int64_t)sw->n_blocks * (8 * kW8Runs + 2 * kSwRows * sw->R) + 8 * (sw->n_slices + 1);
+    if (!bis_spmv_win8_implied(A)) return sw->total_chunks * (int64_t)kW8ChunkBytes + meta;
+    return sw->total_chunks * (int64_t)kW8ValBytes + 8 * (sw->total_chunks - sw->expl_chunks) + 512 * sw->expl_chunks + meta + 8 * (sw->n_slices + 1);
 }
 
-// placement tuning (bis_mat_tune_placement): the stream's size, and an exchange of the buffer the kernel reads
-size_t bis_spmv_win8_stream_bytes(const bis_mat *A) { return A->sw8_state == 1 ? (size_t)kW8ChunkBytes * (size_t)(A->sw8->total_chunks + 1) : 0; }
+// placement tuning (bis_mat_tune_placement): the stream's size, and an exchange of the buffer the kernel reads (values and slots,
+// in either layout)
+size_t bis_spmv_win8_stream_bytes(const bis_mat *A) {
+    if (A->sw8_state != 1) return 0;
+    return bis_spmv_win8_implied(A) ? A->sw8->w8_end : (size_t)kW8ChunkBytes * (size_t)(A->sw8->total_chunks + 1);
+}
+
+// the placement searches' test for the fast level of the stream's placement, priced on the bytes a launch moves (the same
+// measure for both layouts): the form's own arrays, the x granules copied into the blocks' windows, y.  HPCG-256 moves 5.43 GB
+// in today's layout (plain product: fast level 0.755-0.79 ms = 6.9-7.2 TB/s, slow 0.855-0.89 ms = 6.1-6.35) and 4.59 GB with implied
+// slots (fused product, as the search times it there: 0.664-0.688 ms = 6.7-6.9 TB/s on good allocations, 0.81 ms on bad ones);
+// 6.6 TB/s lies between the levels of either.
+double bis_spmv_win8_moved_bytes(const bis_mat *A) {
+    if (A->sw8_state != 1) return 0.0;
+    return (double)bis_spmv_win8_bytes(A) + 64.0 * (double)A->sw8->win_gran_sum + 8.0 * (double)A->n_rows;
+}
+bool bis_spmv_win8_fast(const bis_mat *A, double ms) {
+    return A->sw8_state == 1 && ms > 0.0 && bis_spmv_win8_moved_bytes(A) / (ms * 1e-3) >= 6.6e12;
+}
 void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream) {
     void *old = A->sw8->codes;
     A->sw8->codes = reinterpret_cast<uint32_t *>(stream);
@@ -1654,34 +1765,43 @@ void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream) {
 // Placement tuning of the stream at build time.  WHERE in HBM the stream lies decides between two levels of the kernel's time,
 // 13 % apart (HPCG-256: 0.755 / 0.855 ms; constant over time for an allocation, independent of where x and y lie, and the slow
 // level is the common one early in a process: tools/win8_place2.py, tools/win8_timeline.py, profiles/r05_f_win8_placement.log).
-// So a stream of 1 GiB or more is tried in up to k fresh allocations (option spmv_win8_tune, default 12 -- five slow allocations
+// So a stream of 1 GiB or more (counted in today's layout, 2560 bytes per chunk, also where slots are implied) is tried in up to k fresh allocations (option spmv_win8_tune, default 12 -- five slow allocations
 // in a row have been seen --; the earlier ones are
 // held so that the next one lands elsewhere; bounded by the free memory minus 8 GiB), each a device-to-device copy timed with
 // the kernel itself on a zero vector, and the search ends at the first allocation of the fast level.
 static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
     bis_sellwin *sw = A->sw8;
     const size_t bytes = bis_spmv_win8_stream_bytes(A);
-    const int k = bis_opts().spmv_win8_tune >= 0 ? bis_opts().spmv_win8_tune : (bytes >= ((size_t)1 << 30) ? 12 : 0);
+    // (the size test is on today's layout, 2560 bytes per chunk, in both layouts: the same matrices are searched)
+    const int k = bis_opts().spmv_win8_tune >= 0 ? bis_opts().spmv_win8_tune : ((size_t)kW8ChunkBytes * (size_t)(sw->total_chunks + 1) >= ((size_t)1 << 30) ? 12 : 0);
     if (k <= 0) return BIS_OK;
-    double *x = nullptr, *y = nullptr;
+    double *x = nullptr, *y = nullptr, *part = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     std::vector<void *> losers;
     auto cleanup = [&]() {
         hipStreamSynchronize(ctx->stream);
         for (void *l : losers) hipFree(l);
-        hipFree(x); hipFree(y);
+        hipFree(x); hipFree(y); hipFree(part);
         if (e0) hipEventDestroy(e0);
         if (e1) hipEventDestroy(e1);
         (void)hipGetLastError();
     };
-    if (hipMalloc(&x, sizeof(double) * (size_t)(A->n_cols + 2)) != hipSuccess || hipMalloc(&y, sizeof(double) * (size_t)A->n_rows) != hipSuccess ||
-        hipMemsetAsync(x, 0, sizeof(double) * (size_t)(A->n_cols + 2), ctx->stream) != hipSuccess ||
+    const size_t nx = (size_t)std::max(A->n_cols, A->view_row0 + A->n_rows) + 2; // (x is also the fused dot's w at the rows' own columns)
+    if (hipMalloc(&x, sizeof(double) * nx) != hipSuccess || hipMalloc(&y, sizeof(double) * (size_t)A->n_rows) != hipSuccess ||
+        hipMalloc(&part, sizeof(double) * 4 * (size_t)sw->n_blocks) != hipSuccess ||
+        hipMemsetAsync(x, 0, sizeof(double) * nx, ctx->stream) != hipSuccess ||
         hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { cleanup(); return BIS_OK; } // no room to tune: keep the first allocation
     const int nb = sw->n_blocks, remap_arg = bis_spmv_remap_arg(nb), grid = bis_spmv_grid(nb);
+    // the kernel timed: with implied slots the one CG runs (the fused (Ap, p) dot, w = x) -- the plain product's time did not tell
+    // its placement level (HPCG-256: 0.635 ms plain on an allocation where the CG loop's fused launches took 0.81 ms)
+    const bool implied = bis_spmv_win8_implied(A);
+    const int mode = implied ? 1 : 0;
+    const double *w = implied ? x + A->view_row0 : nullptr;
+    double *partials = implied ? part : nullptr;
     auto measure = [&](double &ms) -> bool {
-        for (int i = 0; i < 2; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, 0, nullptr, nullptr, nullptr, remap_arg, grid) != BIS_OK) return false;
+        for (int i = 0; i < 2; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, mode, w, partials, nullptr, remap_arg, grid) != BIS_OK) return false;
         hipEventRecord(e0, ctx->stream);
-        for (int i = 0; i < 5; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, 0, nullptr, nullptr, nullptr, remap_arg, grid) != BIS_OK) return false;
+        for (int i = 0; i < 5; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, mode, w, partials, nullptr, remap_arg, grid) != BIS_OK) return false;
         hipEventRecord(e1, ctx->stream);
         if (hipEventSynchronize(e1) != hipSuccess) return false;
         float f = 0.f;
@@ -1692,10 +1812,11 @@ static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
     double best = 0.0;
     if (!measure(best)) { cleanup(); ctx->err = "win8 placement tuning: launch failed"; return BIS_ERR_HIP; }
     sw->tune_first_ms = best;
-    // the search ends at an allocation of the fast level: one the kernel reads at >= 5.9 TB/s (fast: 6.0-6.5, slow: 5.5 on uniform
-    // rows), or one at least 8 % faster than the slowest seen (ragged rows never reach 5.9)
+    // the search ends at an allocation of the fast level (bis_spmv_win8_fast), or, in today's layout, one at least 8 % faster than
+    // the slowest seen (ragged rows never reach the fast level's rate).  With implied slots the placements spread over more than
+    // two levels (HPCG-256: 0.65-0.78 ms) and the 8 % rule stopped at middle ones (0.70-0.72 ms): there only the rate counts
     double slowest = best;
-    auto fast_enough = [&](double ms) { return (double)bytes / (ms * 1e-3) >= 5.9e12 || ms <= 0.92 * slowest; };
+    auto fast_enough = [&](double ms) { return bis_spmv_win8_fast(A, ms) || (!implied && ms <= 0.92 * slowest); };
     int trials = 0;
     for (; trials < k && !fast_enough(best); ++trials) {
         size_t free_b = 0, total_b = 0;
@@ -1712,7 +1833,7 @@ static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
     }
     sw->tune_trials = trials;
     sw->tune_kept_ms = best;
-    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 placement: %d re-allocation(s) of %zu bytes tried, kernel %.4f ms on the first allocation, %.4f ms on the one kept\n", trials, bytes, sw->tune_first_ms, best);
+    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 placement: %d re-allocation(s) of %zu bytes tried, kernel %.4f ms on the first allocation, %.4f ms on the one kept (%.0f bytes moved: %.2f TB/s)\n", trials, bytes, sw->tune_first_ms, best, bis_spmv_win8_moved_bytes(A), bis_spmv_win8_moved_bytes(A) / (best * 1e9));
     cleanup();
     return BIS_OK;
 }
@@ -1727,6 +1848,15 @@ extern "C" BIS_API bis_status bis_mat_win8_debug_stream(bis_mat *A, void **ptr, 
     if (set) { if (!sw->own_codes) sw->own_codes = (void *)sw->codes; sw->codes = reinterpret_cast<uint32_t *>(set); }
     else if (sw->own_codes) { sw->codes = reinterpret_cast<uint32_t *>(sw->own_codes); sw->own_codes = nullptr; }
     return BIS_OK;
+}
+
+extern "C" BIS_API void bis_mat_win8_layout(const bis_mat *A, int64_t *chunks, int64_t *explicit_chunks, int64_t *slices, int *blocks, int *implied) {
+    const bool ok = A && A->sw8_state == 1;
+    if (chunks) *chunks = ok ? A->sw8->total_chunks : 0;
+    if (explicit_chunks) *explicit_chunks = ok ? A->sw8->expl_chunks : 0;
+    if (slices) *slices = ok ? A->sw8->n_slices : 0;
+    if (blocks) *blocks = ok ? A->sw8->n_blocks : 0;
+    if (implied) *implied = ok && bis_spmv_win8_implied(A);
 }
 
 extern "C" BIS_API void bis_mat_win8_tuning(const bis_mat *A, int *trials, double *first_ms, double *kept_ms) {
@@ -1777,14 +1907,14 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
     W8_CHECK(hipMalloc(&sw->row_of, sizeof(uint16_t) * (size_t)nb * kSwRows * (size_t)R));
     W8_CHECK(hipMalloc(&slice_chunks, sizeof(int32_t) * (size_t)(sw->n_slices + 1)));
     W8_CHECK(hipMalloc(&sw->slice_chunk0, sizeof(int64_t) * (size_t)(sw->n_slices + 1)));
-    W8_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int), ctx->stream));
+    W8_CHECK(hipMemsetAsync(status, 0, 3 * sizeof(int), ctx->stream));
     W8_CHECK(hipMemsetAsync(status + 5, 0, sizeof(int), ctx->stream));
     W8_CHECK(hipMemsetAsync(slice_chunks, 0, sizeof(int32_t) * (size_t)(sw->n_slices + 1), ctx->stream));
     W8_CHECK(hipMemsetAsync(sw->hdr, 0, sizeof(int32_t) * 2 * kW8Runs * (size_t)nb, ctx->stream));
     if (A->rp64) hipLaunchKernelGGL(w8_plan_kernel<int64_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->n_rows, R, kSwMaxGran, A->view_row0, sw->hdr, slice_chunks, sw->own_rank, sw->row_of, status);
     else hipLaunchKernelGGL(w8_plan_kernel<int32_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, A->n_rows, R, kSwMaxGran, A->view_row0, sw->hdr, slice_chunks, sw->own_rank, sw->row_of, status);
     W8_CHECK(hipGetLastError());
-    int h[2] = {0, 0};
+    int h[3] = {0, 0, 0};
     W8_CHECK(hipMemcpyAsync(h, status, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     const int64_t ns1 = sw->n_slices + 1;
     hipLaunchKernelGGL(sw_widen_kernel, dim3((unsigned)((ns1 + 255) / 256)), dim3(256), 0, ctx->stream, slice_chunks, sw->slice_chunk0, ns1);
@@ -1800,6 +1930,7 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
     hipFree(slice_chunks); slice_chunks = nullptr;
     sw->total_chunks = total;
     sw->max_gran = h[1];
+    sw->win_gran_sum = (int64_t)(unsigned)h[2];
     // not representable (more than 64 runs / 60 KiB of window in some block), or more than 12 % of padding (every padded entry costs
     // 10 streamed bytes: Anderson's 7-entry rows in 8 slots, 14 %, run 0.310 ms against 0.297 for the row-block kernel): that kernel stays
     if (h[0] || (double)total * 256.0 > 1.12 * (double)A->nnz + 256.0 * 4 * 64) {
@@ -1809,16 +1940,53 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
         A->sw8_state = -1;
         return BIS_OK;
     }
+#define W8_FILL(PHASE, STREAM, DESC, SIDE)                                                                                                        \
+    do {                                                                                                                                          \
+        if (A->rp64) hipLaunchKernelGGL((w8_fill_kernel<int64_t, PHASE>), dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, \
+                                        A->val, A->n_rows, R, sw->hdr, sw->slice_chunk0, sw->row_of, STREAM, sw->slice_rec, DESC, SIDE);           \
+        else hipLaunchKernelGGL((w8_fill_kernel<int32_t, PHASE>), dim3(nb), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col,     \
+                                A->val, A->n_rows, R, sw->hdr, sw->slice_chunk0, sw->row_of, STREAM, sw->slice_rec, DESC, SIDE);                   \
+        W8_CHECK(hipGetLastError());                                                                                                              \
+    } while (0)
+    // implied slots (option spmv_win8_implicit, default on): classify the slices, count the chunks that keep their slots; the
+    // layout is built where at least half of the chunks are implicit (stencils: HPCG-256 93.6 %), today's layout elsewhere
+    sw->expl_chunks = total;
+    if (bis_opts().spmv_win8_implicit != 0 && total > 0) {
+        W8_CHECK(hipMalloc(&sw->slice_rec, sizeof(int64_t) * (size_t)ns1));
+        W8_CHECK(hipMemsetAsync(sw->slice_rec, 0, sizeof(int64_t) * (size_t)ns1, ctx->stream));
+        W8_FILL(1, nullptr, nullptr, nullptr);
+        tmp_bytes = 0;
+        W8_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, sw->slice_rec, sw->slice_rec, (int64_t)0, (size_t)ns1, rocprim::plus<int64_t>(), ctx->stream));
+        W8_CHECK(hipMalloc(&tmp, tmp_bytes));
+        W8_CHECK(rocprim::exclusive_scan(tmp, tmp_bytes, sw->slice_rec, sw->slice_rec, (int64_t)0, (size_t)ns1, rocprim::plus<int64_t>(), ctx->stream));
+        int64_t expl = 0;
+        W8_CHECK(hipMemcpyAsync(&expl, sw->slice_rec + sw->n_slices, sizeof expl, hipMemcpyDeviceToHost, ctx->stream));
+        W8_CHECK(hipStreamSynchronize(ctx->stream));
+        hipFree(tmp); tmp = nullptr;
+        if (2 * (total - expl) >= total) sw->expl_chunks = expl;
+        else { hipFree(sw->slice_rec); sw->slice_rec = nullptr; }
+    }
     unsigned char *stream = nullptr;
-    W8_CHECK(hipMalloc(&stream, (size_t)kW8ChunkBytes * (size_t)(total + 1)));
+    const size_t chunk_bytes = sw->slice_rec ? kW8ValBytes : kW8ChunkBytes;
+    size_t stream_bytes = chunk_bytes * (size_t)(total + 1);
+    if (sw->slice_rec) {
+        sw->w8_desc = stream_bytes;
+        sw->w8_side = sw->w8_desc + ((8 * (size_t)(total + 1) + 255) & ~(size_t)255);
+        sw->w8_end = stream_bytes = sw->w8_side + 512 * (size_t)sw->expl_chunks;
+    }
+    W8_CHECK(hipMalloc(&stream, stream_bytes));
     sw->codes = reinterpret_cast<uint32_t *>(stream);
-    W8_CHECK(hipMemsetAsync(stream + (size_t)total * kW8ChunkBytes, 0, kW8ChunkBytes, ctx->stream));
-    if (A->rp64) hipLaunchKernelGGL(w8_fill_kernel<int64_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->val, A->n_rows, R, sw->hdr, sw->slice_chunk0, sw->row_of, stream);
-    else hipLaunchKernelGGL(w8_fill_kernel<int32_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, A->val, A->n_rows, R, sw->hdr, sw->slice_chunk0, sw->row_of, stream);
-    W8_CHECK(hipGetLastError());
+    W8_CHECK(hipMemsetAsync(stream + (size_t)total * chunk_bytes, 0, chunk_bytes, ctx->stream));
+    if (sw->slice_rec) {
+        W8_CHECK(hipMemsetAsync(stream + sw->w8_desc, 0, sw->w8_side - sw->w8_desc, ctx->stream));
+        W8_FILL(2, stream, reinterpret_cast<uint2 *>(stream + sw->w8_desc), stream + sw->w8_side);
+    } else {
+        W8_FILL(0, stream, nullptr, nullptr);
+    }
+#undef W8_FILL
     A->sw8_state = 1;
     if (bis_status tst = w8_tune_placement(ctx, A)) return tst;
-    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 plan (R = %d): %d blocks, window <= %d granules (%zu bytes), %.1f %% padding: used; stream at %p (%zu bytes), hdr %p\n", R, nb, sw->max_gran, (size_t)(2 + 8 * sw->max_gran) * 8, 100.0 * ((double)total * 256.0 / (double)A->nnz - 1.0), (void *)sw->codes, (size_t)kW8ChunkBytes * (size_t)(total + 1), (void *)sw->hdr);
+    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 plan (R = %d): %d blocks, window <= %d granules (%zu bytes), %.1f %% padding: used; implied slots: %s, %.1f %% of %lld chunks implicit; stream at %p (%zu bytes), hdr %p\n", R, nb, sw->max_gran, (size_t)(2 + 8 * sw->max_gran) * 8, 100.0 * ((double)total * 256.0 / (double)A->nnz - 1.0), sw->slice_rec ? "built" : "not built", 100.0 * (double)(total - sw->expl_chunks) / (double)std::max<int64_t>(total, 1), (long long)total, (void *)sw->codes, bis_spmv_win8_stream_bytes(A), (void *)sw->hdr);
     return BIS_OK;
 }
 #undef W8_CHECK
@@ -1835,14 +2003,17 @@ bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
     // (HPCG-256 0.861; 2: 0.945, 4: 1.030).  The waves of the other workgroups on the CU cover the rest of the latency.
     const bool ragged = (double)sw->total_chunks * 256.0 > 1.08 * (double)A->nnz;
     const int depth = bis_opts().spmv_win8_depth > 0 ? bis_opts().spmv_win8_depth : (sw->R == 4 ? (ragged ? 2 : 1) : 3);
-#define W8_L3(MODE, RR, DD) hipLaunchKernelGGL((spmv_win8_kernel<MODE, RR, DD>), dim3(grid), dim3(256), lds, ctx->stream, x, y, A->n_rows, A->n_cols, \
-                                               sw->n_blocks, remap_arg, w, partials, stop, sw->hdr, sw->slice_chunk0, stream, x_al16, own, sw->row_of)
+#define W8_L3(MODE, RR, DD) do { if (sw->slice_rec) W8_L4(MODE, RR, DD, true); else W8_L4(MODE, RR, DD, false); } while (0)
+#define W8_L4(MODE, RR, DD, IMPL) hipLaunchKernelGGL((spmv_win8_kernel<MODE, RR, DD, IMPL>), dim3(grid), dim3(256), lds, ctx->stream, x, y, A->n_rows, A->n_cols, \
+                                               sw->n_blocks, remap_arg, w, partials, stop, sw->hdr, sw->slice_chunk0, stream, x_al16, own, sw->row_of, \
+                                               reinterpret_cast<const w8_v2u *>(stream + sw->w8_desc), stream + sw->w8_side, sw->slice_rec)
 #define W8_L2(MODE, RR) do { if (depth <= 1) W8_L3(MODE, RR, 1); else if (depth == 2) W8_L3(MODE, RR, 2); else if (depth == 3) W8_L3(MODE, RR, 3); else if (depth <= 5) W8_L3(MODE, RR, 4); else W8_L3(MODE, RR, 6); } while (0)
 #define W8_L1(MODE) do { if (sw->R == 4) W8_L2(MODE, 4); else if (sw->R == 2) W8_L2(MODE, 2); else W8_L2(MODE, 1); } while (0)
     if (mode == 1) W8_L1(1); else W8_L1(0);
 #undef W8_L1
 #undef W8_L2
 #undef W8_L3
+#undef W8_L4
     BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
 }

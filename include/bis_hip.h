@@ -192,6 +192,10 @@ BIS_API bis_status bis_mat_retune(bis_ctx *ctx, bis_mat *A);
  * tried, the kernel's time on the first allocation and on the one kept (ms; zeros when the matrix
  * has no such stream or no tuning ran).  For bench / CLI records. */
 BIS_API void bis_mat_win8_tuning(const bis_mat *A, int *trials, double *first_ms, double *kept_ms);
+/* The layout of that stream (zeros without one): its chunks (4 entries of 64 rows), the chunks that keep their
+ * 2-byte window slots (all of them unless *implied), slices (64 rows), blocks; *implied = 1 where the slots of the
+ * other chunks are implied by their rows (option "spmv_win8_implicit"): 2048 bytes per chunk instead of 2560. */
+BIS_API void bis_mat_win8_layout(const bis_mat *A, int64_t *chunks, int64_t *explicit_chunks, int64_t *slices, int *blocks, int *implied);
 /* Column slabs (the SpMV's form for a matrix WITHOUT locality: rows along which the slab index never falls --
  * ascending columns, the usual case --, a column stream that does not
  * pack, an x that does not fit an XCD's L2 -- config 5's unstructured input as generated): K CRS copies of
