@@ -126,6 +126,8 @@ constexpr int kMaxDotBlocks = 8192;
 constexpr int kWinMaxTiles = 128; // x window: at most 128 tiles of 16 columns (16 KiB of LDS)
 constexpr int kWinTile = 16;
 constexpr int kWinTileLog = 4;
+constexpr int kSwRows = 256; // window + sliced-ELL forms (bis_spmv_sell.hip): a block is kSwRows R rows, R rows per lane, R = 1, 2 or 4
+constexpr int kSwMaxR = 4;
 
 struct bis_mat {
     int64_t n_rows = 0, n_cols = 0, nnz = 0;
@@ -304,10 +306,13 @@ bis_status bis_reduce_finish(bis_ctx *ctx, int n_partials, int n_values,
 // only when it has to grow)
 bis_status bis_ensure_partials(bis_ctx *ctx, size_t n);
 // y = A x; if w != nullptr also partials[partials_off + b] = sum_{r in block b}
-// y[r]*w[r] (n_partials = number written).  The caller sizes ctx->partials.
+// y[r]*w[r] (n_partials = number written).  The caller sizes ctx->partials
+// (bis_spmv_partials_bound).
 bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
                            double *y, const double *w, int *n_partials,
                            size_t partials_off = 0);
+// upper bound on the partials one fused bis_spmv_launch of A writes, whichever form A gets (nothing is built)
+size_t bis_spmv_partials_bound(const bis_mat *A);
 bis_status bis_spmv_trsv_level(bis_ctx *ctx, const bis_mat *T, const double *x, double *y,
                                const double *b, const double *D);
 // rows [ra,rb) of A as a matrix sharing A's arrays (y must be offset by ra)
@@ -335,8 +340,6 @@ void bis_spmv_sellwin_drop(bis_mat *A);
 bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A);
 int bis_spmv_win8_blocks(const bis_mat *A);
 int bis_spmv_win8_rows(const bis_mat *A);
-int64_t bis_spmv_win8_slices(const bis_mat *A);
-int64_t bis_spmv_win8_partials(const bis_mat *A);
 int64_t bis_spmv_win8_bytes(const bis_mat *A);
 bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x, double *y, int mode, const double *w,
                                 double *partials, const int *stop, int remap_arg, int grid);

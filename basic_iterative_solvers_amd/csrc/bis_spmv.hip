@@ -35,7 +35,30 @@
 //     on the row-block tables (spmv_rowblock_vd_kernel).  See "Value-dictionary
 //     variant" below and DESIGN.md section 4.
 //
-// Rows longer than the LDS budget fall back to a wave-per-row kernel.
+// The forms of y = A x, in the order of precedence in which spmv_resolve chooses (the only place that does); "dictionary":
+// the matrix has a value dictionary (spmv_valdict >= 1) -- "lane per row" needs spmv_valdict 2 (the default) --; "default
+// variant": spmv_variant -1 or 20.  Modes: plain, fused dot, sweep level.  Public form number: bis_mat_spmv_stream_info.
+//
+//   form (name reported)             chosen when                                            streams per non-zero      fused-dot partials
+//   long rows (spmv_wave_per_row_    a block's products and the longest row exceed 64 KiB   12 B                      -- (plain only: fused dot
+//     kernel), public 0              of LDS                                                                           and sweep level refuse)
+//   x-window (spmv_window_kernel),   spmv_window 1 and every block touches <= 128 tiles;    10 B (2-byte position     4 per block (plain table)
+//     public 0                       plain, fused                                           in the window)
+//   sellwin ("sellwin fmt=F"),       dictionary, lane per row, default variant,             fmt 0, 1: 3 B; 2: 2 B;    1 per 64-row slice
+//     public 4 / 5                   spmv_sellwin != 0, the plan applies; plain, fused      3: 1 B; 4: 4 B per ROW
+//   rowmajor (spmv_rowmajor_vd_      dictionary, lane per row, default variant, rows <= 40  3 B                       4 per 256 rows
+//     kernel), public 2 / 3          entries, <= 8 (32) column windows per 256 rows; all
+//   win8 ("win8 rows=R"), public 6   no dictionary, spmv_win8 != 0, default variant, the    10 B (8 B + a descriptor  4 per block of 256 R rows
+//                                    plan applies (<= 12 % padding); plain, fused           per chunk: implied slots)
+//   colslab ("colslab K=k"),         no dictionary, < 2^29 columns, spmv_colslab != 0,      12 B (10 B where every    4 per block of the last
+//     public 7                       variant -1 / 20 / 41, colslab_try's conditions and     slab packs) + 16 B per    slab (fused table)
+//                                    trial; plain, fused                                    row and later pass
+//   rowblock_vd (spmv_rowblock_vd_   dictionary with consecutive codes, variant 20 on the   3 B                       4 per block (fused table)
+//     kernel), public 1              8-window packed stream; all
+//   rowblock (spmv_rowblock_kernel   everything else; all                                   10 B packed, 12 B         4 per block (fused table)
+//     U= PK= BR=), public 0
+//   (+ 8 B per row where the dictionary keeps the diagonal's values per row: public 3 and 5)
+//
 // An optional fused epilogue accumulates sum_r y[r]*w[r] (the (Ap,p) of
 // cg.hpp:23) into per-wave partials so CG needs no separate dot pass; a third
 // epilogue turns the kernel into one triangular-sweep step on a row range.
@@ -902,9 +925,12 @@ void launch_vd(const SpmvArgs &a) {
                        a.pk_base, a.seg_base, a.col_max, a.stop, a.vcode, a.vd_base, a.vdict);
 }
 
+// value dictionary, consecutive form: the default variant on the packed stream only, and not as a later column slab's pass
+bool rowblock_is_vd(int id, const SpmvArgs &a) { return a.vcode && !a.acc_y && !a.vd_rm_only && id == 20 && a.pk_mode == 1; }
+
 template <typename RP>
 bool launch_by_id(int id, const SpmvArgs &a) {
-    if (a.vcode && !a.acc_y && !a.vd_rm_only && id == 20 && a.pk_mode == 1) { // value dictionary, consecutive form: the default variant only
+    if (rowblock_is_vd(id, a)) {
         if (a.mode == 2) launch_vd<RP, 2>(a);
         else if (a.mode == 1) launch_vd<RP, 1>(a);
         else launch_vd<RP, 0>(a);
@@ -953,7 +979,7 @@ int spmv_variant(const SpmvArgs &a) {
 
 // Names bis_mat_spmv_kernel reports: static strings, built once, so that a launch only stores a pointer.
 // The row-block kernel's instance as launch_by_id picks it: U staged vectors, PK the column stream (WIDE: 32-bit columns,
-// 64-bit x addressing), BR the phase-1 form; or the value-dictionary kernel.
+// 64-bit x addressing), BR the phase-1 form; or the value-dictionary kernel.  nullptr for an id launch_by_id does not know.
 const char *rowblock_name(int id, const SpmvArgs &a) {
     static const std::vector<std::string> names = [] {
         std::vector<std::string> v;
@@ -964,8 +990,10 @@ const char *rowblock_name(int id, const SpmvArgs &a) {
                                 " BR=" + std::to_string(br));
         return v;
     }();
-    if (a.vcode && !a.acc_y && !a.vd_rm_only && id == 20 && a.pk_mode == 1) return "spmv_rowblock_vd_kernel";
+    if (rowblock_is_vd(id, a)) return "spmv_rowblock_vd_kernel";
     const int u = id / 10 == 1 ? 0 : (id / 10 == 2 ? 1 : 2), br = id % 10;
+    static const int known[] = {10, 20, 40, 11, 21, 41, 12, 22}; // (launch_by_id's)
+    if (std::find(std::begin(known), std::end(known), id) == std::end(known)) return nullptr;
     const int pk = a.wide ? 4 : a.pk_mode;
     return names[(size_t)(u * 5 + pk) * 3 + br].c_str();
 }
@@ -1275,94 +1303,19 @@ static bis_status ensure_packed(bis_ctx *ctx, const bis_mat *A_c, int t, SpmvArg
 int bis_spmv_remap_arg(int nb) { return remap_arg_for((nb + 7) & ~7); }
 int bis_spmv_grid(int nb) { return grid_for_map(nb, remap_arg_for((nb + 7) & ~7)); }
 
-// x-window + sliced-ELL form of the dictionary kernel (bis_spmv_sell.hip) where the matrix qualifies; modes 0 and 1
-static bool sellwin_wanted(const SpmvArgs &a) {
-    return a.vcode && spmv_valdict_mode() >= 2 && bis_opts().spmv_sellwin != 0 && (bis_opts().spmv_variant < 0 || bis_opts().spmv_variant == 20);
-}
-static bis_status launch_sellwin(bis_ctx *ctx, const bis_mat *A, const SpmvArgs &a, const double *x, double *y, int mode,
-                                 const double *w, double *partials, size_t partials_off, int *n_partials, bool *done) {
-    *done = false;
-    if (mode == 2 || !sellwin_wanted(a)) return BIS_OK;
-    if (bis_status st = bis_spmv_sellwin_try(ctx, const_cast<bis_mat *>(A))) return st;
-    const int nbr = bis_spmv_sellwin_blocks(A);
-    if (!nbr) return BIS_OK;
-    const int64_t n_slices = bis_spmv_sellwin_slices(A); // one partial of the fused dot per 64-row slice
-    if (mode == 1 && partials_off + (size_t)n_slices > ctx->partials_cap) {
-        ctx->err = "bis_spmv: partials buffer too small (internal)";
-        return BIS_ERR_INVALID;
-    }
-    const int remap_arg = remap_arg_for((nbr + 7) & ~7);
-    bis_prof_begin(ctx);
-    bis_status st = bis_spmv_sellwin_launch(ctx, A, x, y, mode, w, mode == 1 ? partials + partials_off : partials, a.stop,
-                                            remap_arg, grid_for_map(nbr, remap_arg));
-    bis_prof_end(ctx);
-    if (st != BIS_OK) return st;
-    if (mode == 1 && n_partials) *n_partials = (int)n_slices;
-    *done = true;
-    return BIS_OK;
-}
+// ---- the form of a matrix' SpMV: resolved in ONE place (the table in the file header); launches and reports read the plan ----
 
-// window + sliced-ELL form with the 8-byte values streamed (bis_spmv_sell.hip, "win8"): for matrices the dictionary forms do not
-// serve (arbitrary values, or spmv_valdict = 0), where the plan applies; modes 0 and 1
-static bool win8_wanted() { return bis_opts().spmv_win8 != 0 && (bis_opts().spmv_variant < 0 || bis_opts().spmv_variant == 20); }
-static bis_status launch_win8(bis_ctx *ctx, const bis_mat *A, const SpmvArgs &a, const double *x, double *y, int mode,
-                              const double *w, double *partials, size_t partials_off, int *n_partials, bool *done) {
-    *done = false;
-    if (mode == 2 || !win8_wanted() || a.vcode) return BIS_OK; // (a matrix with a value dictionary keeps its dictionary kernels: 3 bytes per non-zero)
-    if (bis_status st = bis_spmv_win8_try(ctx, const_cast<bis_mat *>(A))) return st;
-    const int nbr = bis_spmv_win8_blocks(A);
-    if (!nbr) return BIS_OK;
-    const int64_t n_slices = bis_spmv_win8_partials(A); // (one partial of the fused dot per wave)
-    if (mode == 1 && partials_off + (size_t)n_slices > ctx->partials_cap) {
-        ctx->err = "bis_spmv: partials buffer too small (internal)";
-        return BIS_ERR_INVALID;
-    }
-    const int remap_arg = remap_arg_for((nbr + 7) & ~7);
-    bis_prof_begin(ctx);
-    bis_status st = bis_spmv_win8_launch(ctx, A, x, y, mode, w, mode == 1 ? partials + partials_off : partials, a.stop,
-                                         remap_arg, grid_for_map(nbr, remap_arg));
-    bis_prof_end(ctx);
-    if (st != BIS_OK) return st;
-    if (mode == 1 && n_partials) *n_partials = (int)n_slices;
-    *done = true;
-    return BIS_OK;
-}
+enum SpmvForm { kFormLongRows, kFormWindow, kFormSellwin, kFormRowmajor, kFormWin8, kFormColslab, kFormRowblockVd, kFormRowblock };
 
-// lane-per-row form of the dictionary kernel where the matrix qualifies (*done tells); mode 0 / 1 / 2 as in SpmvArgs
-static bis_status launch_rowmajor(bis_ctx *ctx, const bis_mat *A, const SpmvArgs &a, const double *x, double *y, int mode,
-                                  const double *w, double *partials, size_t partials_off, int *n_partials, bool *done) {
-    *done = false;
-    if (!(a.vcode && spmv_valdict_mode() >= 2 && (bis_opts().spmv_variant < 0 || bis_opts().spmv_variant == 20))) return BIS_OK;
-    if (bis_status st = spmv_try_rowmajor(ctx, const_cast<bis_mat *>(A))) return st;
-    if (A->rm_state != 1) return BIS_OK;
-    const int nbr = A->rm_blocks, nbr8 = (nbr + 7) & ~7;
-    if (mode == 1 && partials_off + (size_t)nbr * 4 > ctx->partials_cap) {
-        ctx->err = "bis_spmv: partials buffer too small (internal)";
-        return BIS_ERR_INVALID;
-    }
-    const int remap_arg = remap_arg_for(nbr8);
-    const int grid = grid_for_map(nbr, remap_arg);
-    const int code_cap = kRmRows * std::max(A->max_row_nnz, 1) + 16; // positions: a block's codes + the 8-alignment slack on both sides
-    const size_t lds = 3 * (size_t)code_cap;
-    double *pp = mode == 1 ? partials + partials_off : partials;
-    if (mode != 2) bis_prof_begin(ctx);
-#define BIS_RM_LAUNCH3(RP, MODE, DIAG, W32)                                                                            \
-    hipLaunchKernelGGL((spmv_rowmajor_vd_kernel<RP, MODE, DIAG, W32>), dim3(grid), dim3(256), lds, ctx->stream, (const RP *)A->row_ptr, x, y, \
-                       A->n_rows, nbr, remap_arg, w, pp, A->rm_pk, A->rm_base, A->rm_seg, a.stop, A->vcode, A->vd_base, A->vdict, code_cap, \
-                       A->vdiag)
-#define BIS_RM_LAUNCH2(RP, MODE, DIAG) do { if (A->rm_kind == 3) BIS_RM_LAUNCH3(RP, MODE, DIAG, true); else BIS_RM_LAUNCH3(RP, MODE, DIAG, false); } while (0)
-#define BIS_RM_LAUNCH(RP, MODE) do { if (A->vd_diag) BIS_RM_LAUNCH2(RP, MODE, true); else BIS_RM_LAUNCH2(RP, MODE, false); } while (0)
-    if (A->rp64) { if (mode == 2) BIS_RM_LAUNCH(int64_t, 2); else if (mode == 1) BIS_RM_LAUNCH(int64_t, 1); else BIS_RM_LAUNCH(int64_t, 0); }
-    else { if (mode == 2) BIS_RM_LAUNCH(int32_t, 2); else if (mode == 1) BIS_RM_LAUNCH(int32_t, 1); else BIS_RM_LAUNCH(int32_t, 0); }
-#undef BIS_RM_LAUNCH
-#undef BIS_RM_LAUNCH2
-#undef BIS_RM_LAUNCH3
-    if (mode != 2) bis_prof_end(ctx);
-    BIS_HIP_CHECK(ctx, hipGetLastError());
-    if (mode == 1 && n_partials) *n_partials = nbr * 4;
-    *done = true;
-    return BIS_OK;
-}
+struct SpmvPlan {
+    SpmvForm form = kFormRowblock;
+    SpmvArgs a{};          // tables, block map (nb, remap_arg, grid), column stream, dictionary; the caller adds x, y, w, partials, stop
+    int n_partials = 0;    // partials the fused dot writes (mode 1)
+    const char *name = ""; // what bis_mat_spmv_kernel reports: a static string
+};
+
+static bis_status spmv_resolve(bis_ctx *ctx, const bis_mat *A_c, int mode, SpmvPlan *p, bool pass = false);
+static bis_status spmv_launch_plan(bis_ctx *ctx, const bis_mat *A, const SpmvPlan &p);
 
 // ---- column slabs (bis_spmv_slab.hip): K passes of the row-block kernel, each gathering from an x slice that fits the L2 ----
 
@@ -1380,36 +1333,21 @@ void bis_spmv_colslab_drop(bis_mat *A) {
     A->cs_trial_ms[0] = A->cs_trial_ms[1] = 0.0;
 }
 
-// one pass of the row-block kernel over matrix B (A itself, or one of its slabs)
-static bis_status rowblock_pass(bis_ctx *ctx, const bis_mat *B, const double *x, double *y, const double *w, size_t partials_off,
-                                int acc_y, const int *stop, int *n_partials) {
-    const bool use_f = w != nullptr;
-    const int64_t lds_doubles = (int64_t)(use_f ? B->chunk_f : B->chunk_nnz) + B->max_row_nnz + 8;
-    const int nb = use_f ? B->n_blocks_f : B->n_blocks, nb8 = (nb + 7) & ~7;
-    if (w && partials_off + (size_t)nb * 4 > ctx->partials_cap) { ctx->err = "bis_spmv: partials buffer too small (internal)"; return BIS_ERR_INVALID; }
-    SpmvArgs a{B->row_ptr, B->col, B->val, x, y, use_f ? B->blkf_row : B->blk_row, use_f ? B->blkf_nnz : B->blk_nnz, nb, nb8, w,
-               ctx->partials + partials_off, sizeof(double) * (size_t)lds_doubles, ctx->stream, w ? 1 : 0};
-    a.n_cus = ctx->n_cus;
-    a.remap = bis_opts().spmv_xcd_remap == 1;
-    a.remap_arg = remap_arg_for(nb8);
-    a.grid = grid_for_map(nb, a.remap_arg);
-    if (bis_status st = ensure_packed(ctx, B, use_f ? 1 : 0, &a)) return st;
-    a.vcode = nullptr; // (the plain row-block kernel: the value-dictionary kernel has no accumulating form)
-    a.stop = stop;
-    a.acc_y = acc_y;
-    const bool ok = launch_by_id<int32_t>(spmv_variant(a), a);
-    if (!ok) { ctx->err = "bis_spmv: unknown BIS_SPMV_VARIANT"; return BIS_ERR_INVALID; }
-    if (w && n_partials) *n_partials = nb * (fused_threads(spmv_variant(a)) / 64);
-    return BIS_OK;
+// one pass of the row-block kernel over matrix B (A itself, or one of its slabs); a fused dot's partials go to `partials`
+static bis_status rowblock_pass(bis_ctx *ctx, const bis_mat *B, const double *x, double *y, const double *w, double *partials,
+                                int acc_y, const int *stop) {
+    SpmvPlan p;
+    if (bis_status st = spmv_resolve(ctx, B, w ? 1 : 0, &p, true)) return st;
+    p.a.x = x; p.a.y = y; p.a.w = w; p.a.partials = partials; p.a.stop = stop;
+    p.a.acc_y = acc_y;
+    return spmv_launch_plan(ctx, B, p);
 }
 
-static bis_status colslab_passes(bis_ctx *ctx, const bis_mat *A, const double *x, double *y, const double *w, size_t partials_off,
-                                 const int *stop, int *n_partials) {
+static bis_status colslab_passes(bis_ctx *ctx, const bis_mat *A, const double *x, double *y, const double *w, double *partials,
+                                 const int *stop) {
     const std::vector<bis_mat *> &S = *A->colslabs;
-    for (size_t k = 0; k < S.size(); ++k) {
-        const bool last = k + 1 == S.size();
-        if (bis_status st = rowblock_pass(ctx, S[k], x, y, last ? w : nullptr, partials_off, k > 0 ? 1 : 0, stop, last ? n_partials : nullptr)) return st;
-    }
+    for (size_t k = 0; k < S.size(); ++k) // (the fused dot rides on the last pass: y is complete there)
+        if (bis_status st = rowblock_pass(ctx, S[k], x, y, k + 1 == S.size() ? w : nullptr, partials, k > 0 ? 1 : 0, stop)) return st;
     return BIS_OK;
 }
 
@@ -1443,7 +1381,7 @@ static bis_status colslab_try(bis_ctx *ctx, bis_mat *A, bool packed) {
         for (int which = 0; which < 2 && good && st == BIS_OK; ++which) {
             for (int rep = 0; rep < 5 && st == BIS_OK; ++rep) {
                 if (rep == 2) good = good && hipEventRecord(ev[0], ctx->stream) == hipSuccess;
-                st = which ? colslab_passes(ctx, A, xs, ys, nullptr, 0, nullptr, nullptr) : rowblock_pass(ctx, A, xs, ys, nullptr, 0, 0, nullptr, nullptr);
+                st = which ? colslab_passes(ctx, A, xs, ys, nullptr, nullptr, nullptr) : rowblock_pass(ctx, A, xs, ys, nullptr, nullptr, 0, nullptr);
             }
             good = good && hipEventRecord(ev[1], ctx->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
                    hipEventElapsedTime(&ms[which], ev[0], ev[1]) == hipSuccess;
@@ -1466,22 +1404,168 @@ static bis_status colslab_try(bis_ctx *ctx, bis_mat *A, bool packed) {
     return BIS_OK;
 }
 
-static bool colslab_wanted(const SpmvArgs &a) {
-    return bis_opts().spmv_colslab != 0 && !a.vcode && !a.wide && (bis_opts().spmv_variant < 0 || bis_opts().spmv_variant == 20 || bis_opts().spmv_variant == 41);
-}
-static bis_status launch_colslab(bis_ctx *ctx, const bis_mat *A, const SpmvArgs &a, const double *x, double *y, const double *w,
-                                 size_t partials_off, int *n_partials, bool *done) {
-    *done = false;
-    if (!colslab_wanted(a)) return BIS_OK;
-    if (bis_status st = colslab_try(ctx, const_cast<bis_mat *>(A), a.pk_mode != 0)) return st;
-    if (A->cs_state != 1) return BIS_OK;
-    bis_prof_begin(ctx);
-    bis_status st = colslab_passes(ctx, A, x, y, w, partials_off, a.stop, n_partials);
-    bis_prof_end(ctx);
-    if (st != BIS_OK) return st;
-    BIS_HIP_CHECK(ctx, hipGetLastError());
-    *done = true;
+// The one place that reads the form-selecting options together with the matrix' build states and runs the lazy builds.
+// mode 0: y = A x; 1: with the fused dot (its own block table); 2: one triangular-sweep level (lane-per-row dictionary form or
+// row-block kernel only).  pass: one plain row-block pass over a slab (or over A: the slabs' trial).  Precedence as in the table
+// of the file header; the builds run in that order too, so the first SpMV's device allocations land where they always did.
+static bis_status spmv_resolve(bis_ctx *ctx, const bis_mat *A_c, int mode, SpmvPlan *p, bool pass) {
+    bis_mat *A = const_cast<bis_mat *>(A_c); // (the forms are a cache on the matrix: the entry points' const handle is cast away here only)
+    *p = SpmvPlan{};
+    SpmvArgs &a = p->a;
+    const bool window = !pass && mode != 2 && A->win_ok && spmv_window_mode();
+    const bool use_f = mode == 1 && !window; // fused epilogue: its own table
+    a.lds_bytes = sizeof(double) * (size_t)((int64_t)(use_f ? A->chunk_f : A->chunk_nnz) + A->max_row_nnz + 8);
+    if (!pass && a.lds_bytes > 64 * 1024) {
+        if (mode == 1) { ctx->err = "bis_spmv: fused dot unsupported for very long rows"; return BIS_ERR_UNSUPPORTED; }
+        if (mode == 2) { ctx->err = "sptrsv level: row too long for the streaming kernel"; return BIS_ERR_UNSUPPORTED; }
+        p->form = kFormLongRows;
+        p->name = "spmv_wave_per_row_kernel";
+        return BIS_OK;
+    }
+    auto block_map = [&a](int nb) {
+        a.nb = nb;
+        a.nb8 = (nb + 7) & ~7;
+        a.remap_arg = remap_arg_for(a.nb8);
+        a.grid = grid_for_map(nb, a.remap_arg);
+    };
+    a.row_ptr = A->row_ptr; a.col = A->col; a.val = A->val;
+    a.blk_row = use_f ? A->blkf_row : A->blk_row;
+    a.blk_nnz = use_f ? A->blkf_nnz : A->blk_nnz;
+    a.stream = ctx->stream;
+    a.mode = mode;
+    a.n_cus = ctx->n_cus;
+    a.remap = bis_opts().spmv_xcd_remap == 1;
+    block_map(use_f ? A->n_blocks_f : A->n_blocks);
+    if (window) {
+        p->form = kFormWindow;
+        p->n_partials = mode == 1 ? a.nb * 4 : 0; // 256-thread workgroups: 4 waves
+        p->name = "spmv_window_kernel";
+        return BIS_OK;
+    }
+    if (bis_status st = ensure_packed(ctx, A, use_f ? 1 : 0, &a)) return st;
+    if (pass) {
+        a.vcode = nullptr; // (the plain row-block kernel: the value-dictionary kernel has no accumulating form)
+    } else {
+        const int v = bis_opts().spmv_variant;
+        const bool lane_per_row = a.vcode && spmv_valdict_mode() >= 2 && (v < 0 || v == 20);
+        if (mode != 2 && lane_per_row && bis_opts().spmv_sellwin != 0) {
+            if (bis_status st = bis_spmv_sellwin_try(ctx, A)) return st;
+            if (const int nb = bis_spmv_sellwin_blocks(A)) {
+                block_map(nb);
+                p->form = kFormSellwin;
+                p->n_partials = mode == 1 ? (int)bis_spmv_sellwin_slices(A) : 0; // one per 64-row slice
+                p->name = form_name(0, bis_spmv_sellwin_format(A));
+                return BIS_OK;
+            }
+        }
+        if (lane_per_row) {
+            if (bis_status st = spmv_try_rowmajor(ctx, A)) return st;
+            if (A->rm_state == 1) {
+                block_map(A->rm_blocks);
+                p->form = kFormRowmajor;
+                p->n_partials = mode == 1 ? A->rm_blocks * 4 : 0;
+                p->name = "spmv_rowmajor_vd_kernel";
+                return BIS_OK;
+            }
+        }
+        // (a matrix with a value dictionary keeps its dictionary kernels: 3 bytes per non-zero)
+        if (mode != 2 && !a.vcode && bis_opts().spmv_win8 != 0 && (v < 0 || v == 20)) {
+            if (bis_status st = bis_spmv_win8_try(ctx, A)) return st;
+            if (const int nb = bis_spmv_win8_blocks(A)) {
+                block_map(nb);
+                p->form = kFormWin8;
+                p->n_partials = mode == 1 ? nb * 4 : 0; // one per wave
+                p->name = form_name(1, bis_spmv_win8_rows(A));
+                return BIS_OK;
+            }
+        }
+        if (mode != 2 && !a.vcode && !a.wide && bis_opts().spmv_colslab != 0 && (v < 0 || v == 20 || v == 41)) {
+            if (bis_status st = colslab_try(ctx, A, a.pk_mode != 0)) return st;
+            if (A->cs_state == 1) {
+                p->form = kFormColslab;
+                p->n_partials = mode == 1 ? A->colslabs->back()->n_blocks_f * (fused_threads(0) / 64) : 0; // the last pass writes them
+                p->name = form_name(2, (int)A->colslabs->size());
+                return BIS_OK;
+            }
+        }
+        if (mode != 2 && bis_opts().spmv_lds_pad > 0) a.lds_bytes += (size_t)bis_opts().spmv_lds_pad;
+    }
+    const int id = spmv_variant(a);
+    p->name = rowblock_name(id, a);
+    if (!p->name) { ctx->err = "bis_spmv: unknown BIS_SPMV_VARIANT"; return BIS_ERR_INVALID; }
+    p->form = rowblock_is_vd(id, a) ? kFormRowblockVd : kFormRowblock;
+    p->n_partials = mode == 1 ? a.nb * (fused_threads(id) / 64) : 0;
     return BIS_OK;
+}
+
+// launches what the plan names; x, y, w, partials (a sweep level: b and D in their place) and stop are in p.a
+static bis_status spmv_launch_plan(bis_ctx *ctx, const bis_mat *A, const SpmvPlan &p) {
+    const SpmvArgs &a = p.a;
+    switch (p.form) {
+    case kFormLongRows: {
+        const int grid = (int)std::min<int64_t>((A->n_rows + 3) / 4, 8192);
+        if (A->rp64)
+            hipLaunchKernelGGL(spmv_wave_per_row_kernel<int64_t>, dim3(grid), dim3(256), 0, ctx->stream,
+                               (const int64_t *)A->row_ptr, A->col, A->val, a.x, a.y, A->n_rows);
+        else
+            hipLaunchKernelGGL(spmv_wave_per_row_kernel<int32_t>, dim3(grid), dim3(256), 0, ctx->stream,
+                               (const int32_t *)A->row_ptr, A->col, A->val, a.x, a.y, A->n_rows);
+        return BIS_OK;
+    }
+    case kFormWindow: {
+        const int xw_doubles = ((A->max_tiles * kWinTile) + 1) & ~1;
+        const size_t lds_win = a.lds_bytes + sizeof(double) * (size_t)xw_doubles;
+#define BIS_WIN_LAUNCH(RP, FUSE)                                                                   \
+    hipLaunchKernelGGL((spmv_window_kernel<RP, 256, 2, FUSE>), dim3(a.nb8), dim3(256), lds_win,    \
+                       ctx->stream, (const RP *)A->row_ptr, A->loc, A->loc_base, A->val, a.x, a.y, \
+                       A->blk_row, A->blk_nnz, A->tiles, A->tile_cnt, A->n_cols, xw_doubles, a.nb, \
+                       bis_opts().spmv_xcd_remap > 0 ? a.nb8 : -1, a.w, a.partials)
+        if (A->rp64) { if (a.w) BIS_WIN_LAUNCH(int64_t, true); else BIS_WIN_LAUNCH(int64_t, false); }
+        else { if (a.w) BIS_WIN_LAUNCH(int32_t, true); else BIS_WIN_LAUNCH(int32_t, false); }
+#undef BIS_WIN_LAUNCH
+        return BIS_OK;
+    }
+    case kFormSellwin:
+        return bis_spmv_sellwin_launch(ctx, A, a.x, a.y, a.mode, a.w, a.partials, a.stop, a.remap_arg, a.grid);
+    case kFormWin8:
+        return bis_spmv_win8_launch(ctx, A, a.x, a.y, a.mode, a.w, a.partials, a.stop, a.remap_arg, a.grid);
+    case kFormRowmajor: {
+        const int code_cap = kRmRows * std::max(A->max_row_nnz, 1) + 16; // positions: a block's codes + the 8-alignment slack on both sides
+        const size_t lds = 3 * (size_t)code_cap;
+#define BIS_RM_LAUNCH3(RP, MODE, DIAG, W32)                                                                            \
+    hipLaunchKernelGGL((spmv_rowmajor_vd_kernel<RP, MODE, DIAG, W32>), dim3(a.grid), dim3(256), lds, ctx->stream, (const RP *)A->row_ptr, a.x, a.y, \
+                       A->n_rows, a.nb, a.remap_arg, a.w, a.partials, A->rm_pk, A->rm_base, A->rm_seg, a.stop, A->vcode, A->vd_base, A->vdict, code_cap, \
+                       A->vdiag)
+#define BIS_RM_LAUNCH2(RP, MODE, DIAG) do { if (A->rm_kind == 3) BIS_RM_LAUNCH3(RP, MODE, DIAG, true); else BIS_RM_LAUNCH3(RP, MODE, DIAG, false); } while (0)
+#define BIS_RM_LAUNCH(RP, MODE) do { if (A->vd_diag) BIS_RM_LAUNCH2(RP, MODE, true); else BIS_RM_LAUNCH2(RP, MODE, false); } while (0)
+        if (A->rp64) { if (a.mode == 2) BIS_RM_LAUNCH(int64_t, 2); else if (a.mode == 1) BIS_RM_LAUNCH(int64_t, 1); else BIS_RM_LAUNCH(int64_t, 0); }
+        else { if (a.mode == 2) BIS_RM_LAUNCH(int32_t, 2); else if (a.mode == 1) BIS_RM_LAUNCH(int32_t, 1); else BIS_RM_LAUNCH(int32_t, 0); }
+#undef BIS_RM_LAUNCH
+#undef BIS_RM_LAUNCH2
+#undef BIS_RM_LAUNCH3
+        return BIS_OK;
+    }
+    case kFormColslab:
+        return colslab_passes(ctx, A, a.x, a.y, a.w, a.partials, a.stop);
+    case kFormRowblockVd:
+    case kFormRowblock:
+        if (A->rp64) launch_by_id<int64_t>(spmv_variant(a), a);
+        else launch_by_id<int32_t>(spmv_variant(a), a);
+        return BIS_OK;
+    }
+    return BIS_ERR_INVALID;
+}
+
+// Upper bound on the partials one fused SpMV of A writes, over every form spmv_resolve can choose -- from the matrix' shape
+// and block tables alone, so that it holds before any form is built.  Row-block kernel: one per wave of a block of the fused
+// table (4; the 16 dates from workgroups of up to 1024 threads and is kept); x-window kernel: 4 per block of the plain table.
+// The forms on blocks of kSwRows R rows, R = 1, 2, 4 (lane-per-row dictionary: R = 1, 4 per block; win8: 4 per block; sellwin:
+// one per slice of kSwRows / 4 rows) write at most ceil(n / (kSwRows R)) 4 R <= n / (kSwRows / 4) + 4 kSwMaxR.  The slabs'
+// last pass runs on a table of no more blocks than A's own.
+size_t bis_spmv_partials_bound(const bis_mat *A) {
+    static_assert(kRmRows == kSwRows, "the lane-per-row form's blocks are the R = 1 case");
+    const size_t rows = (size_t)std::max<int64_t>(A->n_rows, 0);
+    return std::max({(size_t)A->n_blocks_f * 16, (size_t)A->n_blocks * 4, rows / (kSwRows / 4) + 4 * (size_t)kSwMaxR});
 }
 
 // internal: y = A x, optionally partials[b] = sum_{r in block b} y[r]*w[r]
@@ -1490,87 +1574,21 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
                            const double *w, int *n_partials, size_t partials_off) {
     if (n_partials) *n_partials = 0;
     if (A->n_rows == 0) return BIS_OK;
-    const char *&ran = const_cast<bis_mat *>(A)->spmv_kernel[w ? 1 : 0]; // (bis_mat_spmv_kernel)
-    const bool use_f = w != nullptr && !(A->win_ok && spmv_window_mode()); // fused epilogue: its own table
-    const int64_t lds_doubles = (int64_t)(use_f ? A->chunk_f : A->chunk_nnz) + A->max_row_nnz + 8;
-    const size_t lds_bytes = sizeof(double) * (size_t)lds_doubles;
-    if (lds_bytes > 64 * 1024) {
-        if (w) { ctx->err = "bis_spmv: fused dot unsupported for very long rows"; return BIS_ERR_UNSUPPORTED; }
-        const int grid = (int)std::min<int64_t>((A->n_rows + 3) / 4, 8192);
-        bis_prof_begin(ctx);
-        if (A->rp64)
-            hipLaunchKernelGGL(spmv_wave_per_row_kernel<int64_t>, dim3(grid), dim3(256), 0, ctx->stream,
-                               (const int64_t *)A->row_ptr, A->col, A->val, x, y, A->n_rows);
-        else
-            hipLaunchKernelGGL(spmv_wave_per_row_kernel<int32_t>, dim3(grid), dim3(256), 0, ctx->stream,
-                               (const int32_t *)A->row_ptr, A->col, A->val, x, y, A->n_rows);
-        bis_prof_end(ctx);
-        BIS_HIP_CHECK(ctx, hipGetLastError());
-        ran = "spmv_wave_per_row_kernel";
-        return BIS_OK;
-    }
-    const int nb = use_f ? A->n_blocks_f : A->n_blocks, nb8 = (nb + 7) & ~7;
-    if (w && partials_off + (size_t)nb * 4 > ctx->partials_cap) {
+    SpmvPlan p;
+    if (bis_status st = spmv_resolve(ctx, A, w ? 1 : 0, &p)) return st;
+    if (w && partials_off + (size_t)p.n_partials > ctx->partials_cap) {
         ctx->err = "bis_spmv: partials buffer too small (internal)";
         return BIS_ERR_INVALID;
     }
-    if (A->win_ok && spmv_window_mode()) {
-        const int xw_doubles = ((A->max_tiles * kWinTile) + 1) & ~1;
-        const size_t lds_win = lds_bytes + sizeof(double) * (size_t)xw_doubles;
-        bis_prof_begin(ctx);
-#define BIS_WIN_LAUNCH(RP, FUSE)                                                                   \
-    hipLaunchKernelGGL((spmv_window_kernel<RP, 256, 2, FUSE>), dim3(nb8), dim3(256), lds_win,      \
-                       ctx->stream, (const RP *)A->row_ptr, A->loc, A->loc_base, A->val, x, y,     \
-                       A->blk_row, A->blk_nnz, A->tiles, A->tile_cnt, A->n_cols, xw_doubles, nb,   \
-                       bis_opts().spmv_xcd_remap > 0 ? nb8 : -1, w, ctx->partials + partials_off)
-        if (A->rp64) { if (w) BIS_WIN_LAUNCH(int64_t, true); else BIS_WIN_LAUNCH(int64_t, false); }
-        else { if (w) BIS_WIN_LAUNCH(int32_t, true); else BIS_WIN_LAUNCH(int32_t, false); }
-#undef BIS_WIN_LAUNCH
-        bis_prof_end(ctx);
-        BIS_HIP_CHECK(ctx, hipGetLastError());
-        if (w && n_partials) *n_partials = nb * 4; // 256-thread workgroups: 4 waves
-        ran = "spmv_window_kernel";
-        return BIS_OK;
-    }
-    SpmvArgs a{A->row_ptr, A->col, A->val, x, y, use_f ? A->blkf_row : A->blk_row,
-               use_f ? A->blkf_nnz : A->blk_nnz, nb, nb8, w,
-               ctx->partials + partials_off, lds_bytes,
-               ctx->stream, w ? 1 : 0};
-    a.n_cus = ctx->n_cus;
-    a.remap = bis_opts().spmv_xcd_remap == 1;
-    a.remap_arg = remap_arg_for(nb8);
-    a.grid = grid_for_map(nb, a.remap_arg);
-    if (bis_status st = ensure_packed(ctx, A, use_f ? 1 : 0, &a)) return st;
-    a.stop = ctx->spmv_stop; // a device schedule (bis_cg_iterate, bis_stat_iterate) is enqueuing: no-op once its stop flag is set
-    {
-        bool done = false;
-        if (bis_status st = launch_sellwin(ctx, A, a, x, y, w ? 1 : 0, w, ctx->partials, partials_off, n_partials, &done)) return st;
-        if (done) { ran = form_name(0, bis_spmv_sellwin_format(A)); return BIS_OK; }
-    }
-    {
-        bool done = false;
-        if (bis_status st = launch_rowmajor(ctx, A, a, x, y, w ? 1 : 0, w, ctx->partials, partials_off, n_partials, &done)) return st;
-        if (done) { ran = "spmv_rowmajor_vd_kernel"; return BIS_OK; }
-    }
-    {
-        bool done = false;
-        if (bis_status st = launch_win8(ctx, A, a, x, y, w ? 1 : 0, w, ctx->partials, partials_off, n_partials, &done)) return st;
-        if (done) { ran = form_name(1, bis_spmv_win8_rows(A)); return BIS_OK; }
-    }
-    {
-        bool done = false;
-        if (bis_status st = launch_colslab(ctx, A, a, x, y, w, partials_off, n_partials, &done)) return st;
-        if (done) { ran = form_name(2, (int)A->colslabs->size()); return BIS_OK; }
-    }
-    if (bis_opts().spmv_lds_pad > 0) a.lds_bytes += (size_t)bis_opts().spmv_lds_pad;
+    p.a.x = x; p.a.y = y; p.a.w = w; p.a.partials = ctx->partials + partials_off;
+    p.a.stop = ctx->spmv_stop; // a device schedule (bis_cg_iterate, bis_stat_iterate) is enqueuing: no-op once its stop flag is set
     bis_prof_begin(ctx);
-    const bool ok = A->rp64 ? launch_by_id<int64_t>(spmv_variant(a), a)
-                            : launch_by_id<int32_t>(spmv_variant(a), a);
+    const bis_status st = spmv_launch_plan(ctx, A, p);
     bis_prof_end(ctx);
-    if (!ok) { ctx->err = "bis_spmv: unknown BIS_SPMV_VARIANT"; return BIS_ERR_INVALID; }
+    if (st != BIS_OK) return st;
     BIS_HIP_CHECK(ctx, hipGetLastError());
-    if (w && n_partials) *n_partials = nb * (fused_threads(spmv_variant(a)) / 64);
-    ran = rowblock_name(spmv_variant(a), a);
+    if (n_partials) *n_partials = p.n_partials;
+    const_cast<bis_mat *>(A)->spmv_kernel[w ? 1 : 0] = p.name; // (bis_mat_spmv_kernel)
     return BIS_OK;
 }
 
@@ -1579,25 +1597,11 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x, doub
 bis_status bis_spmv_trsv_level(bis_ctx *ctx, const bis_mat *T, const double *x, double *y,
                                const double *b, const double *D) {
     if (T->n_rows == 0) return BIS_OK;
-    const int64_t lds_doubles = (int64_t)T->chunk_nnz + T->max_row_nnz + 8;
-    const size_t lds_bytes = sizeof(double) * (size_t)lds_doubles;
-    if (lds_bytes > 64 * 1024) { ctx->err = "sptrsv level: row too long for the streaming kernel"; return BIS_ERR_UNSUPPORTED; }
-    const int nb = T->n_blocks, nb8 = (nb + 7) & ~7;
-    SpmvArgs a{T->row_ptr, T->col, T->val, x, y, T->blk_row, T->blk_nnz, nb, nb8, b,
-               const_cast<double *>(D), lds_bytes, ctx->stream, 2};
-    a.n_cus = ctx->n_cus;
-    a.remap = bis_opts().spmv_xcd_remap == 1;
-    a.remap_arg = remap_arg_for(nb8);
-    a.grid = grid_for_map(nb, a.remap_arg);
-    if (bis_status st = ensure_packed(ctx, T, 0, &a)) return st;
-    a.stop = ctx->spmv_stop;
-    {
-        bool done = false;
-        if (bis_status st = launch_rowmajor(ctx, T, a, x, y, 2, b, const_cast<double *>(D), 0, nullptr, &done)) return st;
-        if (done) return BIS_OK;
-    }
-    const bool ok = T->rp64 ? launch_by_id<int64_t>(spmv_variant(a), a) : launch_by_id<int32_t>(spmv_variant(a), a);
-    if (!ok) return BIS_ERR_INVALID;
+    SpmvPlan p;
+    if (bis_status st = spmv_resolve(ctx, T, 2, &p)) return st;
+    p.a.x = x; p.a.y = y; p.a.w = b; p.a.partials = const_cast<double *>(D);
+    p.a.stop = ctx->spmv_stop;
+    if (bis_status st = spmv_launch_plan(ctx, T, p)) return st;
     BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
 }
@@ -1613,78 +1617,84 @@ bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x, double *y) 
     return bis_spmv_launch(ctx, A, x, y, nullptr, nullptr);
 }
 
+} // extern "C"
+
+// What the plain SpMV of A streams: the plan's form (and sellwin format) -> col_bytes, val_bytes, n_dict and the public form
+// number (include/bis_hip.h).  sellwin's formats: 0, 1 a 2-byte window slot and a 1-byte value code per non-zero; 2 one 16-bit
+// code (slot : 13 | value index : 3); 3 one byte, the index of the non-zero's (column - row, value) pair; 4 a 32-bit mask of
+// pairs per ROW.  win8 keeps col_bytes 2 also with implied slots (bis_mat_win8_layout tells the layouts apart).
+struct SpmvReport { int col_bytes, val_bytes, n_dict, form; };
+
+static bis_status spmv_report(bis_ctx *ctx, const bis_mat *A, SpmvPlan *p, SpmvReport *r) {
+    if (bis_status st = spmv_resolve(ctx, A, 0, p)) return st;
+    switch (p->form) {
+    case kFormLongRows: *r = {4, 8, 0, 0}; break;
+    case kFormWindow: *r = {2, 8, 0, 0}; break; // (16-bit positions in the block's x window)
+    case kFormRowblock: *r = {p->a.pk_mode ? 2 : 4, 8, 0, 0}; break;
+    case kFormRowblockVd: *r = {2, 1, A->vd_n, 1}; break;
+    case kFormRowmajor: *r = {2, 1, A->vd_n, A->vd_diag ? 3 : 2}; break;
+    case kFormSellwin: {
+        static const int col_val[5][2] = {{2, 1}, {2, 1}, {2, 0}, {1, 0}, {0, 0}}; // val_bytes 0: the value index shares the column code
+        const int fmt = bis_spmv_sellwin_format(A);
+        *r = {col_val[fmt][0], col_val[fmt][1], A->vd_n, A->vd_diag ? 5 : 4};
+        break;
+    }
+    case kFormWin8: *r = {2, 8, 0, 6}; break;
+    case kFormColslab: {
+        bool all_packed = true;
+        for (const bis_mat *B : *A->colslabs) {
+            SpmvPlan pb;
+            if (bis_status st = spmv_resolve(ctx, B, 0, &pb, true)) return st;
+            all_packed = all_packed && (pb.a.pk_mode != 0 || B->nnz == 0);
+        }
+        *r = {all_packed ? 2 : 4, 8, (int)A->colslabs->size(), 7}; // (n_dict: the number of slabs)
+        break;
+    }
+    }
+    return BIS_OK;
+}
+
+extern "C" {
+
 bis_status bis_mat_spmv_stream_info(bis_ctx *ctx, const bis_mat *A, int *col_bytes, int *val_bytes, int *n_dict, int *form) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, A, "bis_mat_spmv_stream_info: bad arguments");
-    SpmvArgs a{};
-    const int64_t lds_doubles = (int64_t)A->chunk_nnz + A->max_row_nnz + 8;
-    if (A->n_rows > 0 && sizeof(double) * (size_t)lds_doubles <= 64 * 1024 && !(A->win_ok && spmv_window_mode()))
-        if (bis_status st = ensure_packed(ctx, A, 0, &a)) return st;
-    int f = 0;
-    if (sellwin_wanted(a)) {
-        if (bis_status st = bis_spmv_sellwin_try(ctx, const_cast<bis_mat *>(A))) return st;
-        if (bis_spmv_sellwin_blocks(A)) f = A->vd_diag ? 5 : 4;
-    }
-    if (!f && a.vcode && spmv_valdict_mode() >= 2 && (bis_opts().spmv_variant < 0 || bis_opts().spmv_variant == 20)) {
-        if (bis_status st = spmv_try_rowmajor(ctx, const_cast<bis_mat *>(A))) return st;
-        if (A->rm_state == 1) f = A->vd_diag ? 3 : 2;
-    }
-    if (!f && a.vcode && !a.vd_rm_only && spmv_variant(a) == 20 && a.pk_mode == 1) f = 1;
-    if (!f && !a.vcode && win8_wanted() && A->n_rows > 0) { // form 6: window + sliced ELL, 8-byte values + 2-byte window slots
-        if (bis_status st = bis_spmv_win8_try(ctx, const_cast<bis_mat *>(A))) return st;
-        if (bis_spmv_win8_blocks(A)) f = 6;
-    }
-    if (!f && colslab_wanted(a) && A->n_rows > 0 && sizeof(double) * (size_t)lds_doubles <= 64 * 1024) { // form 7: K column slabs, each a pass of the row-block kernel
-        if (bis_status st = colslab_try(ctx, const_cast<bis_mat *>(A), a.pk_mode != 0)) return st;
-        if (A->cs_state == 1) {
-            bool all_packed = true;
-            for (const bis_mat *B : *A->colslabs) {
-                SpmvArgs b{};
-                if (bis_status st = ensure_packed(ctx, B, 0, &b)) return st;
-                all_packed = all_packed && (b.pk_mode != 0 || B->nnz == 0);
-            }
-            if (col_bytes) *col_bytes = all_packed ? 2 : 4;
-            if (val_bytes) *val_bytes = 8;
-            if (n_dict) *n_dict = (int)A->colslabs->size(); // (the number of slabs)
-            if (form) *form = 7;
-            return BIS_OK;
-        }
-    }
-    if (f == 6) {
-        if (col_bytes) *col_bytes = 2; // (also with implied slots: col_bytes 0 names the row-mask form; bis_mat_win8_layout tells them apart)
-        if (val_bytes) *val_bytes = 8;
-        if (n_dict) *n_dict = 0;
-        if (form) *form = 6;
-        return BIS_OK;
-    }
-    if (col_bytes) *col_bytes = (f >= 4 && bis_spmv_sellwin_format(A) == 4) ? 0 : (f >= 4 && bis_spmv_sellwin_format(A) == 3) ? 1 : ((f >= 2 || a.pk_mode) ? 2 : 4); // 1: one byte per non-zero, the index of its (column - row, value) pair; 0: a 32-bit mask of pairs per ROW
-    if (val_bytes) *val_bytes = f ? (f >= 4 && bis_spmv_sellwin_format(A) >= 2 ? 0 : 1) : 8; // 0: the value index shares the column code
-    if (n_dict) *n_dict = f ? A->vd_n : 0;
-    if (form) *form = f;
+    SpmvPlan p;
+    SpmvReport r{};
+    if (bis_status st = spmv_report(ctx, A, &p, &r)) return st;
+    if (col_bytes) *col_bytes = r.col_bytes;
+    if (val_bytes) *val_bytes = r.val_bytes;
+    if (n_dict) *n_dict = r.n_dict;
+    if (form) *form = r.form;
     return BIS_OK;
 }
 
 bis_status bis_mat_spmv_streamed_bytes(bis_ctx *ctx, const bis_mat *A, int64_t *bytes) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, A && bytes, "bis_mat_spmv_streamed_bytes: bad arguments");
-    int col_b = 4, val_b = 8, n_dict = 0, form = 0;
-    if (bis_status st = bis_mat_spmv_stream_info(ctx, A, &col_b, &val_b, &n_dict, &form)) return st;
+    SpmvPlan p;
+    SpmvReport r{};
+    if (bis_status st = spmv_report(ctx, A, &p, &r)) return st;
     const int64_t rp = A->rp64 ? 8 : 4;
+    // what the row-block kernel streams of a matrix B: columns and values, row pointers, block table (and window bases)
+    auto rowblock_bytes = [&](const bis_mat *B) {
+        return (int64_t)(r.col_bytes + r.val_bytes) * B->nnz + rp * (B->n_rows + 1) + (int64_t)B->n_blocks * (12 + (r.col_bytes == 2 ? 32 : 0));
+    };
     int64_t b = 8 * A->n_cols + 8 * A->n_rows; // x once, y once
-    if (form == 7) { // the slabs' CRS copies, and y read and written again by every pass after the first
-        for (const bis_mat *B : *A->colslabs)
-            b += (int64_t)(col_b + val_b) * B->nnz + rp * (B->n_rows + 1) + (int64_t)B->n_blocks * (12 + (col_b == 2 ? 32 : 0));
+    switch (p.form) {
+    case kFormLongRows: b += 12 * A->nnz + rp * (A->n_rows + 1); break;
+    case kFormWindow: b += 10 * A->nnz + rp * (A->n_rows + 1) + (int64_t)A->n_blocks * 16; break; // (and 4 bytes per tile a block touches)
+    case kFormRowblock: b += rowblock_bytes(A); break;
+    case kFormRowblockVd: b += rowblock_bytes(A) + 2048; break;
+    case kFormRowmajor: b += 3 * A->nnz + rp * (A->n_rows + 1) + (int64_t)A->rm_blocks * (A->rm_kind == 3 ? 128 : 32) + 2048; break;
+    case kFormSellwin: b += bis_spmv_sellwin_bytes(A); break;
+    case kFormWin8: b += bis_spmv_win8_bytes(A); break;
+    case kFormColslab: // the slabs' CRS copies, and y read and written again by every pass after the first
+        for (const bis_mat *B : *A->colslabs) b += rowblock_bytes(B);
         b += 16 * A->n_rows * ((int64_t)A->colslabs->size() - 1);
-    } else if (form == 6) {
-        b += bis_spmv_win8_bytes(A);
-    } else if (form >= 4) {
-        b += bis_spmv_sellwin_bytes(A);
-    } else if (form >= 2) {
-        b += 3 * A->nnz + rp * (A->n_rows + 1) + (int64_t)A->rm_blocks * (A->rm_kind == 3 ? 128 : 32) + 2048;
-    } else {
-        b += (int64_t)(col_b + val_b) * A->nnz + rp * (A->n_rows + 1) + (int64_t)A->n_blocks * (12 + (col_b == 2 ? 32 : 0)) + (form == 1 ? 2048 : 0);
+        break;
     }
-    if (form == 3 || form == 5) b += 8 * A->n_rows; // the per-row diagonal values
+    if (r.form == 3 || r.form == 5) b += 8 * A->n_rows; // the per-row diagonal values
     *bytes = b;
     return BIS_OK;
 }

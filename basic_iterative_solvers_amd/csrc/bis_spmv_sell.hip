@@ -74,7 +74,6 @@ struct bis_sellwin {
 
 namespace {
 
-constexpr int kSwRows = 256;
 constexpr int kSwRuns = 32;
 constexpr int kSwRunGran = 64; // granules per run at most
 constexpr int kSwHash = 4096;
@@ -1707,8 +1706,6 @@ void bis_spmv_win8_drop(bis_mat *A) {
 
 int bis_spmv_win8_blocks(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->n_blocks : 0; }
 int bis_spmv_win8_rows(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->R : 0; }
-int64_t bis_spmv_win8_slices(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->n_slices : 0; }
-int64_t bis_spmv_win8_partials(const bis_mat *A) { return A->sw8_state == 1 ? (int64_t)A->sw8->n_blocks * 4 : 0; } // fused dot: one per wave
 bool bis_spmv_win8_implied(const bis_mat *A) { return A->sw8_state == 1 && A->sw8->slice_rec != nullptr; }
 // bytes of the form's own arrays one launch reads: the stream (with its padding), block headers, slice offsets.  The implied-slot
 // layout: 2048 bytes of values per chunk, 8 bytes of slot bases per chunk of an implicit slice, 512 bytes of slots per chunk of an

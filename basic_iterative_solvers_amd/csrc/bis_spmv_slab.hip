@@ -1,4 +1,4 @@
-// bis_spmv_slab.hip -- column slabs of a matrix WITHOUT locality (bis_spmv.hip: launch_colslab).
+// bis_spmv_slab.hip -- column slabs of a matrix WITHOUT locality (bis_spmv.hip: colslab_try).
 //
 // A matrix whose rows reach all over x (config 5's `unstr:80,80,80` as generated: a mesh numbered at random) gathers x
 // through the fabric: x (12.3 MB) does not fit the 4 MB L2 of an XCD, every 8-byte operand costs a 64-byte fetch, and the

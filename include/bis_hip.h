@@ -148,7 +148,16 @@ BIS_API int bis_mat_rp_width(const bis_mat *A);
  * block's x entries copied into an LDS window by coalesced loads and the codes
  * stored per 64-row slice in lane order (sliced ELL, 12 bytes per 4 non-zeros
  * and lane, short rows padded with an arithmetically neutral entry; option
- * "spmv_sellwin" 0 switches it off).
+ * "spmv_sellwin" 0 switches it off; its denser formats report col_bytes 2 and
+ * val_bytes 0 (one 16-bit code per non-zero), col_bytes 1 and val_bytes 0 (one
+ * byte: the index of the non-zero's (column - row, value) pair) or col_bytes 0
+ * (a 32-bit mask of pairs per ROW)), 6 = the window + sliced-ELL form with the
+ * 8-byte values streamed (col_bytes 2: the window slot, also where the slots are
+ * implied; matrices without a dictionary; option "spmv_win8" 0 switches it off),
+ * 7 = the CRS-value kernel in K passes over column slabs (n_dict = K).  Form 0
+ * also covers the wave-per-row kernel of very long rows (col_bytes 4) and the
+ * opt-in x-window kernel (col_bytes 2).  The report names what bis_spmv launches
+ * and builds nothing else.
  * All are lossless re-encodings of the CRS arrays, which stay authoritative:
  * same products, same summation order, bit-identical y.  Option
  * "spmv_valdict" 0 switches the dictionary off, 1 allows form 1 only. */
