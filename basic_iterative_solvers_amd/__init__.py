@@ -16,7 +16,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "lib", "libbis_hip.so")
 
-PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7})
+PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8})
 
 _lib = None
 
@@ -39,6 +39,7 @@ def load_library():
         _lib.bis_mat_sweep_kernel.restype = C.c_char_p
         _lib.bis_mat_spmv_kernel.restype = C.c_char_p
         _lib.bis_mat_ilu0_kernel.restype = C.c_char_p
+        _lib.bis_itrsv_kernel.restype = C.c_char_p
     return _lib
 
 
@@ -251,6 +252,11 @@ class Context:
         self.check(self.lib.bis_bsptrsv(self.h, Us.h, C.c_void_p(x.ptr), C.c_void_p(D.ptr),
                                         C.c_void_p(b.ptr)))
 
+    def itrsv(self, T, D_inv, b, x, work, n_sweeps):
+        """x ~ (D + T)^-1 b by n_sweeps Jacobi-Richardson steps on the strict triangle T (bis_itrsv); work: n entries of scratch."""
+        self.check(self.lib.bis_itrsv(self.h, T.h, C.c_void_p(D_inv.ptr), C.c_void_p(b.ptr), C.c_void_p(x.ptr),
+                                      C.c_void_p(work.ptr) if work is not None else C.c_void_p(), C.c_int(int(n_sweeps))))
+
     def _ew3(self, fn, r, a, b, scale, n=None):
         n = r.n if n is None else n
         self.check(fn(self.h, C.c_void_p(r.ptr), C.c_void_p(a.ptr), C.c_void_p(b.ptr), _i64(n),
@@ -431,6 +437,11 @@ class Mat:
     def ilu0_kernel(self):
         """Name of the elimination kernel that factorised this ILU(0) L factor (bis_mat_ilu0_kernel); "" for other matrices."""
         return self.ctx.lib.bis_mat_ilu0_kernel(self.h).decode()
+
+    def itrsv_kernel(self):
+        """Name of the path the last bis_itrsv step on this triangle took (bis_itrsv_kernel): "itrsv_fused_rowblock" or
+        "itrsv spmv+epilogue form=F"."""
+        return self.ctx.lib.bis_itrsv_kernel(self.h).decode()
 
     def retune(self):
         """Rebuild everything derived from the CRS arrays (bis_mat_retune): required after writing values in place."""

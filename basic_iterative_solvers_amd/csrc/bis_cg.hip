@@ -328,7 +328,7 @@ bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                      const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D,
                                      int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, cg && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_ILU0 && outer_iters >= 1 && inner_iters >= 0,
+    BIS_REQUIRE(ctx, cg && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_ILU0_ITER && outer_iters >= 1 && inner_iters >= 0,
                 "bis_cg_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !cg->initialised && cg->enqueued == 0, "bis_cg_set_preconditioner: call it before bis_cg_init / bis_cg_iterate");
     if (cg->z == cg->r) { // z aliased r (no preconditioner at creation): it needs its own storage now

@@ -210,6 +210,7 @@ struct bis_mat {
     const char *sweep_kernel[2] = {"", ""}; // the kernel the last forward / backward sweep on this triangle ran (bis_mat_sweep_kernel)
     const char *spmv_kernel[2] = {"", ""};  // the kernel the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)
     const char *ilu0_kernel = "";           // the elimination kernel that made this ILU(0) L factor (bis_mat_ilu0_kernel)
+    const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \
@@ -315,6 +316,10 @@ bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
 size_t bis_spmv_partials_bound(const bis_mat *A);
 bis_status bis_spmv_trsv_level(bis_ctx *ctx, const bis_mat *T, const double *x, double *y,
                                const double *b, const double *D);
+// one step of bis_itrsv: x_new = (b - T x_old) * D_inv.  *form = -1: done, fused into the row-block kernel; otherwise
+// x_new = T x_old in the SpMV form of that public number, and the caller finishes the step in place
+bis_status bis_spmv_itrsv_step(bis_ctx *ctx, const bis_mat *T, const double *x_old, double *x_new, const double *b,
+                               const double *D_inv, int *form);
 // rows [ra,rb) of A as a matrix sharing A's arrays (y must be offset by ra)
 bis_status bis_mat_row_view(bis_ctx *ctx, const bis_mat *A, int64_t ra,
                             int64_t rb, bis_mat **out);

@@ -114,6 +114,8 @@ __device__ __forceinline__ int pk_decode(unsigned code, const int (&B)[8], int l
 // range: y[r] = (w[r] - (A x)[r]) / dinv_or_d[r], i.e. x_level = (b - T x)/D
 // (kernels.hpp:70,102); y may be the same array as x -- rows of one level do
 // not reference each other.
+// MODE 3: one Jacobi-Richardson step on a triangle (bis_itrsv.hip): y[r] = (w[r] - (A x)[r]) * dinv[r], the row sum
+// exactly MODE 0's, subtraction and multiplication rounded separately; every row reads x, so y must not be x.
 //
 // PK != 0: the column stream is the packed one (2 B per non-zero): code =
 // segment:3 | offset:13, column = seg_base[8*b + segment] + offset.  PK 1 picks
@@ -280,9 +282,11 @@ __global__ __launch_bounds__(T) void spmv_rowblock_kernel(
         const int a = (int)((int64_t)rp_a - s4), z = (int)((int64_t)rp_z - s4);
         // (acc_y: this launch is a later column slab of the matrix -- bis_spmv_slab.hip -- and continues the row's sum where the
         // slab before it left it in y)
-        double acc = (MODE != 2 && acc_y) ? y[r] : 0.0;
+        double acc = (MODE < 2 && acc_y) ? y[r] : 0.0;
         for (int j = a; j < z; ++j) acc += prod[j];
-        if (MODE == 2) y[r] = (w[r] - acc) / partials[r];
+        if (MODE == 3) // (b and 1/D are streamed once: non-temporal, like the elementwise kernels' operands)
+            y[r] = __dmul_rn(__dsub_rn(__builtin_nontemporal_load(w + r), acc), __builtin_nontemporal_load(partials + r));
+        else if (MODE == 2) y[r] = (w[r] - acc) / partials[r];
         else y[r] = acc;
         if (FUSE_DOT) dot_acc = fma(acc, w[r], dot_acc);
     }
@@ -903,7 +907,8 @@ void launch_variant(const SpmvArgs &a) {
                        a.nb, a.remap_arg, a.w, a.partials, a.pk, a.pk_base, a.seg_base, a.col_max, a.stop, a.acc_y)
 #define BIS_LVM(PK)                                                                               \
     do {                                                                                          \
-        if (a.mode == 2) BIS_LV(PK, 2);                                                           \
+        if (a.mode == 3) BIS_LV(PK, 3);                                                           \
+        else if (a.mode == 2) BIS_LV(PK, 2);                                                      \
         else if (a.mode == 1) BIS_LV(PK, 1);                                                      \
         else BIS_LV(PK, 0);                                                                       \
     } while (0)
@@ -1651,6 +1656,29 @@ static bis_status spmv_report(bis_ctx *ctx, const bis_mat *A, SpmvPlan *p, SpmvR
         break;
     }
     }
+    return BIS_OK;
+}
+
+// internal (bis_itrsv.hip): one step x_new = (b - T x_old) * D_inv of the iterative triangular solve.  Where the plain SpMV
+// of T resolves to the CRS-value row-block kernel, that kernel runs with the step as its epilogue (MODE 3: the product is
+// never written and read back) and *form = -1; every other form -- the wave-per-row and x-window kernels, the dictionary
+// forms, win8, column slabs -- runs as it is, T x_old into x_new, *form = its public number (bis_mat_spmv_stream_info), and
+// the caller's epilogue kernel finishes the step in place.
+bis_status bis_spmv_itrsv_step(bis_ctx *ctx, const bis_mat *T, const double *x_old, double *x_new, const double *b,
+                               const double *D_inv, int *form) {
+    SpmvPlan p;
+    SpmvReport r{};
+    if (bis_status st = spmv_report(ctx, T, &p, &r)) return st;
+    if (p.form != kFormRowblock) {
+        *form = r.form;
+        return bis_spmv_launch(ctx, T, x_old, x_new, nullptr, nullptr);
+    }
+    *form = -1;
+    p.a.mode = 3;
+    p.a.x = x_old; p.a.y = x_new; p.a.w = b; p.a.partials = const_cast<double *>(D_inv);
+    p.a.stop = ctx->spmv_stop;
+    if (bis_status st = spmv_launch_plan(ctx, T, p)) return st;
+    BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
 }
 

@@ -859,6 +859,10 @@ bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_m
                                     int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1, "bis_apply_preconditioner: bad arguments");
+    if (pc == BIS_PC_ILU0_ITER)
+        BIS_REQUIRE(ctx, L_strict && U_strict && inner_iters >= 0 && (n == 0 || (tmp && work && tmp != work && tmp != output &&
+                         tmp != input && work != output && work != input)),
+                    "bis_apply_preconditioner: ILU0_ITER needs both factors, inner_iters >= 0, and tmp, work distinct from each other, output and input");
     double *input_storage = nullptr;
     bis_status st = BIS_OK;
     if (outer_iters > 1) { // :348-352 (the one place the reference allocates in a kernel)
@@ -896,6 +900,10 @@ bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_m
         case BIS_PC_ILU0:
             st = bis_sptrsv(ctx, L_strict, tmp, L_D, input);                       // :390
             if (st == BIS_OK) st = bis_bsptrsv(ctx, U_strict, output, U_D, tmp);   // :394
+            break;
+        case BIS_PC_ILU0_ITER: // (not in the reference) both solves as bis_itrsv; A_D_inv carries 1 / U_D
+            st = bis_itrsv(ctx, L_strict, L_D, input, tmp, work, inner_iters);
+            if (st == BIS_OK) st = bis_itrsv(ctx, U_strict, A_D_inv, tmp, output, work, inner_iters);
             break;
         default:
             st = bis_copy_vector(ctx, output, input, n);                           // :398

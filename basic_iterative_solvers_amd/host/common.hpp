@@ -51,16 +51,21 @@
 using Interface = void *; // the SMAX seam of the reference (common.hpp:18-24) is the C ABI here
 #define SMAX_ARGS(...)
 
-enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47
+enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8) is this build's addition
     None, Jacobi, GaussSeidel, BackwardsGaussSeidel, SymmetricGaussSeidel, TwoStageGS,
-    SymmetricTwoStageGS, ILU0
+    SymmetricTwoStageGS, ILU0, ILU0Iter
 };
+
+// -inner K: inner sweeps of the two-stage Gauss-Seidel types and of -p ilu0it, at run time; the default is the
+// compile-time PRECOND_INNER_ITERS, so a command line without the flag runs what it always ran
+inline int &precond_inner_iters() { static int k = PRECOND_INNER_ITERS; return k; }
 enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB };
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
                               "symmetric-gauss-seidel", "two-stage gauss-seidel",
                               "symmetric two-stage gauss-seidel", "incomplete LU(0)"};
+    if (t == PrecondType::ILU0Iter) return "incomplete LU(0), iterative solves (" + std::to_string(precond_inner_iters()) + ")";
     return n[static_cast<int>(t)];
 }
 inline std::string to_string(SolverType t) {
@@ -74,6 +79,7 @@ struct Args {
     SolverType method{};
     PrecondType preconditioner{};
     int restart_length = 10;
+    int inner_iters = PRECOND_INNER_ITERS; // -inner K (precond_inner_iters())
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

@@ -80,7 +80,7 @@ inline void two_stage_gauss_seidel(const MatrixCRS *strict, double *tmp, double 
                                    double *input, double *output, const int N, int = 0,
                                    Interface * = nullptr, const std::string & = "") {
     bis::check(bis_two_stage_gauss_seidel(bis::ctx(), strict->dev, tmp, work, D_inv, input, output, N,
-                                          PRECOND_INNER_ITERS), "two_stage_gauss_seidel");
+                                          precond_inner_iters()), "two_stage_gauss_seidel");
 }
 inline void apply_preconditioner(const PrecondType pc, const int N, const MatrixCRS *L_strict,
                                  const MatrixCRS *U_strict, double *A_D, double *A_D_inv, double *L_D,
@@ -90,7 +90,7 @@ inline void apply_preconditioner(const PrecondType pc, const int N, const Matrix
                                         L_strict ? L_strict->dev : nullptr,
                                         U_strict ? U_strict->dev : nullptr, A_D, A_D_inv, L_D, U_D,
                                         output, input, tmp, work, PRECOND_OUTER_ITERS,
-                                        PRECOND_INNER_ITERS), "apply_preconditioner");
+                                        precond_inner_iters()), "apply_preconditioner");
 }
 
 // ---- device-scalar forms (this build's addition): the factor / the result lives in device memory, no host round trip.

@@ -57,7 +57,7 @@ class ConjugateGradientSolver : public Solver {
             if (preconditioner != PrecondType::None && preconditioner != PrecondType::Jacobi)
                 bis::check(bis_cg_set_preconditioner(bis::ctx(), fcg, (int)preconditioner, L_strict ? L_strict->dev : nullptr,
                                                      U_strict ? U_strict->dev : nullptr, A_D, A_D_inv, L_D, U_D,
-                                                     PRECOND_OUTER_ITERS, PRECOND_INNER_ITERS), "bis_cg_set_preconditioner");
+                                                     PRECOND_OUTER_ITERS, precond_inner_iters()), "bis_cg_set_preconditioner");
             bis::check(bis_cg_init(bis::ctx(), fcg, tolerance, &residual_norm), "bis_cg_init");
             collected_residual_norms[collected_residual_norms_count++] = residual_norm;
             return;

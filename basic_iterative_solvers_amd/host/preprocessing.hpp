@@ -36,7 +36,7 @@ inline void factor_LU(Solver *s) {
         s->L_strict->adopt(Ls);
         s->U_strict->adopt(Us);
     }
-    if (s->preconditioner == PrecondType::ILU0) {
+    if (s->preconditioner == PrecondType::ILU0 || s->preconditioner == PrecondType::ILU0Iter) {
         // The reference's wired-in factor_ILU0_new needs the SMAX library (SURVEY.md
         // section 5, defect 2); this is its serial factor_ILU0_old arithmetic,
         // level-scheduled on the device.  Overwrites L_strict/U_strict, L_D, U_D.
@@ -47,6 +47,8 @@ inline void factor_LU(Solver *s) {
         s->U_strict->free_host();
         s->L_strict->adopt(Ls);
         s->U_strict->adopt(Us);
+        // -p ilu0it multiplies by the pivots' reciprocals: A_D_inv carries 1 / U_D for that type (L_D is the vector of ones)
+        if (s->preconditioner == PrecondType::ILU0Iter) elemwise_div_vectors(s->A_D_inv, s->L_D, s->U_D, s->N);
     }
 }
 

@@ -5,7 +5,8 @@
 // with SCAMAC strings when built with -DUSE_SCAMAC, main.cpp:48-54):
 //     hpcg:N | hpcg:NX,NY,NZ | anderson:L[,shift=S][,W=w][,t=t][,seed=k] | fem:NX[,NY,NZ][,keep=K][,seed=k] | unstr:NX[,NY,NZ][,keep=K][,seed=k]
 // and `-unfused` / `-dev K` select the kernel-by-kernel CG and the device;
-// `-perm mc` applies the multi-colour reordering of utilities/permute.hpp.
+// `-perm mc` applies the multi-colour reordering of utilities/permute.hpp; `-p ilu0it` is ILU(0) with iterative
+// triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st).
 #pragma once
 
 #include <sys/stat.h>
@@ -47,18 +48,27 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 {"j", PrecondType::Jacobi}, {"gs", PrecondType::GaussSeidel},
                 {"bgs", PrecondType::BackwardsGaussSeidel}, {"sgs", PrecondType::SymmetricGaussSeidel},
                 {"2st", PrecondType::TwoStageGS}, {"s2st", PrecondType::SymmetricTwoStageGS},
-                {"ilu0", PrecondType::ILU0}};
+                {"ilu0", PrecondType::ILU0}, {"ilu0it", PrecondType::ILU0Iter}};
             auto it = pcs.find(pt);
             if (it == pcs.end()) {
                 fprintf(stderr, "ERROR: assign_cli_inputs: Please choose an available preconditioner type: "
                                 "\n-p j (Jacobi)\n-p gs (Gauss-Seidel)\n-p bgs (Backwards Gauss-Seidel)"
                                 "\n-p sgs (Symmetric Gauss-Seidel)\n-p 2st (2 Stage Gauss-Seidel)"
-                                "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)\n");
+                                "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)"
+                                "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)\n");
                 exit(EXIT_FAILURE);
             }
             a->preconditioner = it->second;
         } else if (arg == "-scale" && i + 1 < argc) a->num_scale = (bool)atoi(argv[++i]);
         else if (arg == "-rl" && i + 1 < argc) a->restart_length = atoi(argv[++i]);
+        else if (arg == "-inner" && i + 1 < argc) {
+            a->inner_iters = atoi(argv[++i]);
+            if (a->inner_iters < 0) {
+                fprintf(stderr, "ERROR: -inner K: K >= 0\n");
+                exit(EXIT_FAILURE);
+            }
+            precond_inner_iters() = a->inner_iters;
+        }
         else if (arg == "-unfused") a->unfused = true;
         else if (arg == "-hostscalars") a->host_scalars = true;
         else if (arg == "-trsv" && i + 1 < argc) {

@@ -64,7 +64,9 @@ enum {
     BIS_PC_SYMMETRIC_GAUSS_SEIDEL = 4,
     BIS_PC_TWO_STAGE_GS = 5,
     BIS_PC_SYMMETRIC_TWO_STAGE_GS = 6,
-    BIS_PC_ILU0 = 7
+    BIS_PC_ILU0 = 7,
+    /* not in the reference: ILU(0) whose two triangular solves are bis_itrsv with inner_iters steps each */
+    BIS_PC_ILU0_ITER = 8
 };
 
 typedef struct bis_ctx bis_ctx; /* device + stream + scratch (SMAX::Interface
@@ -436,8 +438,33 @@ BIS_API bis_status bis_two_stage_gauss_seidel(bis_ctx *ctx,
                                               const double *input,
                                               double *output, int64_t n,
                                               int inner_iters);
+/* Iterative triangular solve (no reference counterpart; the reference has the idea for Gauss-Seidel only,
+ * two_stage_gauss_seidel): x ~ (D + T_strict)^-1 b for a strictly lower OR upper triangular T_strict (the same code: no
+ * row depends on another inside a step), by n_sweeps Jacobi-Richardson steps.  D_inv holds 1 / D.  The arithmetic:
+ *     x_0[i]     = D_inv[i] * b[i]
+ *     s_i        = (T_strict x_k)[i]              exactly the value bis_spmv(T_strict, x_k) gives: same products, same order
+ *     x_{k+1}[i] = (b[i] - s_i) * D_inv[i]        subtraction and multiplication rounded separately (no fma)
+ * for k = 0 .. n_sweeps - 1.  T_strict is nilpotent: with as many steps as it has dependency levels the result is the
+ * exact solve's up to rounding; fewer steps give the truncated Neumann series sum_{j <= n_sweeps} (-D^-1 T)^j D^-1 b.
+ * x and work (n entries each) alternate as x_k; the result is in x for every n_sweeps >= 0 (work is not touched when
+ * n_sweeps = 0 and may then be NULL).  x must not alias b, work or D_inv, work must not alias b or D_inv:
+ * BIS_ERR_INVALID.  Stream-ordered, non-blocking; nothing is allocated once the SpMV form of T_strict exists (it is
+ * built at the first bis_spmv / bis_itrsv / bis_mat_spmv_stream_info on T_strict, as for bis_spmv).
+ * A step is one launch where that form is the CRS-value row-block kernel (the step is its epilogue), else the SpMV
+ * in its form followed by one elementwise launch.  bis_itrsv_kernel names the path the last step on T_strict took:
+ * "itrsv_fused_rowblock" or "itrsv spmv+epilogue form=F", F the form number of bis_mat_spmv_stream_info (static
+ * string; "" before the first step). */
+BIS_API bis_status bis_itrsv(bis_ctx *ctx, const bis_mat *T_strict, const double *D_inv,
+                             const double *b, double *x, double *work, int n_sweeps);
+BIS_API const char *bis_itrsv_kernel(const bis_mat *T_strict);
 /* apply_preconditioner, kernels.hpp:336-414: output = M^-1 input
- * (outer_iters = PRECOND_OUTER_ITERS, inner_iters = PRECOND_INNER_ITERS). */
+ * (outer_iters = PRECOND_OUTER_ITERS, inner_iters = PRECOND_INNER_ITERS).
+ * BIS_PC_ILU0_ITER (8): tmp = bis_itrsv(L_strict, L_D, input, inner_iters), then output = bis_itrsv(U_strict,
+ * A_D_inv, tmp, inner_iters).  L_D is the vector of ones of bis_mat_ilu0, its own reciprocal; for this type the
+ * A_D_inv argument carries 1 / U_D (bis_elemwise_div_vectors(A_D_inv, L_D, U_D) after bis_mat_ilu0); A_D and U_D are
+ * not read.  Scratch: tmp holds the lower solve's result and work (n entries, as for the two-stage types) is the
+ * alternate buffer of both solves; the steps finish in place, so no third buffer is needed.  tmp and work must be
+ * distinct from each other and from output and input (BIS_ERR_INVALID); output may alias input. */
 BIS_API bis_status bis_apply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
