@@ -13,6 +13,19 @@
 #include "bis_hip.h"
 
 struct bis_trsv_plan;
+struct bis_trsv_tiled;
+struct bis_trsv_chain;
+// What the triangular sweeps of one direction have built on a matrix, all lazily (trsv_resolve, bis_sptrsv.hip).  A value
+// change (bis_mat_values_changed) drops the tiled plan with its `tried` flag (it holds a copy of the values) and the level
+// plan (its row views carry dictionaries); the chained plan and its flag stay (chains depend on the pattern only).
+// Destroying the matrix drops everything.
+struct bis_trsv_side {
+    bis_trsv_plan *level = nullptr;  // level analysis, row views, the level-scheduled kernels' scratch
+    bis_trsv_tiled *tiled = nullptr; // bis_trsv_tiled.hip, tried first: where it exists no level analysis is made
+    bis_trsv_chain *chain = nullptr; // bis_trsv_chain.hip, for matrices without a grid: built from the level analysis
+    bool tiled_tried = false, chain_tried = false; // the build ran (whether or not a plan came of it)
+    const char *kernel = "";         // the kernel the last sweep of this direction ran (bis_mat_sweep_kernel)
+};
 
 struct bis_named_kernel {
     int type = 0;
@@ -198,16 +211,7 @@ struct bis_mat {
     // structured-grid hint (generators, bis_mat_set_grid_hint): row = ((z*ny + y)*nx + x)*dof + d; 0 = none.
     // Inherited by the strict triangles and the ILU(0) factors; the tiled sweep cuts its tiles in all grid directions with it.
     int64_t grid[4] = {0, 0, 0, 0};
-    // triangular-solve plans (built lazily)
-    bis_trsv_plan *plan_fwd = nullptr;
-    bis_trsv_plan *plan_bwd = nullptr;
-    // the tiled natural-order sweep's plans (bis_trsv_tiled.hip), tried first: where they exist no level analysis is made
-    struct bis_trsv_tiled *tiled_fwd = nullptr, *tiled_bwd = nullptr;
-    bool tiled_tried_fwd = false, tiled_tried_bwd = false;
-    // the chained sweep's plans (bis_trsv_chain.hip), for matrices without a grid: built from the level analysis
-    struct bis_trsv_chain *chain_fwd = nullptr, *chain_bwd = nullptr;
-    bool chain_tried_fwd = false, chain_tried_bwd = false;
-    const char *sweep_kernel[2] = {"", ""}; // the kernel the last forward / backward sweep on this triangle ran (bis_mat_sweep_kernel)
+    bis_trsv_side trsv[2]; // what the sweeps built for this triangle, forward / backward (bis_trsv_side_of)
     const char *spmv_kernel[2] = {"", ""};  // the kernel the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)
     const char *ilu0_kernel = "";           // the elimination kernel that made this ILU(0) L factor (bis_mat_ilu0_kernel)
     const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
@@ -366,6 +370,11 @@ void bis_mat_free_meta(bis_mat *A);
 // after the values of A changed in place: drops every structure derived from them (dictionaries, code streams, sweep plans)
 void bis_mat_values_changed(bis_mat *A);
 void bis_trsv_plan_destroy(bis_trsv_plan *p);
+inline bis_trsv_side &bis_trsv_side_of(bis_mat *A, bool backward) { return A->trsv[backward ? 1 : 0]; }
+// drops the tiled plans, their `tried` flags and the level plans of both directions; with chains = true the chained plans
+// and their flags as well (see bis_trsv_side)
+void bis_trsv_drop(bis_mat *A, bool chains);
+bool bis_trsv_holds_plans(const bis_mat *A); // some direction holds a level, tiled or chained plan
 // `to` has the sparsity pattern of `from` (ILU(0): the factor L and the strict lower triangle of A the elimination was scheduled
 // by): it takes over from's level plan (levels, level-sorted rows) instead of analysing the same pattern again.  No-op when
 // from has none, to has one, or the plan refers to from's storage (row views).
@@ -373,7 +382,6 @@ void bis_trsv_plan_adopt(bis_mat *to, bis_mat *from, bool backward);
 bis_status bis_mat_split_strict_impl(bis_ctx *ctx, const bis_mat *A, bis_mat **L_strict,
                                      bis_mat **U_strict, double *D, double *D_inv, bool check_diag);
 // tiled natural-order sweep (bis_trsv_tiled.hip); *out stays null when the matrix does not qualify
-struct bis_trsv_tiled;
 bis_status bis_trsv_tiled_build(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_tiled **out);
 bis_status bis_trsv_tiled_solve(bis_ctx *ctx, bis_trsv_tiled *p, double *x, const double *D, const double *b);
 void bis_trsv_tiled_destroy(bis_trsv_tiled *p);
@@ -383,7 +391,6 @@ bis_status bis_trsv_analyse_device(bis_ctx *ctx, const bis_mat *T, bool backward
                                    std::vector<int64_t> &level_ptr, int &n_levels, int64_t &max_width,
                                    bool &triangular, int **level_out = nullptr);
 // chained sweep (bis_trsv_chain.hip); *out stays null where it does not apply
-struct bis_trsv_chain;
 bis_status bis_trsv_chain_build(bis_ctx *ctx, const bis_mat *T, bool backward, const int *level_dev, int n_levels,
                                 bis_trsv_chain **out);
 bis_status bis_trsv_chain_solve(bis_ctx *ctx, const bis_mat *T, bis_trsv_chain *p, double *x, const double *D, const double *b);

@@ -432,13 +432,7 @@ bis_status finalize_t(bis_ctx *ctx, bis_mat *A) {
 // hold a copy of the values in their entry stream), the level plans (their row views carry dictionaries of their own).
 void bis_mat_values_changed(bis_mat *A) {
     bis_spmv_drop_valdict(A);
-    bis_trsv_tiled_destroy(A->tiled_fwd);
-    bis_trsv_tiled_destroy(A->tiled_bwd);
-    A->tiled_fwd = A->tiled_bwd = nullptr;
-    A->tiled_tried_fwd = A->tiled_tried_bwd = false;
-    bis_trsv_plan_destroy(A->plan_fwd);
-    bis_trsv_plan_destroy(A->plan_bwd);
-    A->plan_fwd = A->plan_bwd = nullptr;
+    bis_trsv_drop(A, /*chains=*/false);
 }
 
 void bis_mat_free_meta(bis_mat *A) {
@@ -650,12 +644,7 @@ bis_status bis_mat_destroy(bis_ctx *ctx, bis_mat *A) {
     BIS_CTX_OK(ctx);
     if (!A) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    bis_trsv_plan_destroy(A->plan_fwd);
-    bis_trsv_plan_destroy(A->plan_bwd);
-    bis_trsv_tiled_destroy(A->tiled_fwd);
-    bis_trsv_tiled_destroy(A->tiled_bwd);
-    bis_trsv_chain_destroy(A->chain_fwd);
-    bis_trsv_chain_destroy(A->chain_bwd);
+    bis_trsv_drop(A, /*chains=*/true);
     if (!A->view) {
         hipFree(A->row_ptr);
         hipFree(A->col);
@@ -682,7 +671,7 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
     BIS_REQUIRE(ctx, A && !A->view, "bis_mat_tune_placement: owning matrix required");
     // the streamed arrays are re-allocated: row views made earlier -- the triangular-solve plans cache some -- would
     // keep pointing at the freed ones
-    BIS_REQUIRE(ctx, !A->plan_fwd && !A->plan_bwd && !A->tiled_fwd && !A->tiled_bwd && !A->chain_fwd && !A->chain_bwd, "bis_mat_tune_placement: call it before the first triangular solve on this matrix");
+    BIS_REQUIRE(ctx, !bis_trsv_holds_plans(A), "bis_mat_tune_placement: call it before the first triangular solve on this matrix");
     if (first_ms) *first_ms = 0.0;
     if (best_ms) *best_ms = 0.0;
     if (A->nnz == 0 || A->n_rows == 0 || max_trials <= 0) return BIS_OK;

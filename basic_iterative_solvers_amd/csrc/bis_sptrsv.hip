@@ -1,14 +1,37 @@
-// bis_sptrsv.hip -- sparse triangular solves (reference kernels.hpp:54-117,
-// serial there) and the preconditioner dispatcher built on them
-// (kernels.hpp:312-414).
+// bis_sptrsv.hip -- sparse triangular solves (reference kernels.hpp:54-117, serial there): the dispatcher of every
+// sweep form (trsv_resolve, trsv_solve) and the level-scheduled kernels.  The tiled and the chained sweep have files of
+// their own (bis_trsv_tiled.hip, bis_trsv_chain.hip); the preconditioner built on the sweeps is in bis_precond.hip.
 //
-// Three execution modes, chosen from the structure of the triangle (get_plan):
+// The forms of x = (D + T)^-1 b, in the order in which trsv_resolve tries them (the only place that does; it reads the
+// options in effect at every call, only the builds and the trial's outcome are kept on the matrix, bis_trsv_side):
 //
-//  (1) colour-sorted matrices (`-perm mc`): at most 64 contiguous blocks of mutually
-//      independent rows (bis_analysis.hip finds them on the device) -- one streaming
-//      SpMV launch with the triangular epilogue per block (bis_spmv.hip MODE 2).
-//  (2) everything else (natural orderings: hundreds to thousands of dependency
-//      levels): level-scheduled, synchronisation-free solve in ONE launch.
+//   form              kernel                     taken where                                          switched off by
+//   ----------------  -------------------------  ---------------------------------------------------  -----------------------
+//   tiled             trsv_tiled_kernel          the tiled plan applies (grid hint; the plan checks   trsv_tiled = 0;
+//                                                the dependency order itself: no level analysis)      trsv_inject_loss > 0,
+//                                                                                                     trsv_one_xcd > 0
+//     ... tried AFTER the chained form ("chain_first") on grids with several unknowns per node, 16384 <= n <=
+//     1.2 M (pairs / 2560)^1.5 rows, trsv_tiled < 0 and trsv_chain < 0; where it then applies the level plan goes
+//   row-block views   spmv_rowblock_kernel (...) at most 64 contiguous blocks of mutually independent  trsv_host_analysis > 0
+//                                                rows (colour-sorted; get_plan): one streaming SpMV   (no block search: only
+//                                                launch with the triangular epilogue per block        ascending level ranges)
+//   per-level         trsv_level_kernel (...)    at most 64 levels that are not such blocks           --
+//   chained           trsv_chain_kernel          the chained plan applies (chains of >= 3 rows on     trsv_chain = 0;
+//                                                average, residency bound); built once per side from  trsv_inject_loss > 0,
+//                                                the level analysis, whose level array then goes      trsv_one_xcd > 0
+//   wave per row      sptrsv_wave_kernel         rows of > 16 entries, or > 8 on levels of at most    trsv_wave = 0,
+//                                                16 n_cus rows on average -- or the first sweep's     trsv_one_xcd > 0
+//                                                trial kept it, or trsv_wave = 1
+//   lane per row      sptrsv_syncfree_kernel     everything else
+//
+//   The trial (trsv_trial != 0): where the rule says "wave per row" on a triangle of >= 200000 rows, levels of >= 1024
+//   rows on average and rows of <= 128 entries, with no trsv_grid, trsv_wave, one-XCD mode or loss injection, the first
+//   sweep runs both kernels twice, times the second run and keeps the lane kernel below 0.9 x the wave kernel's time.
+//   Inside a device schedule, or where x aliases b or D, the choice stays open (the rule serves that sweep).
+//   trsv_grid overrides both grids (the wave grid stays capped by residency and device_share), trsv_batch the lane
+//   kernel's batch, trsv_by_pos = 0 keeps the scratch in row order, trsv_wave_wgs sets the wave grid's workgroups per CU.
+//
+// The level-scheduled, synchronisation-free solve (wave / lane per row), ONE launch:
 //      analysis (once per matrix, on the device): level[r] = 1 + max level of the
 //        rows r depends on; rows stably sorted by level into perm[] so that every
 //        dependency of the row at position i sits at a position < i.
@@ -26,13 +49,12 @@
 //        spin is bounded (a lost hand-off would publish NaN instead of hanging).
 //        The publishing store is predicated inside volatile asm on the straight-line
 //        path of the wait loop -- see the hazard notes at the kernels.
-//  (3) at most 64 levels that are not contiguous: one plain launch per level.
 //
 //   The user-visible x is written with a plain store (nobody polls it), so x
 //   may alias b (gmres.hpp:173, gauss_seidel.hpp:37).
 //
 // HBM traffic ~ 12*nnz_T + 28*N algorithmic (+ 24*N for the sentinel scratch);
-// mode (2) is latency-bound on stencils: one cross-CU hand-off (~3 us) per level.
+// the level-scheduled solve is latency-bound on stencils: one cross-CU hand-off (~3 us) per level.
 #include "bis_internal.hpp"
 
 #include <algorithm>
@@ -53,9 +75,18 @@ struct bis_trsv_plan {
     // few-level orderings whose levels are contiguous row ranges: one row view per level
     std::vector<bis_mat *> level_views;
     std::vector<int64_t> level_row0;
-    int wave_choice = 0;   // level-scheduled kernels: 0 not decided yet, 1 a wave per row, 2 a lane per row (trial at the first sweep, see trsv_solve_impl)
+    int wave_choice = 0;   // level-scheduled kernels: 0 not decided yet, 1 a wave per row, 2 a lane per row (trial at the first sweep, see trsv_trial)
     float trial_ms[2] = {0.f, 0.f};
 };
+
+static void drop_row_views(bis_trsv_plan *p) { // row views: only their block tables are theirs
+    for (bis_mat *v : p->level_views) {
+        bis_mat_free_meta(v);
+        delete v;
+    }
+    p->level_views.clear();
+    p->level_row0.clear();
+}
 
 void bis_trsv_plan_destroy(bis_trsv_plan *p) {
     if (!p) return;
@@ -64,20 +95,37 @@ void bis_trsv_plan_destroy(bis_trsv_plan *p) {
     hipFree(p->pcol);
     hipFree(p->level);
     hipFree(p->ticket);
-    for (bis_mat *v : p->level_views) { // row views: only their block tables are theirs
-        bis_mat_free_meta(v);
-        delete v;
-    }
+    drop_row_views(p);
     delete p;
 }
 
 void bis_trsv_plan_adopt(bis_mat *to, bis_mat *from, bool backward) {
     if (!to || !from || to == from) return;
-    bis_trsv_plan *&src = backward ? from->plan_bwd : from->plan_fwd;
-    bis_trsv_plan *&dst = backward ? to->plan_bwd : to->plan_fwd;
+    bis_trsv_plan *&src = bis_trsv_side_of(from, backward).level;
+    bis_trsv_plan *&dst = bis_trsv_side_of(to, backward).level;
     if (!src || dst || !src->level_views.empty() || to->n_rows != from->n_rows || to->nnz != from->nnz || to->rp64 != from->rp64) return;
     dst = src;
     src = nullptr;
+}
+
+void bis_trsv_drop(bis_mat *A, bool chains) {
+    for (bis_trsv_side &s : A->trsv) {
+        bis_trsv_tiled_destroy(s.tiled);
+        s.tiled = nullptr;
+        s.tiled_tried = false;
+        bis_trsv_plan_destroy(s.level);
+        s.level = nullptr;
+        if (!chains) continue;
+        bis_trsv_chain_destroy(s.chain);
+        s.chain = nullptr;
+        s.chain_tried = false;
+    }
+}
+
+bool bis_trsv_holds_plans(const bis_mat *A) {
+    for (const bis_trsv_side &s : A->trsv)
+        if (s.level || s.tiled || s.chain) return true;
+    return false;
 }
 
 namespace {
@@ -422,9 +470,23 @@ bool check_triangular(const RP *rp, const int32_t *col, int64_t n, bool backward
     return true;
 }
 
+// One row view of T per contiguous row range [first, second), in sweep order.  A failed bis_mat_row_view drops the views
+// made so far (as the plan's destructor does) and returns its status: what follows is the caller's decision.
+bis_status add_row_views(bis_ctx *ctx, const bis_mat *T, bis_trsv_plan *p, const std::vector<std::pair<int64_t, int64_t>> &ranges) {
+    for (const auto &r : ranges) {
+        bis_mat *v = nullptr;
+        const bis_status st = bis_mat_row_view(ctx, T, r.first, r.second, &v);
+        if (st != BIS_OK) { drop_row_views(p); return st; }
+        p->level_views.push_back(v);
+        p->level_row0.push_back(r.first);
+    }
+    return BIS_OK;
+}
+
+// The level plan of this side, built at the first call: the independent row blocks or the level analysis
+// (trsv_host_analysis: on the host), and the row views where the blocks / levels are contiguous row ranges.
 bis_status get_plan(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_plan **out) {
-    bis_mat *M = const_cast<bis_mat *>(T);
-    bis_trsv_plan *&slot = backward ? M->plan_bwd : M->plan_fwd;
+    bis_trsv_plan *&slot = bis_trsv_side_of(const_cast<bis_mat *>(T), backward).level;
     if (slot) { *out = slot; return BIS_OK; }
     const int64_t n = T->n_rows;
     bis_status st = BIS_OK;
@@ -453,13 +515,10 @@ bis_status get_plan(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_plan
         if (st != BIS_OK) { bis_trsv_plan_destroy(p); return st; }
         if (!bounds.empty()) {
             const int nb = (int)bounds.size() - 1;
-            for (int l = 0; l < nb && st == BIS_OK; ++l) {
-                const int64_t r0 = backward ? bounds[l + 1] : bounds[l], r1 = backward ? bounds[l] : bounds[l + 1];
-                bis_mat *v = nullptr;
-                st = bis_mat_row_view(ctx, T, r0, r1, &v);
-                if (st == BIS_OK) { p->level_views.push_back(v); p->level_row0.push_back(r0); }
-            }
-            if (st != BIS_OK) { bis_trsv_plan_destroy(p); return st; }
+            std::vector<std::pair<int64_t, int64_t>> ranges;
+            for (int l = 0; l < nb; ++l) ranges.emplace_back(bounds[backward ? l + 1 : l], bounds[backward ? l : l + 1]); // (backward: descending bounds)
+            st = add_row_views(ctx, T, p, ranges);
+            if (st != BIS_OK) { bis_trsv_plan_destroy(p); return st; } // the block search promised views: without them the sweep fails
             p->n_levels = nb;
             p->max_level_width = 0;
             for (int l = 0; l < nb; ++l) p->max_level_width = std::max<int64_t>(p->max_level_width, std::llabs(bounds[l + 1] - bounds[l]));
@@ -508,14 +567,12 @@ bis_status get_plan(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_plan
             for (int64_t i = p->level_ptr[l]; i + 1 < p->level_ptr[l + 1]; ++i)
                 if (perm[i + 1] != perm[i] + 1) { contiguous = false; break; }
         if (contiguous && (int64_t)T->chunk_nnz + T->max_row_nnz + 8 <= 8192) {
+            std::vector<std::pair<int64_t, int64_t>> ranges;
             for (int l = 0; l < p->n_levels; ++l) {
                 const int64_t r0 = perm[p->level_ptr[l]];
-                bis_mat *v = nullptr;
-                st = bis_mat_row_view(ctx, T, r0, r0 + (p->level_ptr[l + 1] - p->level_ptr[l]), &v);
-                if (st != BIS_OK) { for (auto *m : p->level_views) bis_mat_destroy(ctx, m); p->level_views.clear(); break; }
-                p->level_views.push_back(v);
-                p->level_row0.push_back(r0);
+                ranges.emplace_back(r0, r0 + (p->level_ptr[l + 1] - p->level_ptr[l]));
             }
+            (void)add_row_views(ctx, T, p, ranges); // here the views are an optimisation: without them the sweep launches per level
         }
     }
     slot = p;
@@ -523,31 +580,76 @@ bis_status get_plan(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_plan
     return BIS_OK;
 }
 
-bis_status trsv_solve_impl(bis_ctx *ctx, const bis_mat *T, bool backward, double *x, const double *D,
-                           const double *b, const char *&kernel) {
-    BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, T && (T->n_rows == 0 || (x && D && b)), "sptrsv: bad arguments");
-    BIS_REQUIRE(ctx, T->n_rows == T->n_cols, "sptrsv: square matrix required");
+enum TrsvForm { kTrsvTiled, kTrsvChained, kTrsvViews, kTrsvPerLevel, kTrsvWave, kTrsvLane };
+
+// What trsv_resolve decided for one sweep call.
+struct TrsvPlan {
+    TrsvForm form = kTrsvLane;
+    const char *kernel = ""; // what bis_mat_sweep_kernel reports after the sweep
+    bis_trsv_plan *p = nullptr; // the side's level plan (every form but the tiled one)
+    // the two level-scheduled kernels only
+    int lane_grid = 0, wave_grid = 0; // (wave_grid: sized where the wave kernel can run at this call)
+    int batch = 0;                    // lane kernel: dependencies loaded per round trip
+    const int32_t *dep = nullptr;     // columns, or their positions in the level order (pos_flag)
+    int pos_flag = 0;
+    int one_xcd = 0;
+    bool trial = false;               // this sweep times both kernels and keeps one (trsv_trial)
+    int64_t inject_loss = 0;          // test hook: the non-zero (1-based) whose dependency is redirected for this call; 0 none
+};
+
+const char *trsv_level_kernel_name(TrsvForm form) { return form == kTrsvWave ? "sptrsv_wave_kernel" : "sptrsv_syncfree_kernel"; }
+
+// builds the tiled plan of this side unless a build has been tried: side.tiled tells whether the triangle has one
+bis_status ensure_tiled(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_side &side) {
+    if (side.tiled_tried) return BIS_OK;
+    side.tiled_tried = true;
+    return bis_trsv_tiled_build(ctx, T, backward, &side.tiled);
+}
+
+// The level-scheduled kernels' scratch, at their first sweep (a matrix that ends up on the chained or the tiled sweep never
+// needs it): xs, and with by_pos the position table -- the scratch vector lives in LEVEL order (position in perm), so the
+// polls and the stores of neighbouring lanes fall into the same cache lines; pcol = positions of the columns.
+bis_status ensure_scratch(bis_ctx *ctx, const bis_mat *T, bis_trsv_plan *p, bool by_pos) {
     const int64_t n = T->n_rows;
-    if (n == 0) return BIS_OK;
+    if (!p->xs) {
+        const hipError_t xe = hipMalloc(&p->xs, sizeof(double) * (size_t)(n + 1)); // + one slot nobody publishes (test hook)
+        if (xe != hipSuccess) { (void)hipGetLastError(); ctx->err = "sptrsv: out of memory for the scratch vector"; return BIS_ERR_HIP; }
+    }
+    if (!by_pos || p->pcol || p->no_pos || T->nnz <= 0) return BIS_OK;
+    int32_t *inv = nullptr;
+    BIS_HIP_CHECK(ctx, hipMalloc(&inv, sizeof(int32_t) * (size_t)n));
+    hipError_t pe = hipMalloc(&p->pcol, sizeof(int32_t) * (size_t)T->nnz);
+    if (pe != hipSuccess) { hipFree(inv); p->pcol = nullptr; ctx->err = "sptrsv: out of memory for the position table"; return BIS_ERR_HIP; }
+    hipLaunchKernelGGL(invert_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       p->perm, n, inv);
+    // the view's first non-zero: row views share the parent's arrays
+    int64_t k0 = 0;
+    { int64_t a64 = 0; int32_t a32 = 0;
+      BIS_HIP_CHECK(ctx, hipMemcpyAsync(T->rp64 ? (void *)&a64 : (void *)&a32, T->row_ptr, T->rp64 ? 8 : 4, hipMemcpyDeviceToHost, ctx->stream));
+      BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+      k0 = T->rp64 ? a64 : a32; }
+    if (k0 != 0) { // a row view (absolute indices into the parent's arrays): keep the row-order scratch
+        hipFree(p->pcol); p->pcol = nullptr; p->no_pos = true;
+    } else
+    hipLaunchKernelGGL(cols_to_positions_kernel, dim3((unsigned)std::min<int64_t>((T->nnz + 255) / 256, 8192)), dim3(256), 0,
+                       ctx->stream, T->col, inv, T->nnz, p->pcol);
+    BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    hipFree(inv);
+    return BIS_OK;
+}
+
+// The one place that decides which form serves this sweep call (the table in the file header), reads the form-selecting
+// options -- those in effect now -- and runs the lazy builds; what it builds stays on the matrix (bis_trsv_side).
+bis_status trsv_resolve(bis_ctx *ctx, const bis_mat *T, bool backward, const double *x, const double *D, const double *b,
+                        TrsvPlan *out) {
+    bis_trsv_side &side = bis_trsv_side_of(const_cast<bis_mat *>(T), backward);
+    const int64_t n = T->n_rows;
+    TrsvPlan &plan = *out;
+    auto take = [&](TrsvForm form, const char *kernel) { plan.form = form; plan.kernel = kernel; return BIS_OK; };
     // natural orderings on a grid: the tiled sweep (modes: bis_trsv_tiled_build), tried first -- its plan
     // checks the dependency order itself, so where it applies the level analysis below is never made
-    const bool tiled_allowed = bis_opts().trsv_tiled != 0 && bis_opts().trsv_inject_loss <= 0 && bis_opts().trsv_one_xcd <= 0;
-    auto tiled_sweep = [&](bool *done) -> bis_status {
-        *done = false;
-        bis_mat *M = const_cast<bis_mat *>(T);
-        bis_trsv_tiled *&ts = backward ? M->tiled_bwd : M->tiled_fwd;
-        bool &tried = backward ? M->tiled_tried_bwd : M->tiled_tried_fwd;
-        if (!tried) {
-            tried = true;
-            const bis_status tst = bis_trsv_tiled_build(ctx, T, backward, &ts);
-            if (tst != BIS_OK) return tst;
-        }
-        if (!ts) return BIS_OK;
-        *done = true;
-        kernel = "trsv_tiled_kernel";
-        return bis_trsv_tiled_solve(ctx, ts, x, D, b);
-    };
+    const bool flagless_ok = bis_opts().trsv_inject_loss <= 0 && bis_opts().trsv_one_xcd <= 0; // the tiled and the chained sweep have neither the hook nor the mode
+    const bool tiled_allowed = bis_opts().trsv_tiled != 0 && flagless_ok;
     // ... except on grids with several unknowns per node and up to ~a million rows, where the chained sweep is tried first: the
     // unknowns of a node are a chain, the tiles of such a matrix are 2 x 2 x 2 nodes, and the chained sweep measured faster
     // (FEM-like 20^3 / 40^3 / 60^3 x 3: 0.40 / 0.84 / 1.42 ms against 0.53 / 1.05 / 1.63 tiled; 80^3 x 3 a tie at 2.3; 100^3 x 3
@@ -559,74 +661,40 @@ bis_status trsv_solve_impl(bis_ctx *ctx, const bis_mat *T, bool backward, double
     const bool chain_first = tiled_allowed && bis_opts().trsv_tiled < 0 && bis_opts().trsv_chain < 0 && T->grid[0] > 0 && T->grid[3] > 1 &&
                              n >= 16384 && n <= chain_first_max;
     if (tiled_allowed && !chain_first) {
-        bool done = false;
-        const bis_status tst = tiled_sweep(&done);
-        if (tst != BIS_OK || done) return tst;
+        if (bis_status st = ensure_tiled(ctx, T, backward, side)) return st;
+        if (side.tiled) return take(kTrsvTiled, "trsv_tiled_kernel");
     }
     bis_trsv_plan *p = nullptr;
-    bis_status st = get_plan(ctx, T, backward, &p);
-    if (st != BIS_OK) return st;
-    if (!p->level_views.empty()) {
-        kernel = "spmv_rowblock_kernel (triangular epilogue, a launch per independent row block)";
-        for (int l = 0; l < p->n_levels; ++l) {
-            const int64_t r0 = p->level_row0[l];
-            st = bis_spmv_trsv_level(ctx, p->level_views[l], x, x + r0, b + r0, D + r0);
-            if (st != BIS_OK) return st;
-        }
-        return BIS_OK;
-    }
-    if (p->n_levels <= kFewLevels) {
-        kernel = "trsv_level_kernel (a launch per level)";
-        for (int l = 0; l < p->n_levels; ++l) {
-            const int64_t lo = p->level_ptr[l], hi = p->level_ptr[l + 1];
-            const int grid = (int)std::min<int64_t>((hi - lo + 255) / 256, (int64_t)ctx->n_cus * 32);
-            if (T->rp64)
-                hipLaunchKernelGGL(trsv_level_kernel<int64_t>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const int64_t *)T->row_ptr, T->col, T->val, p->perm, lo, hi, D, b, x, ctx->spmv_stop);
-            else
-                hipLaunchKernelGGL(trsv_level_kernel<int32_t>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const int32_t *)T->row_ptr, T->col, T->val, p->perm, lo, hi, D, b, x, ctx->spmv_stop);
-        }
-        BIS_HIP_CHECK(ctx, hipGetLastError());
-        return BIS_OK;
-    }
+    if (bis_status st = get_plan(ctx, T, backward, &p)) return st;
+    plan.p = p;
+    if (!p->level_views.empty()) return take(kTrsvViews, "spmv_rowblock_kernel (triangular epilogue, a launch per independent row block)");
+    if (p->n_levels <= kFewLevels) return take(kTrsvPerLevel, "trsv_level_kernel (a launch per level)");
     // many narrow levels on a matrix without a grid: the chained sweep (bis_trsv_chain.hip) where its plan applies
-    if (bis_opts().trsv_chain != 0 && bis_opts().trsv_inject_loss <= 0 && bis_opts().trsv_one_xcd <= 0) {
-        bis_mat *M = const_cast<bis_mat *>(T);
-        bis_trsv_chain *&cs = backward ? M->chain_bwd : M->chain_fwd;
-        bool &tried = backward ? M->chain_tried_bwd : M->chain_tried_fwd;
-        if (!tried) {
-            tried = true;
-            if (p->level) {
-                const bis_status cst = bis_trsv_chain_build(ctx, T, backward, p->level, p->n_levels, &cs);
-                hipFree(p->level);
-                p->level = nullptr;
-                if (cst != BIS_OK) return cst;
-            }
-        } else if (p->level) { // (a level plan rebuilt after the values changed: the chains depend on the pattern only)
-            hipFree(p->level);
-            p->level = nullptr;
+    if (bis_opts().trsv_chain != 0 && flagless_ok) {
+        bis_status cst = BIS_OK;
+        if (!side.chain_tried) {
+            side.chain_tried = true;
+            if (p->level) cst = bis_trsv_chain_build(ctx, T, backward, p->level, p->n_levels, &side.chain);
         }
-        if (cs) { kernel = "trsv_chain_kernel"; return bis_trsv_chain_solve(ctx, T, cs, x, D, b); }
+        hipFree(p->level); // tried, now or before (a level plan rebuilt after the values changed: the chains depend on the pattern only)
+        p->level = nullptr;
+        if (cst != BIS_OK) return cst;
+        if (side.chain) return take(kTrsvChained, "trsv_chain_kernel");
     }
     if (chain_first) { // (no chained plan for this matrix after all)
-        bool done = false;
-        const bis_status tst = tiled_sweep(&done);
-        if (tst == BIS_OK && done) { // the tiled sweep serves this triangle from now on: the level plan made for the chained attempt goes
-            bis_mat *M = const_cast<bis_mat *>(T);
-            bis_trsv_plan *&slot = backward ? M->plan_bwd : M->plan_fwd;
-            bis_trsv_plan_destroy(slot);
-            slot = nullptr;
+        if (bis_status st = ensure_tiled(ctx, T, backward, side)) return st;
+        if (side.tiled) { // the tiled sweep serves this triangle from now on: the level plan made for the chained attempt goes
+            bis_trsv_plan_destroy(side.level);
+            side.level = nullptr;
+            plan.p = nullptr;
+            return take(kTrsvTiled, "trsv_tiled_kernel");
         }
-        if (tst != BIS_OK || done) return tst;
     }
-    if (!p->xs) {
-        const hipError_t xe = hipMalloc(&p->xs, sizeof(double) * (size_t)(n + 1)); // + one slot nobody publishes (test hook)
-        if (xe != hipSuccess) { (void)hipGetLastError(); ctx->err = "sptrsv: out of memory for the scratch vector"; return BIS_ERR_HIP; }
-    }
-    const int fill_grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(fill_sentinel_kernel, dim3(fill_grid), dim3(256), 0, ctx->stream,
-                       (unsigned long long *)p->xs, n + 1, p->ticket);
+    // ---- the level-scheduled kernels
+    const int by_pos = bis_opts().trsv_by_pos < 0 ? 1 : bis_opts().trsv_by_pos;
+    if (bis_status st = ensure_scratch(ctx, T, p, by_pos != 0)) return st;
+    plan.dep = (by_pos && p->pcol) ? p->pcol : T->col;
+    plan.pos_flag = (by_pos && p->pcol) ? 1 : 0;
     // persistent grid: resident by construction (<= 8 workgroups of 256 per CU, 51 VGPRs)
     const int64_t n_tickets = (n + kTrsvT - 1) / kTrsvT;
     // Only ~one level is runnable at a time: keep a few of the widest levels
@@ -634,55 +702,17 @@ bis_status trsv_solve_impl(bis_ctx *ctx, const bis_mat *T, bool backward, double
     // (measured: HPCG-128 4.6 ms at 64-128 workgroups, 9.3 ms at 512, 22 ms at
     // 1024; Anderson-256 4.5 ms at 256, 13.5 ms at 1024).
     int64_t want = (4 * p->max_level_width + kTrsvT - 1) / kTrsvT + 1;
-    const int one_xcd = bis_opts().trsv_one_xcd < 0 ? 0 : bis_opts().trsv_one_xcd;
+    const int one_xcd = plan.one_xcd = bis_opts().trsv_one_xcd < 0 ? 0 : bis_opts().trsv_one_xcd;
     if (one_xcd) want = std::min<int64_t>(want, (int64_t)(ctx->n_cus / 8) * one_xcd) * 8; // per XCD x 8 XCDs
     else want = std::min<int64_t>(want, ctx->n_cus);
     if (bis_opts().trsv_grid > 0) want = bis_opts().trsv_grid;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(one_xcd ? n_tickets * 8 : n_tickets, want),
+    plan.lane_grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(one_xcd ? n_tickets * 8 : n_tickets, want),
                                                                  (int64_t)ctx->n_cus * 8));
     // dependencies loaded per round trip: the whole row when it fits (HPCG-128 U, 13 per row: 3.05 ms with 16,
     // 5.28 ms with 8; Anderson-256, 3 per row: 2.4 ms with 4 or 8)
-    const int batch = bis_opts().trsv_batch > 0 ? bis_opts().trsv_batch : (T->max_row_nnz > 8 ? 16 : T->max_row_nnz > 4 ? 8 : 4);
-    // The scratch vector lives in LEVEL order (position in perm), so the polls and the
-    // stores of neighbouring lanes fall into the same cache lines; pcol = positions
-    // of the columns, built at the first solve.
-    const int by_pos = bis_opts().trsv_by_pos < 0 ? 1 : bis_opts().trsv_by_pos;
-    if (by_pos && !p->pcol && !p->no_pos && T->nnz > 0) {
-        int32_t *inv = nullptr;
-        BIS_HIP_CHECK(ctx, hipMalloc(&inv, sizeof(int32_t) * (size_t)n));
-        hipError_t pe = hipMalloc(&p->pcol, sizeof(int32_t) * (size_t)T->nnz);
-        if (pe != hipSuccess) { hipFree(inv); p->pcol = nullptr; ctx->err = "sptrsv: out of memory for the position table"; return BIS_ERR_HIP; }
-        hipLaunchKernelGGL(invert_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           p->perm, n, inv);
-        // the view's first non-zero: row views share the parent's arrays
-        int64_t k0 = 0;
-        { int64_t a64 = 0; int32_t a32 = 0;
-          BIS_HIP_CHECK(ctx, hipMemcpyAsync(T->rp64 ? (void *)&a64 : (void *)&a32, T->row_ptr, T->rp64 ? 8 : 4, hipMemcpyDeviceToHost, ctx->stream));
-          BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-          k0 = T->rp64 ? a64 : a32; }
-        if (k0 != 0) { // a row view (absolute indices into the parent's arrays): keep the row-order scratch
-            hipFree(p->pcol); p->pcol = nullptr; p->no_pos = true;
-        } else
-        hipLaunchKernelGGL(cols_to_positions_kernel, dim3((unsigned)std::min<int64_t>((T->nnz + 255) / 256, 8192)), dim3(256), 0,
-                           ctx->stream, T->col, inv, T->nnz, p->pcol);
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(inv);
-    }
-    const int32_t *dep = (by_pos && p->pcol) ? p->pcol : T->col;
-    const int pos_flag = (by_pos && p->pcol) ? 1 : 0;
-    // Test hook (bis_set_option("trsv_inject_loss", k)): the first dependency of the k-th non-zero's row is
-    // redirected, for this one sweep, to the scratch slot nobody publishes -- the row gives up after
-    // kSpinLimit polls, publishes NaN and raises the fault word.
-    struct Restore { bis_ctx *c; int32_t *at; int32_t old; ~Restore() { if (at) { hipMemcpyAsync(at, &old, 4, hipMemcpyHostToDevice, c->stream); hipStreamSynchronize(c->stream); } } } restore{ctx, nullptr, 0};
-    if (bis_opts().trsv_inject_loss > 0 && pos_flag && (int64_t)bis_opts().trsv_inject_loss <= T->nnz) {
-        int32_t *at = p->pcol + (bis_opts().trsv_inject_loss - 1);
-        const int32_t lost = (int32_t)n;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(&restore.old, at, 4, hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(at, &lost, 4, hipMemcpyHostToDevice, ctx->stream));
-        restore.at = at;
-        bis_opts().trsv_inject_loss = -1; // one shot
-    }
+    plan.batch = bis_opts().trsv_batch > 0 ? bis_opts().trsv_batch : (T->max_row_nnz > 8 ? 16 : T->max_row_nnz > 4 ? 8 : 4);
+    // Test hook (bis_set_option("trsv_inject_loss", k)), see PcolRedirect: needs the position table
+    if (bis_opts().trsv_inject_loss > 0 && plan.pos_flag && (int64_t)bis_opts().trsv_inject_loss <= T->nnz) plan.inject_loss = bis_opts().trsv_inject_loss;
     // rows of more than 8 dependencies: one wave per row (config-5 stand-in, ~35 per row: 10.8 / 25.3 ms per
     // forward / backward sweep with a lane per row -> 6.0 / 6.0 ms; HPCG-128, 13 per row: 2.88 / 3.05 -> 2.64 / 2.66;
     // Anderson-256, 3 per row and 22 K rows per level: 2.4 ms with a lane per row, 8.6 ms with a wave per row)
@@ -692,40 +722,22 @@ bis_status trsv_solve_impl(bis_ctx *ctx, const bis_mat *T, bool backward, double
     const int wave_auto = T->max_row_nnz > 16 || (T->max_row_nnz > 8 && avg_width <= (int64_t)ctx->n_cus * 16);
     // Where the rule says "a wave per row" the other kernel is sometimes the faster one (`unstr:80,80,80` as generated, 135 levels of
     // 11 K rows, 33 entries per row: forward 1.50 ms with a wave per row, 1.21 with a lane per row; backward 1.52 against 3.55), and
-    // nothing known before the sweep tells the cases apart: the first sweep of a large triangle runs both (twice each, the second
-    // run timed; the results are the same bits) and the plan keeps the faster one.  Not inside a device schedule (a stopped
-    // schedule's launches are no-ops), not when x aliases an input (the sweep could not be repeated).
+    // nothing known before the sweep tells the cases apart: the first sweep of a large triangle runs both (trsv_trial) and the plan
+    // keeps the faster one.  Not inside a device schedule (a stopped schedule's launches are no-ops), not when x aliases an input
+    // (the sweep could not be repeated): the choice then waits for a later sweep.
     if (p->wave_choice == 0 && bis_opts().trsv_wave < 0) {
         // (levels of 1024 rows or more only: on narrow ones a lane per row is hopeless -- `unstr:80,80,80` RCM-ordered, 215 rows per level: 105 ms
         // against 13 with a wave per row -- and the trial itself would cost more than it can win)
-        const bool can_try = bis_opts().trsv_trial != 0 && wave_auto && !one_xcd && n >= 200000 && T->max_row_nnz <= 128 && avg_width >= 1024 &&
-                             x != b && x != D && !ctx->spmv_stop && bis_opts().trsv_inject_loss <= 0 && bis_opts().trsv_grid <= 0;
-        if (!can_try) {
-            if (ctx->spmv_stop || x == b || x == D) { /* decide at a later sweep */ }
-            else p->wave_choice = wave_auto ? 1 : 2;
-        } else {
-            hipEvent_t ev[2] = {nullptr, nullptr};
-            bool good = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-            bis_status tst = BIS_OK;
-            for (int v = 1; v <= 2 && good && tst == BIS_OK; ++v) {
-                p->wave_choice = v;
-                for (int rep = 0; rep < 2 && tst == BIS_OK; ++rep) {
-                    if (rep == 1) good = good && hipEventRecord(ev[0], ctx->stream) == hipSuccess;
-                    tst = trsv_solve_impl(ctx, T, backward, x, D, b, kernel);
-                }
-                good = good && hipEventRecord(ev[1], ctx->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-                       hipEventElapsedTime(&p->trial_ms[v - 1], ev[0], ev[1]) == hipSuccess;
-            }
-            if (ev[0]) hipEventDestroy(ev[0]);
-            if (ev[1]) hipEventDestroy(ev[1]);
-            (void)hipGetLastError();
-            p->wave_choice = (good && tst == BIS_OK && p->trial_ms[1] < 0.9f * p->trial_ms[0]) ? 2 : 1;
-            kernel = p->wave_choice == 1 ? "sptrsv_wave_kernel" : "sptrsv_syncfree_kernel";
-            return tst; // (x holds the solution: the last of the four sweeps)
-        }
+        const bool repeatable = x != b && x != D && !ctx->spmv_stop;
+        plan.trial = bis_opts().trsv_trial != 0 && wave_auto && !one_xcd && n >= 200000 && T->max_row_nnz <= 128 && avg_width >= 1024 && repeatable &&
+                     (bis_opts().trsv_inject_loss <= 0 || plan.inject_loss) /* (a hook that fires is spent by the time the trial starts) */ && bis_opts().trsv_grid <= 0;
+        if (!plan.trial && repeatable) p->wave_choice = wave_auto ? 1 : 2;
     }
+    // (trsv_wave >= 0 overrides the kernel without touching the kept choice; the one-XCD mode exists in the lane kernel only)
     const int wave_mode = bis_opts().trsv_wave >= 0 ? bis_opts().trsv_wave : (p->wave_choice ? (p->wave_choice == 1 ? 1 : 0) : (wave_auto ? 1 : 0));
-    if (wave_mode && !one_xcd) {
+    plan.form = (wave_mode && !one_xcd) ? kTrsvWave : kTrsvLane;
+    plan.kernel = trsv_level_kernel_name(plan.form);
+    if (plan.form == kTrsvWave) {
         // a few levels of rows in flight, one row per wave; at most 4 workgroups per CU: every wave of the
         // grid must be resident (static round robin, see the kernel)
         // Rows are dealt to the waves round robin, so EVERY wave of the grid must be resident: the grid is
@@ -752,37 +764,137 @@ bis_status trsv_solve_impl(bis_ctx *ctx, const bis_mat *T, bool backward, double
         // option "device_share" = k: k processes run sweeps on this device at the same time (ranks of a test or a rehearsal
         // sharing one GPU), each keeps to 1/k of the residency so that all their grids fit together
         const int share = std::max(1, bis_opts().device_share);
-        wg = std::max<int64_t>(1, std::min<int64_t>(wg, std::min<int64_t>((n + 3) / 4, std::max<int64_t>(1, (int64_t)ctx->n_cus * per_cu / share))));
-        if (T->rp64)
-            hipLaunchKernelGGL(sptrsv_wave_kernel<int64_t>, dim3((unsigned)wg), dim3(kTrsvT), 0, ctx->stream,
-                               (const int64_t *)T->row_ptr, dep, T->val, p->perm, n, D, b, x,
-                               (unsigned long long *)p->xs, p->ticket, pos_flag, ctx->fault_dev, ctx->spmv_stop);
-        else
-            hipLaunchKernelGGL(sptrsv_wave_kernel<int32_t>, dim3((unsigned)wg), dim3(kTrsvT), 0, ctx->stream,
-                               (const int32_t *)T->row_ptr, dep, T->val, p->perm, n, D, b, x,
-                               (unsigned long long *)p->xs, p->ticket, pos_flag, ctx->fault_dev, ctx->spmv_stop);
-        BIS_HIP_CHECK(ctx, hipGetLastError());
-        kernel = "sptrsv_wave_kernel";
-        return BIS_OK;
+        plan.wave_grid = (int)std::max<int64_t>(1, std::min<int64_t>(wg, std::min<int64_t>((n + 3) / 4, std::max<int64_t>(1, (int64_t)ctx->n_cus * per_cu / share))));
     }
-    kernel = "sptrsv_syncfree_kernel";
-#define BIS_TRSV_LAUNCH(RP, ONE, B)                                                                    \
-    hipLaunchKernelGGL((sptrsv_syncfree_kernel<RP, ONE, B>), dim3(grid), dim3(kTrsvT), 0, ctx->stream, \
-                       (const RP *)T->row_ptr, dep, T->val, p->perm, n, D, b, x,                      \
-                       (unsigned long long *)p->xs, p->ticket, pos_flag, ctx->fault_dev, ctx->spmv_stop)
-#define BIS_TRSV_B(RP, ONE)                                                                            \
-    do {                                                                                               \
-        if (batch >= 32) BIS_TRSV_LAUNCH(RP, ONE, 32);                                                 \
-        else if (batch >= 16) BIS_TRSV_LAUNCH(RP, ONE, 16);                                            \
-        else if (batch >= 8) BIS_TRSV_LAUNCH(RP, ONE, 8);                                              \
-        else BIS_TRSV_LAUNCH(RP, ONE, 4);                                                              \
-    } while (0)
-    if (T->rp64) { if (one_xcd) BIS_TRSV_B(int64_t, true); else BIS_TRSV_B(int64_t, false); }
-    else { if (one_xcd) BIS_TRSV_B(int32_t, true); else BIS_TRSV_B(int32_t, false); }
-#undef BIS_TRSV_B
-#undef BIS_TRSV_LAUNCH
+    return BIS_OK;
+}
+
+// ---- one launch function per form (the tiled and the chained sweep: bis_trsv_tiled_solve, bis_trsv_chain_solve)
+
+bis_status trsv_launch_views(bis_ctx *ctx, const bis_trsv_plan *p, double *x, const double *D, const double *b) {
+    for (int l = 0; l < p->n_levels; ++l) {
+        const int64_t r0 = p->level_row0[l];
+        if (bis_status st = bis_spmv_trsv_level(ctx, p->level_views[l], x, x + r0, b + r0, D + r0)) return st;
+    }
+    return BIS_OK;
+}
+
+bis_status trsv_launch_per_level(bis_ctx *ctx, const bis_mat *T, const bis_trsv_plan *p, double *x, const double *D, const double *b) {
+    for (int l = 0; l < p->n_levels; ++l) {
+        const int64_t lo = p->level_ptr[l], hi = p->level_ptr[l + 1];
+        const int grid = (int)std::min<int64_t>((hi - lo + 255) / 256, (int64_t)ctx->n_cus * 32);
+        if (T->rp64)
+            hipLaunchKernelGGL(trsv_level_kernel<int64_t>, dim3(grid), dim3(256), 0, ctx->stream,
+                               (const int64_t *)T->row_ptr, T->col, T->val, p->perm, lo, hi, D, b, x, ctx->spmv_stop);
+        else
+            hipLaunchKernelGGL(trsv_level_kernel<int32_t>, dim3(grid), dim3(256), 0, ctx->stream,
+                               (const int32_t *)T->row_ptr, T->col, T->val, p->perm, lo, hi, D, b, x, ctx->spmv_stop);
+    }
     BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
+}
+
+// The level-scheduled sweep with the kernel `form` names (the plan's, or the trial's candidate): sentinel fill + ONE launch.
+bis_status trsv_launch_scheduled(bis_ctx *ctx, const bis_mat *T, const TrsvPlan &plan, TrsvForm form, double *x, const double *D,
+                                 const double *b) {
+    const bis_trsv_plan *p = plan.p;
+    const int64_t n = T->n_rows;
+    const int fill_grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(fill_sentinel_kernel, dim3(fill_grid), dim3(256), 0, ctx->stream,
+                       (unsigned long long *)p->xs, n + 1, p->ticket);
+#define BIS_TRSV_ARGS(RP) (const RP *)T->row_ptr, plan.dep, T->val, p->perm, n, D, b, x, (unsigned long long *)p->xs, p->ticket, \
+                          plan.pos_flag, ctx->fault_dev, ctx->spmv_stop
+    if (form == kTrsvWave) {
+        if (T->rp64) hipLaunchKernelGGL(sptrsv_wave_kernel<int64_t>, dim3((unsigned)plan.wave_grid), dim3(kTrsvT), 0, ctx->stream, BIS_TRSV_ARGS(int64_t));
+        else hipLaunchKernelGGL(sptrsv_wave_kernel<int32_t>, dim3((unsigned)plan.wave_grid), dim3(kTrsvT), 0, ctx->stream, BIS_TRSV_ARGS(int32_t));
+    } else {
+#define BIS_TRSV_LAUNCH(RP, ONE, B) \
+    hipLaunchKernelGGL((sptrsv_syncfree_kernel<RP, ONE, B>), dim3(plan.lane_grid), dim3(kTrsvT), 0, ctx->stream, BIS_TRSV_ARGS(RP))
+#define BIS_TRSV_B(RP, ONE)                                                                            \
+    do {                                                                                               \
+        if (plan.batch >= 32) BIS_TRSV_LAUNCH(RP, ONE, 32);                                            \
+        else if (plan.batch >= 16) BIS_TRSV_LAUNCH(RP, ONE, 16);                                       \
+        else if (plan.batch >= 8) BIS_TRSV_LAUNCH(RP, ONE, 8);                                         \
+        else BIS_TRSV_LAUNCH(RP, ONE, 4);                                                              \
+    } while (0)
+        if (T->rp64) { if (plan.one_xcd) BIS_TRSV_B(int64_t, true); else BIS_TRSV_B(int64_t, false); }
+        else { if (plan.one_xcd) BIS_TRSV_B(int32_t, true); else BIS_TRSV_B(int32_t, false); }
+#undef BIS_TRSV_B
+#undef BIS_TRSV_LAUNCH
+    }
+#undef BIS_TRSV_ARGS
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+
+// The wave / lane trial of a large triangle's first sweep: each kernel twice, the second run timed; the lane kernel is kept
+// only below 0.9 x the wave kernel's time.  The results are the same bits; x holds the last run's.
+bis_status trsv_trial(bis_ctx *ctx, const bis_mat *T, TrsvPlan &plan, double *x, const double *D, const double *b) {
+    bis_trsv_plan *p = plan.p;
+    const TrsvForm cand[2] = {kTrsvWave, kTrsvLane};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool good = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    bis_status st = BIS_OK;
+    for (int v = 0; v < 2 && good && st == BIS_OK; ++v) {
+        for (int rep = 0; rep < 2 && st == BIS_OK; ++rep) {
+            if (rep == 1) good = good && hipEventRecord(ev[0], ctx->stream) == hipSuccess;
+            st = trsv_launch_scheduled(ctx, T, plan, cand[v], x, D, b);
+        }
+        good = good && hipEventRecord(ev[1], ctx->stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+               hipEventElapsedTime(&p->trial_ms[v], ev[0], ev[1]) == hipSuccess;
+    }
+    if (ev[0]) hipEventDestroy(ev[0]);
+    if (ev[1]) hipEventDestroy(ev[1]);
+    (void)hipGetLastError();
+    p->wave_choice = (good && st == BIS_OK && p->trial_ms[1] < 0.9f * p->trial_ms[0]) ? 2 : 1;
+    plan.form = cand[p->wave_choice - 1];
+    plan.kernel = trsv_level_kernel_name(plan.form);
+    return st;
+}
+
+// Test hook (bis_set_option("trsv_inject_loss", k)): the first dependency of the k-th non-zero's row is redirected, for
+// this one call, to the scratch slot nobody publishes -- the row gives up after kSpinLimit polls, publishes NaN and raises
+// the fault word.  One shot; the entry of the position table is restored when the call's launches are enqueued.
+struct PcolRedirect {
+    bis_ctx *c;
+    int32_t *at = nullptr;
+    int32_t old = 0;
+    bis_status set(int32_t *entry, int32_t lost) {
+        BIS_HIP_CHECK(c, hipMemcpyAsync(&old, entry, 4, hipMemcpyDeviceToHost, c->stream));
+        BIS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+        BIS_HIP_CHECK(c, hipMemcpyAsync(entry, &lost, 4, hipMemcpyHostToDevice, c->stream));
+        at = entry;
+        bis_opts().trsv_inject_loss = -1; // one shot
+        return BIS_OK;
+    }
+    ~PcolRedirect() { if (at) { hipMemcpyAsync(at, &old, 4, hipMemcpyHostToDevice, c->stream); hipStreamSynchronize(c->stream); } }
+};
+
+bis_status trsv_sweep_scheduled(bis_ctx *ctx, const bis_mat *T, TrsvPlan &plan, double *x, const double *D, const double *b) {
+    PcolRedirect loss{ctx};
+    if (plan.inject_loss)
+        if (bis_status st = loss.set(plan.p->pcol + (plan.inject_loss - 1), (int32_t)T->n_rows)) return st;
+    return plan.trial ? trsv_trial(ctx, T, plan, x, D, b) : trsv_launch_scheduled(ctx, T, plan, plan.form, x, D, b);
+}
+
+bis_status trsv_sweep(bis_ctx *ctx, const bis_mat *T, bool backward, double *x, const double *D, const double *b) {
+    BIS_REQUIRE(ctx, T && (T->n_rows == 0 || (x && D && b)), "sptrsv: bad arguments");
+    BIS_REQUIRE(ctx, T->n_rows == T->n_cols, "sptrsv: square matrix required");
+    if (T->n_rows == 0) return BIS_OK;
+    TrsvPlan plan;
+    bis_status st = trsv_resolve(ctx, T, backward, x, D, b, &plan);
+    if (st != BIS_OK) return st;
+    bis_trsv_side &side = bis_trsv_side_of(const_cast<bis_mat *>(T), backward);
+    switch (plan.form) {
+    case kTrsvTiled: st = bis_trsv_tiled_solve(ctx, side.tiled, x, D, b); break;
+    case kTrsvChained: st = bis_trsv_chain_solve(ctx, T, side.chain, x, D, b); break;
+    case kTrsvViews: st = trsv_launch_views(ctx, plan.p, x, D, b); break;
+    case kTrsvPerLevel: st = trsv_launch_per_level(ctx, T, plan.p, x, D, b); break;
+    case kTrsvWave:
+    case kTrsvLane: st = trsv_sweep_scheduled(ctx, T, plan, x, D, b); break;
+    }
+    if (st == BIS_OK) side.kernel = plan.kernel;
+    return st;
 }
 
 // one sweep = every launch of the call (sentinel fill + the sweep kernel, or a launch per level): HIP-event bracketed on the
@@ -799,13 +911,11 @@ bis_status trsv_solve(bis_ctx *ctx, const bis_mat *T, bool backward, double *x, 
         }
         hipEventRecord(ctx->prof_sweep_events[ctx->prof_sweep_used].first, ctx->stream);
     }
-    const char *kernel = "";
-    const bis_status st = trsv_solve_impl(ctx, T, backward, x, D, b, kernel);
+    const bis_status st = trsv_sweep(ctx, T, backward, x, D, b);
     if (prof) {
         hipEventRecord(ctx->prof_sweep_events[ctx->prof_sweep_used].second, ctx->stream);
         ++ctx->prof_sweep_used;
     }
-    if (T && st == BIS_OK && kernel[0]) const_cast<bis_mat *>(T)->sweep_kernel[backward ? 1 : 0] = kernel;
     return st;
 }
 
@@ -823,7 +933,7 @@ bis_status bis_trsv_level_sets(bis_ctx *ctx, const bis_mat *T_lower, const std::
 
 extern "C" {
 
-const char *bis_mat_sweep_kernel(const bis_mat *T, int backward) { return T ? T->sweep_kernel[backward ? 1 : 0] : ""; }
+const char *bis_mat_sweep_kernel(const bis_mat *T, int backward) { return T ? T->trsv[backward ? 1 : 0].kernel : ""; }
 
 bis_status bis_sptrsv(bis_ctx *ctx, const bis_mat *L_strict, double *x, const double *D,
                       const double *b) {
@@ -833,87 +943,6 @@ bis_status bis_sptrsv(bis_ctx *ctx, const bis_mat *L_strict, double *x, const do
 bis_status bis_bsptrsv(bis_ctx *ctx, const bis_mat *U_strict, double *x, const double *D,
                        const double *b) {
     return trsv_solve(ctx, U_strict, true, x, D, b);
-}
-
-// two_stage_gauss_seidel, kernels.hpp:312-333.
-bis_status bis_two_stage_gauss_seidel(bis_ctx *ctx, const bis_mat *strict, double *tmp,
-                                      double *work, const double *D_inv, const double *input,
-                                      double *output, int64_t n, int inner_iters) {
-    BIS_CTX_OK(ctx);
-    bis_status st = bis_elemwise_mult_vectors(ctx, work, D_inv, input, n, 1.0);   // :317
-    if (st == BIS_OK) st = bis_copy_vector(ctx, output, work, n);                  // :319
-    for (int inner = 1; st == BIS_OK && inner <= inner_iters; ++inner) {
-        st = bis_spmv(ctx, strict, work, tmp);                                     // :323
-        if (st == BIS_OK) st = bis_elemwise_mult_vectors(ctx, tmp, D_inv, tmp, n, -1.0); // :325
-        std::swap(work, tmp);                                                      // :327
-        if (st == BIS_OK) st = bis_sum_vectors(ctx, output, output, work, n, 1.0); // :331
-    }
-    return st;
-}
-
-// apply_preconditioner, kernels.hpp:336-414.
-bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_mat *L_strict,
-                                    const bis_mat *U_strict, const double *A_D,
-                                    const double *A_D_inv, const double *L_D, const double *U_D,
-                                    double *output, double *input, double *tmp, double *work,
-                                    int outer_iters, int inner_iters) {
-    BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1, "bis_apply_preconditioner: bad arguments");
-    if (pc == BIS_PC_ILU0_ITER)
-        BIS_REQUIRE(ctx, L_strict && U_strict && inner_iters >= 0 && (n == 0 || (tmp && work && tmp != work && tmp != output &&
-                         tmp != input && work != output && work != input)),
-                    "bis_apply_preconditioner: ILU0_ITER needs both factors, inner_iters >= 0, and tmp, work distinct from each other, output and input");
-    double *input_storage = nullptr;
-    bis_status st = BIS_OK;
-    if (outer_iters > 1) { // :348-352 (the one place the reference allocates in a kernel)
-        st = bis_vec_alloc(ctx, n, &input_storage);
-        if (st == BIS_OK) st = bis_copy_vector(ctx, input_storage, input, n);
-    }
-    for (int i = 0; st == BIS_OK && i < outer_iters; ++i) {
-        switch (pc) {
-        case BIS_PC_JACOBI:
-            st = bis_elemwise_div_vectors(ctx, output, input, A_D, n, 1.0);        // :357
-            break;
-        case BIS_PC_GAUSS_SEIDEL:
-            st = bis_sptrsv(ctx, L_strict, output, A_D, input);                    // :359
-            break;
-        case BIS_PC_BACKWARDS_GAUSS_SEIDEL:
-            st = bis_bsptrsv(ctx, U_strict, output, A_D, input);                   // :361
-            break;
-        case BIS_PC_SYMMETRIC_GAUSS_SEIDEL:
-            st = bis_sptrsv(ctx, L_strict, tmp, A_D, input);                       // :365
-            if (st == BIS_OK) st = bis_elemwise_mult_vectors(ctx, tmp, tmp, A_D, n, 1.0); // :369
-            if (st == BIS_OK) st = bis_bsptrsv(ctx, U_strict, output, A_D, tmp);   // :373
-            break;
-        case BIS_PC_TWO_STAGE_GS:
-            st = bis_two_stage_gauss_seidel(ctx, L_strict, tmp, work, A_D_inv, input, output, n,
-                                            inner_iters);                          // :376
-            break;
-        case BIS_PC_SYMMETRIC_TWO_STAGE_GS:
-            st = bis_two_stage_gauss_seidel(ctx, L_strict, tmp, work, A_D_inv, input, output, n,
-                                            inner_iters);                          // :379
-            if (st == BIS_OK) st = bis_elemwise_mult_vectors(ctx, output, output, A_D, n, 1.0); // :382
-            if (st == BIS_OK)
-                st = bis_two_stage_gauss_seidel(ctx, U_strict, tmp, work, A_D_inv, output, output,
-                                                n, inner_iters);                   // :384
-            break;
-        case BIS_PC_ILU0:
-            st = bis_sptrsv(ctx, L_strict, tmp, L_D, input);                       // :390
-            if (st == BIS_OK) st = bis_bsptrsv(ctx, U_strict, output, U_D, tmp);   // :394
-            break;
-        case BIS_PC_ILU0_ITER: // (not in the reference) both solves as bis_itrsv; A_D_inv carries 1 / U_D
-            st = bis_itrsv(ctx, L_strict, L_D, input, tmp, work, inner_iters);
-            if (st == BIS_OK) st = bis_itrsv(ctx, U_strict, A_D_inv, tmp, output, work, inner_iters);
-            break;
-        default:
-            st = bis_copy_vector(ctx, output, input, n);                           // :398
-        }
-        if (st == BIS_OK && outer_iters > 1 && i != outer_iters - 1)
-            st = bis_copy_vector(ctx, input, output, n);                           // :401-403
-    }
-    if (st == BIS_OK && outer_iters > 1) st = bis_copy_vector(ctx, input, input_storage, n); // :406-408
-    if (input_storage) bis_vec_free(ctx, input_storage);
-    return st;
 }
 
 } // extern "C"
