@@ -40,6 +40,7 @@ def load_library():
         _lib.bis_mat_spmv_kernel.restype = C.c_char_p
         _lib.bis_mat_ilu0_kernel.restype = C.c_char_p
         _lib.bis_itrsv_kernel.restype = C.c_char_p
+        _lib.bis_mat_spmm_kernel.restype = C.c_char_p
     return _lib
 
 
@@ -244,6 +245,18 @@ class Context:
     def spmv(self, A, x, y):
         self.check(self.lib.bis_spmv(self.h, A.h, C.c_void_p(x.ptr), C.c_void_p(y.ptr)))
 
+    def spmm(self, A, X, Y, k):
+        """Y = A X for k interleaved vectors (X[c*k + j], Y[r*k + j]; bis_spmm)."""
+        self.check(self.lib.bis_spmm(self.h, A.h, C.c_void_p(X.ptr), C.c_void_p(Y.ptr), C.c_int(int(k))))
+
+    def mvec_set_col(self, X, n, k, j, v):
+        """Column j of the interleaved n x k block X = the plain vector v (bis_mvec_set_col)."""
+        self.check(self.lib.bis_mvec_set_col(self.h, C.c_void_p(X.ptr), _i64(n), C.c_int(int(k)), C.c_int(int(j)), C.c_void_p(v.ptr)))
+
+    def mvec_get_col(self, v, X, n, k, j):
+        """The plain vector v = column j of the interleaved n x k block X (bis_mvec_get_col)."""
+        self.check(self.lib.bis_mvec_get_col(self.h, C.c_void_p(v.ptr), C.c_void_p(X.ptr), _i64(n), C.c_int(int(k)), C.c_int(int(j))))
+
     def sptrsv(self, Ls, x, D, b):
         self.check(self.lib.bis_sptrsv(self.h, Ls.h, C.c_void_p(x.ptr), C.c_void_p(D.ptr),
                                        C.c_void_p(b.ptr)))
@@ -324,6 +337,9 @@ class Context:
     # ---- fused CG ------------------------------------------------------------
     def cg(self, A, b, x, A_D=None):
         return CG(self, A, b, x, A_D)
+
+    def mcg(self, A, B, X, k, A_D=None):
+        return MCG(self, A, B, X, k, A_D)
 
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
@@ -434,6 +450,17 @@ class Mat:
         """Name of the kernel (and template instance) the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)."""
         return self.ctx.lib.bis_mat_spmv_kernel(self.h, C.c_int(int(fused))).decode()
 
+    def spmm_kernel(self):
+        """Name of the path and template instance the last bis_spmm on this matrix launched (bis_mat_spmm_kernel)."""
+        return self.ctx.lib.bis_mat_spmm_kernel(self.h).decode()
+
+    def spmm_streamed_bytes(self, k):
+        """12 nnz + rp_width (n_rows + 1) + 8 k (n_cols + n_rows) (bis_mat_spmm_streamed_bytes)."""
+        b = C.c_int64()
+        if self.ctx.lib.bis_mat_spmm_streamed_bytes(self.h, C.c_int(int(k)), C.byref(b)) != 0:
+            raise BisError("bis_mat_spmm_streamed_bytes: bad arguments")
+        return b.value
+
     def ilu0_kernel(self):
         """Name of the elimination kernel that factorised this ILU(0) L factor (bis_mat_ilu0_kernel); "" for other matrices."""
         return self.ctx.lib.bis_mat_ilu0_kernel(self.h).decode()
@@ -498,6 +525,37 @@ class CG:
     def free(self):
         if self.h:
             self.ctx.lib.bis_cg_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class MCG:
+    """k CG solves in lock-step on one matrix stream (bis_mcg_*): B, X are n x k interleaved device blocks."""
+
+    def __init__(self, ctx, A, B, X, k, A_D=None):
+        self.ctx, self.k = ctx, int(k)
+        self.h = C.c_void_p()
+        self._keep = (A, B, X, A_D)
+        ctx.check(ctx.lib.bis_mcg_create(ctx.h, A.h, C.c_void_p(A_D.ptr) if A_D else C.c_void_p(),
+                                         C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k), C.byref(self.h)))
+
+    def init(self, tol):
+        r0 = np.zeros(self.k)
+        self.ctx.check(self.ctx.lib.bis_mcg_init(self.ctx.h, self.h, C.c_double(tol), r0.ctypes))
+        return r0
+
+    def iterate(self, n):
+        self.ctx.check(self.ctx.lib.bis_mcg_iterate(self.ctx.h, self.h, C.c_int(int(n))))
+
+    def status(self, j, hist_cap=4096):
+        iters, conv = C.c_int(), C.c_int()
+        hist = np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_mcg_status(self.ctx.h, self.h, C.c_int(int(j)), C.byref(iters), C.byref(conv),
+                                                   hist.ctypes, C.c_int(hist_cap)))
+        return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_mcg_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 

@@ -63,45 +63,7 @@ enum { S_RZ = 0, S_PAP, S_RZ_NEW, S_RR, S_ALPHA, S_BETA, S_STOP, S_COUNT = 8 }; 
 constexpr int kT = 256;
 constexpr int kMaxIters = 1 << 20;
 
-// ---- last-arriver reductions ---------------------------------------------------------
-// A streaming pass ends with a global reduction of per-workgroup partial sums.  Instead of a
-// second launch, every workgroup publishes its partials (write-through `sc1` stores, drained with
-// vmcnt(0) before the arrival is counted -- the "drained sc1 payload, then the flag" hand-off of
-// MI355X_MICROARCH.md, no release fence that would write back the pass' own dirty lines) and
-// takes a ticket; the workgroup that takes the LAST ticket re-reads all partials with L2-bypassing
-// loads and sums them in index order, so the result does not depend on which workgroup finishes
-// last: bit-reproducible like the two-launch form.
-__device__ __forceinline__ void publish(double *slot, double v) {
-    __hip_atomic_store(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double fetch(const double *slot) {
-    return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// thread 0 only; returns true in the workgroup that arrives last (and re-arms the counter)
-__device__ __forceinline__ bool arrive_last(unsigned *counter, unsigned n_groups) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the published partials have left this CU
-    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t != n_groups - 1) return false;
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // next use: after a kernel boundary
-    return true;
-}
-
-// The same with a counter per 16 workgroups under one top counter.  Tickets on ONE address serialise at ~11.4 ns each (measured:
-// the sweeps' ticket counter): 2048 workgroups of pass B cost 23 us in tickets alone -- nothing next to 70 us of streaming
-// on 16.8 M rows, but most of the pass on one rank's 1/8 share of a strong-scaled problem (34 us measured for 2 M rows against
-// 10 us of bandwidth time: profiles/r04_b_dist_gap_slab32.txt).  Two levels: 16 + n/16 tickets on the critical path.
-constexpr unsigned kArriveGroup = 16;
-constexpr unsigned kArriveSubs = 2048 / kArriveGroup; // kMaxReduceBlocks workgroups at most
-__device__ __forceinline__ bool arrive_last2(unsigned *top, unsigned *sub, unsigned block, unsigned n_blocks) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the published partials have left this CU
-    const unsigned g = block / kArriveGroup;
-    const unsigned n_in = min(kArriveGroup, n_blocks - g * kArriveGroup), n_groups = (n_blocks + kArriveGroup - 1) / kArriveGroup;
-    if (__hip_atomic_fetch_add(&sub[g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != n_in - 1) return false;
-    __hip_atomic_store(&sub[g], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != n_groups - 1) return false;
-    __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // next use: after a kernel boundary
-    return true;
-}
+// (the last-arriver reductions -- publish, fetch, arrive_last, arrive_last2 -- live in bis_internal.hpp: bis_mcg.hip shares them)
 
 // the scalar bookkeeping of one iteration (thread 0 of one workgroup): beta, the recorded
 // residual norm, the iteration count and the stopping test of solver.hpp:177-192

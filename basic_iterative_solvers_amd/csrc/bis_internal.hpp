@@ -215,6 +215,7 @@ struct bis_mat {
     const char *spmv_kernel[2] = {"", ""};  // the kernel the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)
     const char *ilu0_kernel = "";           // the elimination kernel that made this ILU(0) L factor (bis_mat_ilu0_kernel)
     const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
+    const char *spmm_kernel = "";           // the path and template instance the last bis_spmm on this matrix launched (bis_mat_spmm_kernel)
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \
@@ -270,6 +271,46 @@ __device__ __forceinline__ double block_sum(double v, double *lds /*[T/64]*/) {
     return r;
 }
 
+// ---- last-arriver reductions ---------------------------------------------------------
+// A streaming pass ends with a global reduction of per-workgroup partial sums.  Instead of a
+// second launch, every workgroup publishes its partials (write-through `sc1` stores, drained with
+// vmcnt(0) before the arrival is counted -- the "drained sc1 payload, then the flag" hand-off of
+// MI355X_MICROARCH.md, no release fence that would write back the pass' own dirty lines) and
+// takes a ticket; the workgroup that takes the LAST ticket re-reads all partials with L2-bypassing
+// loads and sums them in index order, so the result does not depend on which workgroup finishes
+// last: bit-reproducible like the two-launch form.
+__device__ __forceinline__ void publish(double *slot, double v) {
+    __hip_atomic_store(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double fetch(const double *slot) {
+    return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// thread 0 only; returns true in the workgroup that arrives last (and re-arms the counter)
+__device__ __forceinline__ bool arrive_last(unsigned *counter, unsigned n_groups) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the published partials have left this CU
+    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != n_groups - 1) return false;
+    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // next use: after a kernel boundary
+    return true;
+}
+
+// The same with a counter per 16 workgroups under one top counter.  Tickets on ONE address serialise at ~11.4 ns each (measured:
+// the sweeps' ticket counter): 2048 workgroups of pass B cost 23 us in tickets alone -- nothing next to 70 us of streaming
+// on 16.8 M rows, but most of the pass on one rank's 1/8 share of a strong-scaled problem (34 us measured for 2 M rows against
+// 10 us of bandwidth time: profiles/r04_b_dist_gap_slab32.txt).  Two levels: 16 + n/16 tickets on the critical path.
+constexpr unsigned kArriveGroup = 16;
+constexpr unsigned kArriveSubs = 2048 / kArriveGroup; // kMaxReduceBlocks workgroups at most
+__device__ __forceinline__ bool arrive_last2(unsigned *top, unsigned *sub, unsigned block, unsigned n_blocks) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the published partials have left this CU
+    const unsigned g = block / kArriveGroup;
+    const unsigned n_in = min(kArriveGroup, n_blocks - g * kArriveGroup), n_groups = (n_blocks + kArriveGroup - 1) / kArriveGroup;
+    if (__hip_atomic_fetch_add(&sub[g], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != n_in - 1) return false;
+    __hip_atomic_store(&sub[g], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != n_groups - 1) return false;
+    __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // next use: after a kernel boundary
+    return true;
+}
+
 // XCD-aware remap (cdna_hip_programming.md T1 / MI355X_MICROARCH.md "Workgroup
 // dispatch"): hardware deals workgroups round-robin over the 8 XCDs, so
 // blockIdx b lands on XCD b%8.  Map it to a logical block id such that each
@@ -316,6 +357,9 @@ bis_status bis_ensure_partials(bis_ctx *ctx, size_t n);
 bis_status bis_spmv_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
                            double *y, const double *w, int *n_partials,
                            size_t partials_off = 0);
+// Y = A X for n_rhs interleaved vectors (bis_spmm.hip); a launch made while ctx->spmv_stop is set returns at once when
+// spmv_stop[1] is, like bis_spmv_launch (n_rhs == 1 IS bis_spmv_launch)
+bis_status bis_spmm_launch(bis_ctx *ctx, const bis_mat *A, const double *X, double *Y, int n_rhs);
 // upper bound on the partials one fused bis_spmv_launch of A writes, whichever form A gets (nothing is built)
 size_t bis_spmv_partials_bound(const bis_mat *A);
 bis_status bis_spmv_trsv_level(bis_ctx *ctx, const bis_mat *T, const double *x, double *y,

@@ -336,6 +336,31 @@ BIS_API const char *bis_mat_ilu0_kernel(const bis_mat *L_strict);
 /* spmv / native_spmv, kernels.hpp:22-52: y = A x. */
 BIS_API bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x,
                             double *y);
+/* ---- several right-hand sides (no reference counterpart) ---------------------
+ * Y = A X for n_rhs vectors stored interleaved (row-major n x n_rhs):
+ * X[c*n_rhs + j], Y[r*n_rhs + j]; X has n_cols*n_rhs entries, Y n_rows*n_rhs.
+ * 1 <= n_rhs <= 8.  The matrix is streamed once for all vectors.
+ * Arithmetic: for every row r and column j, acc = 0.0, then for the row's
+ * entries e in CRS storage order acc += val[e] * X[col[e]*n_rhs + j], the
+ * product and the addition rounded separately (no fma), rows of any length in
+ * the same left-to-right order.  Column j of the result therefore equals
+ * bis_spmv on column j bit for bit on every matrix whose bis_spmv does not run
+ * "spmv_wave_per_row_kernel" (that kernel alone uses fma and a lane tree).
+ * n_rhs == 1 forwards to bis_spmv.  n_rhs < 1, n_rhs > 8, null pointers or
+ * X == Y: BIS_ERR_INVALID; n_rows == 0: BIS_OK.  Stream-ordered, non-blocking,
+ * allocates nothing (it works on the row-block tables bis_mat_create built). */
+BIS_API bis_status bis_spmm(bis_ctx *ctx, const bis_mat *A, const double *X, double *Y, int n_rhs);
+/* what the last bis_spmm on A launched, with its template instance:
+ * "spmm_rowblock_kernel K=4 V=2 RP=32" (V: doubles per gather load),
+ * "spmm_lane_serial_kernel K=3 RP=32" (a row too long for the LDS tile),
+ * "bis_spmv K=1" (static string; "" before the first call). */
+BIS_API const char *bis_mat_spmm_kernel(const bis_mat *A);
+/* 12 nnz + rp_width (n_rows + 1) + 8 n_rhs (n_cols + n_rows): the bytes one bis_spmm moves at least */
+BIS_API bis_status bis_mat_spmm_streamed_bytes(const bis_mat *A, int n_rhs, int64_t *bytes);
+/* column j of an interleaved block <-> a plain vector of n entries (strided copies, stream-ordered) */
+BIS_API bis_status bis_mvec_set_col(bis_ctx *ctx, double *X, int64_t n, int n_rhs, int j, const double *v);
+BIS_API bis_status bis_mvec_get_col(bis_ctx *ctx, double *v, const double *X, int64_t n, int n_rhs, int j);
+
 /* sptrsv / native_sptrsv, kernels.hpp:54-86: x = (D + L_strict)^-1 b,
  * natural row order arithmetic; x may alias b. */
 BIS_API bis_status bis_sptrsv(bis_ctx *ctx, const bis_mat *L_strict, double *x,
@@ -568,6 +593,31 @@ BIS_API bis_status bis_cg_iterate(bis_ctx *ctx, bis_cg *cg, int n_iters);
 BIS_API bis_status bis_cg_status(bis_ctx *ctx, bis_cg *cg, int *iters,
                                  int *converged, double *hist_host,
                                  int hist_cap);
+
+/* ---- k CG solves in lock-step on one matrix stream (no reference counterpart) --
+ * Per column j exactly the recurrences, the recorded norm, the history and the
+ * stop test (threshold tol * ||r0_j||) of bis_cg_*; one iteration is bis_spmm on
+ * P, the k sums (AP_j, P_j), pass B on R / Z with 2 k sums, pass C on X / P.
+ * Scalars, histories and flags live on the device per column; every reduction
+ * is summed in index order by the last arriver (deterministic; not bis_cg's
+ * tree: parity with bis_cg holds at the history gate, not bit for bit).  The
+ * columns never mix: no bit of a column depends on another column's data.  A
+ * column that has stopped (converged or diverged) is frozen as bis_cg freezes:
+ * pass C of the stopping iteration still updates its x, after that nothing of
+ * it changes.  When every column has stopped, every later launch is a no-op.
+ * A square; A_D NULL (no preconditioner) or the diagonal (Jacobi), n entries,
+ * shared by all columns; B, X: n x n_rhs interleaved (bis_spmm's layout); X
+ * holds the n_rhs start vectors on entry and is updated in place. */
+typedef struct bis_mcg bis_mcg;
+BIS_API bis_status bis_mcg_create(bis_ctx *ctx, const bis_mat *A, const double *A_D, const double *B, double *X,
+                                  int n_rhs, bis_mcg **out);
+/* r0 = b - A x0, z0, p0 per column; r0_norms_host (n_rhs entries, may be NULL) receives ||r0_j||_2 (blocking) */
+BIS_API bis_status bis_mcg_init(bis_ctx *ctx, bis_mcg *m, double tol, double *r0_norms_host);
+BIS_API bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters); /* non-blocking */
+/* blocking: column j's iterations, converged flag and residual history [0..iters] */
+BIS_API bis_status bis_mcg_status(bis_ctx *ctx, bis_mcg *m, int j, int *iters, int *converged, double *hist_host,
+                                  int hist_cap);
+BIS_API bis_status bis_mcg_destroy(bis_ctx *ctx, bis_mcg *m);
 
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
