@@ -41,6 +41,7 @@ def load_library():
         _lib.bis_mat_ilu0_kernel.restype = C.c_char_p
         _lib.bis_itrsv_kernel.restype = C.c_char_p
         _lib.bis_mat_spmm_kernel.restype = C.c_char_p
+        _lib.bis_mat_sweepm_kernel.restype = C.c_char_p
     return _lib
 
 
@@ -265,6 +266,27 @@ class Context:
         self.check(self.lib.bis_bsptrsv(self.h, Us.h, C.c_void_p(x.ptr), C.c_void_p(D.ptr),
                                         C.c_void_p(b.ptr)))
 
+    def sptrsm(self, Ls, X, D, B, k):
+        """X_j = (D + Ls)^-1 B_j for k interleaved vectors (bis_sptrsm); X may alias B."""
+        self.check(self.lib.bis_sptrsm(self.h, Ls.h, C.c_void_p(X.ptr), C.c_void_p(D.ptr), C.c_void_p(B.ptr), C.c_int(int(k))))
+
+    def bsptrsm(self, Us, X, D, B, k):
+        """X_j = (D + Us)^-1 B_j for k interleaved vectors (bis_bsptrsm); X may alias B."""
+        self.check(self.lib.bis_bsptrsm(self.h, Us.h, C.c_void_p(X.ptr), C.c_void_p(D.ptr), C.c_void_p(B.ptr), C.c_int(int(k))))
+
+    def mitrsv(self, T, D_inv, B, X, work, n_sweeps, k):
+        """bis_itrsv on every column of the interleaved n x k block B (bis_mitrsv); work: n x k entries of scratch."""
+        self.check(self.lib.bis_mitrsv(self.h, T.h, C.c_void_p(D_inv.ptr), C.c_void_p(B.ptr), C.c_void_p(X.ptr),
+                                       C.c_void_p(work.ptr) if work is not None else C.c_void_p(), C.c_int(int(n_sweeps)), C.c_int(int(k))))
+
+    def mvec_div_diag(self, R, A, D, n, k):
+        """R[i,j] = A[i,j] / (1.0 * D[i]) on interleaved n x k blocks (bis_mvec_div_diag)."""
+        self.check(self.lib.bis_mvec_div_diag(self.h, C.c_void_p(R.ptr), C.c_void_p(A.ptr), C.c_void_p(D.ptr), _i64(n), C.c_int(int(k))))
+
+    def mvec_mul_diag(self, R, A, D, n, k):
+        """R[i,j] = A[i,j] * 1.0 * D[i] on interleaved n x k blocks (bis_mvec_mul_diag)."""
+        self.check(self.lib.bis_mvec_mul_diag(self.h, C.c_void_p(R.ptr), C.c_void_p(A.ptr), C.c_void_p(D.ptr), _i64(n), C.c_int(int(k))))
+
     def itrsv(self, T, D_inv, b, x, work, n_sweeps):
         """x ~ (D + T)^-1 b by n_sweeps Jacobi-Richardson steps on the strict triangle T (bis_itrsv); work: n entries of scratch."""
         self.check(self.lib.bis_itrsv(self.h, T.h, C.c_void_p(D_inv.ptr), C.c_void_p(b.ptr), C.c_void_p(x.ptr),
@@ -330,6 +352,16 @@ class Context:
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
         self.check(self.lib.bis_apply_preconditioner(
             self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc), _i64(n),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), p(out), p(inp), p(tmp), p(work),
+            C.c_int(outer), C.c_int(inner)))
+
+    def mapply_preconditioner(self, pc, n, k, Ls, Us, A_D, A_D_inv, L_D, U_D, out, inp, tmp, work, outer=1, inner=0):
+        """bis_apply_preconditioner on interleaved n x k blocks (bis_mapply_preconditioner)."""
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        self.check(self.lib.bis_mapply_preconditioner(
+            self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc), _i64(n), C.c_int(int(k)),
             Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
             p(A_D), p(A_D_inv), p(L_D), p(U_D), p(out), p(inp), p(tmp), p(work),
             C.c_int(outer), C.c_int(inner)))
@@ -446,6 +478,10 @@ class Mat:
         """Name of the kernel the last forward / backward sweep on this triangle ran (bis_mat_sweep_kernel)."""
         return self.ctx.lib.bis_mat_sweep_kernel(self.h, C.c_int(int(backward))).decode()
 
+    def sweepm_kernel(self, backward=False):
+        """What the last multi-vector forward / backward sweep on this triangle launched, with its instance (bis_mat_sweepm_kernel)."""
+        return self.ctx.lib.bis_mat_sweepm_kernel(self.h, C.c_int(int(backward))).decode()
+
     def spmv_kernel(self, fused=False):
         """Name of the kernel (and template instance) the last plain / fused-dot SpMV of this matrix launched (bis_mat_spmv_kernel)."""
         return self.ctx.lib.bis_mat_spmv_kernel(self.h, C.c_int(int(fused))).decode()
@@ -537,6 +573,15 @@ class MCG:
         self._keep = (A, B, X, A_D)
         ctx.check(ctx.lib.bis_mcg_create(ctx.h, A.h, C.c_void_p(A_D.ptr) if A_D else C.c_void_p(),
                                          C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k), C.byref(self.h)))
+
+    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
+        self.ctx.check(self.ctx.lib.bis_mcg_set_preconditioner(
+            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
 
     def init(self, tol):
         r0 = np.zeros(self.k)

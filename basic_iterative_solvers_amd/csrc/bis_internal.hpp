@@ -15,6 +15,7 @@
 struct bis_trsv_plan;
 struct bis_trsv_tiled;
 struct bis_trsv_chain;
+struct bis_trsm_plan;
 // What the triangular sweeps of one direction have built on a matrix, all lazily (trsv_resolve, bis_sptrsv.hip).  A value
 // change (bis_mat_values_changed) drops the tiled plan with its `tried` flag (it holds a copy of the values) and the level
 // plan (its row views carry dictionaries); the chained plan and its flag stay (chains depend on the pattern only).
@@ -23,8 +24,10 @@ struct bis_trsv_side {
     bis_trsv_plan *level = nullptr;  // level analysis, row views, the level-scheduled kernels' scratch
     bis_trsv_tiled *tiled = nullptr; // bis_trsv_tiled.hip, tried first: where it exists no level analysis is made
     bis_trsv_chain *chain = nullptr; // bis_trsv_chain.hip, for matrices without a grid: built from the level analysis
+    bis_trsm_plan *multi = nullptr;  // bis_sptrsm.hip: the multi-vector sweeps' own level plan (structure only), whatever form the single-vector sweep takes
     bool tiled_tried = false, chain_tried = false; // the build ran (whether or not a plan came of it)
     const char *kernel = "";         // the kernel the last sweep of this direction ran (bis_mat_sweep_kernel)
+    const char *kernel_m = "";       // ... and the last multi-vector sweep, with its instance (bis_mat_sweepm_kernel)
 };
 
 struct bis_named_kernel {
@@ -125,6 +128,7 @@ struct bis_options {
     int spmv_sellwin_masks = -1; // 0: never the per-row pair masks (fmt 4: 4 bytes per ROW where the matrix has at most 32 (column - row, value) pairs)
     int device_share = -1;  // k > 1: this device is shared by k processes that all run persistent grids (several ranks on one GPU in a test
                             // or rehearsal): kernels that need their whole grid resident keep to 1/k of the device
+    int trsm_form = -1;     // multi-vector sweeps (bis_sptrsm.hip): -1 / 0 by level count, 1 = a launch per level at any level count, 2 = the persistent wave-per-row kernel at any level count
     int trsv_inject_oom = -1;  // test hook: 1 makes the tiled sweep's device plan run out of memory
     int trsv_inject_loss = -1; // test hook: k > 0 makes row k-1 of the next natural-order sweep wait for a result nobody publishes
 };
@@ -414,6 +418,7 @@ void bis_mat_free_meta(bis_mat *A);
 // after the values of A changed in place: drops every structure derived from them (dictionaries, code streams, sweep plans)
 void bis_mat_values_changed(bis_mat *A);
 void bis_trsv_plan_destroy(bis_trsv_plan *p);
+void bis_trsm_plan_destroy(bis_trsm_plan *p); // bis_sptrsm.hip
 inline bis_trsv_side &bis_trsv_side_of(bis_mat *A, bool backward) { return A->trsv[backward ? 1 : 0]; }
 // drops the tiled plans, their `tried` flags and the level plans of both directions; with chains = true the chained plans
 // and their flags as well (see bis_trsv_side)

@@ -14,6 +14,12 @@
 // still updates its x, then no lane touches it again; when every column has stopped, every later launch returns at once,
 // the SpMM included.  The reduction tree is not bis_cg's (other workgroup ranges): parity with bis_cg is at the history
 // gate, not bit for bit.
+//
+// With a general preconditioner (bis_mcg_set_preconditioner) the schedule is bis_cg.hip's general-preconditioner branch per
+// column: pass B updates R and the k sums (r,r) only (mcg_update_pc_kernel), Z = M^-1 R through bis_mapply_preconditioner
+// (multi-vector sweeps, bis_sptrsm.hip), then the k sums (r_j, z_j) and the per-column bookkeeping (mcg_rz_kernel), then
+// pass C.  The sweeps and the elementwise kernels of the apply may still compute a frozen column's z: nothing of that
+// column is read afterwards.  Without the call, the None / Jacobi schedule above is launched exactly as before.
 #include "bis_internal.hpp"
 
 #include <algorithm>
@@ -34,12 +40,19 @@ struct bis_mcg {
     double *hist = nullptr; // [k][hist_cap]
     int hist_cap = 0;
     int enqueued = 0;
-    unsigned *counters = nullptr; // two last-arriver counter sets (pass A', pass B)
+    unsigned *counters = nullptr; // three last-arriver counter sets (pass A', pass B, the (r,z) pass of a general preconditioner)
+    bool initialised = false;     // bis_mcg_init has run
+    // general preconditioner (bis_mcg_set_preconditioner): Z = M^-1 R through bis_mapply_preconditioner
+    int pc = -1;
+    const bis_mat *pcL = nullptr, *pcU = nullptr;
+    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
+    double *pc_tmp = nullptr, *pc_work = nullptr; // n x k blocks of the apply's scratch, where the type needs them
+    int pc_inner = 0;
 };
 
 namespace {
 
-enum { M_RZ = 0, M_PAP, M_ALPHA, M_BETA, M_RR, M_STOP, M_COUNT = 8 };
+enum { M_RZ = 0, M_PAP, M_ALPHA, M_BETA, M_RR, M_STOP, M_RR_NEW /* general preconditioner: (r,r) between pass B and the bookkeeping */, M_COUNT = 8 };
 constexpr int kT = 256;
 constexpr int kMaxK = 8;
 constexpr int kMaxIters = 1 << 20;
@@ -192,6 +205,97 @@ __global__ __launch_bounds__(kT) void mcg_update_kernel(int64_t n, int k, double
     }
 }
 
+// General preconditioner, pass B: r = fma(-alpha_j, t, r) and (r,r)_j only (INIT: r = b - A x0); z and (r,z) follow after
+// the apply.  The last workgroup parks alpha_j and (r,r)_j for mcg_rz_kernel and pass C.
+template <bool INIT>
+__global__ __launch_bounds__(kT) void mcg_update_pc_kernel(int64_t n, int k, double *sc, const int *flags, const double *__restrict__ T,
+                                                           const double *__restrict__ B, double *__restrict__ R, double *partials,
+                                                           size_t stride, unsigned *counter) {
+    __shared__ double lds[kT];
+    if (!INIT && flags[1]) return;
+    const int act = (kT / k) * k, t = threadIdx.x, j = t % k;
+    unsigned frozen = 0;
+    if (!INIT)
+        for (int c = 0; c < k; ++c) frozen |= flags[4 + 4 * c + 1] ? 1u << c : 0u;
+    const bool live = t < act && !(frozen >> j & 1u);
+    double acc[1] = {0.0};
+    if (live) {
+        const double alpha = INIT ? 0.0 : sc[j * M_COUNT + M_RZ] / sc[j * M_COUNT + M_PAP]; // cg.hpp:19-23
+        const int64_t total = n * k, gs = (int64_t)gridDim.x * act;
+        for (int64_t e = (int64_t)blockIdx.x * act + t; e < total; e += gs) {
+            const double tv = __builtin_nontemporal_load(T + e);
+            double rv;
+            if (INIT) rv = B[e] - tv;                 // compute_residual, kernels.hpp:155-162
+            else rv = fma(-alpha, tv, R[e]);          // cg.hpp:31
+            R[e] = rv;
+            acc[0] = fma(rv, rv, acc[0]);
+        }
+    }
+    if (!fold_and_arrive<1>(acc, k, act, lds, partials, stride, counter)) return;
+    // every other workgroup has read its columns' scalars and flags before it arrived: they may change now
+    double out[kMaxK];
+    sum_partials<1>(k, partials, stride, lds, out);
+    if (t != 0) return;
+    for (int c = 0; c < k; ++c) {
+        if (frozen >> c & 1u) continue;
+        double *scc = sc + c * M_COUNT;
+        if (!INIT) scc[M_ALPHA] = scc[M_RZ] / scc[M_PAP]; // pass C applies it to x
+        scc[M_RR_NEW] = out[c];
+    }
+}
+
+// General preconditioner, after Z = M^-1 R: the k sums (r_j, z_j), then the per-column bookkeeping of pass B's last
+// workgroup (INIT: p = z and the start of the solve instead).
+template <bool INIT>
+__global__ __launch_bounds__(kT) void mcg_rz_kernel(int64_t n, int k, double *sc, int *flags, const double *__restrict__ R,
+                                                    const double *__restrict__ Z, double *__restrict__ P, double *partials,
+                                                    size_t stride, unsigned *counter, double *hist, int hist_cap, double tol) {
+    __shared__ double lds[kT];
+    if (!INIT && flags[1]) return;
+    const int act = (kT / k) * k, t = threadIdx.x, j = t % k;
+    unsigned frozen = 0;
+    if (!INIT)
+        for (int c = 0; c < k; ++c) frozen |= flags[4 + 4 * c + 1] ? 1u << c : 0u;
+    const bool live = t < act && !(frozen >> j & 1u);
+    double acc[1] = {0.0};
+    if (live) {
+        const int64_t total = n * k, gs = (int64_t)gridDim.x * act;
+        for (int64_t e = (int64_t)blockIdx.x * act + t; e < total; e += gs) {
+            const double zv = Z[e];
+            if (INIT) P[e] = zv;
+            acc[0] = fma(R[e], zv, acc[0]);
+        }
+    }
+    if (!fold_and_arrive<1>(acc, k, act, lds, partials, stride, counter)) return;
+    double out[kMaxK];
+    sum_partials<1>(k, partials, stride, lds, out);
+    if (t != 0) return;
+    bool all = true;
+    for (int c = 0; c < k; ++c) {
+        double *scc = sc + c * M_COUNT;
+        int *fc = flags + 4 + 4 * c;
+        if (INIT) {
+            const double norm0 = sqrt(scc[M_RR_NEW]);
+            scc[M_RZ] = out[c];
+            scc[M_RR] = scc[M_RR_NEW];
+            scc[M_STOP] = tol * norm0;             // init_stopping_criteria, solver.hpp:173-175
+            scc[M_PAP] = scc[M_ALPHA] = scc[M_BETA] = 0.0;
+            hist[(size_t)c * hist_cap] = norm0;
+            fc[0] = fc[1] = fc[2] = fc[3] = 0;
+        } else if (!(frozen >> c & 1u)) {
+            mcg_book(out[c], scc[M_RR_NEW], scc, fc, hist + (size_t)c * hist_cap, hist_cap);
+        }
+        all = all && fc[1];
+    }
+    if (INIT) { flags[0] = flags[1] = flags[2] = flags[3] = 0; }
+    else if (all) { // the last column has stopped, in this iteration: pass C of it still runs, nothing after it
+        int it_last = 0;
+        for (int c = 0; c < k; ++c) it_last = max(it_last, flags[4 + 4 * c + 3]);
+        flags[3] = it_last;
+        flags[1] = 1;
+    }
+}
+
 // pass C: x += alpha_j p ; p = z + beta_j p.  `it`: the iteration this launch belongs to -- a column whose stop test fired
 // in THIS iteration still gets its x update (bis_cg.hip, pass C).
 __global__ __launch_bounds__(kT) void mcg_p_update_kernel(int64_t n, int k, const double *__restrict__ sc, const int *__restrict__ flags,
@@ -211,6 +315,12 @@ __global__ __launch_bounds__(kT) void mcg_p_update_kernel(int64_t n, int k, cons
         __builtin_nontemporal_store(xv, X + e);
         P[e] = fma(beta, pv, Z[e]);
     }
+}
+
+// Z = M^-1 R with the preconditioner of bis_mcg_set_preconditioner
+inline bis_status mcg_apply_pc(bis_ctx *ctx, bis_mcg *m) {
+    return bis_mapply_preconditioner(ctx, m->pc, m->n, m->k, m->pcL, m->pcU, m->pcAD, m->pcADinv, m->pcLD, m->pcUD, m->Z, m->R,
+                                     m->pc_tmp, m->pc_work, 1, m->pc_inner);
 }
 
 inline int mcg_grid(int64_t n, int k) {
@@ -243,12 +353,57 @@ bis_status bis_mcg_create(bis_ctx *ctx, const bis_mat *A, const double *A_D, con
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
     if (st == BIS_OK && (hipMalloc(&m->flags, sizeof(int) * n_flags) != hipSuccess ||
                          hipMemsetAsync(m->flags, 0, sizeof(int) * n_flags, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&m->counters, sizeof(unsigned) * 2 * kCounterSet) != hipSuccess ||
-                         hipMemsetAsync(m->counters, 0, sizeof(unsigned) * 2 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK && (hipMalloc(&m->counters, sizeof(unsigned) * 3 * kCounterSet) != hipSuccess ||
+                         hipMemsetAsync(m->counters, 0, sizeof(unsigned) * 3 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
     if (st == BIS_OK) st = bis_ensure_partials(ctx, (size_t)2 * kMaxK * kMaxReduceBlocks);
     if (st != BIS_OK) { bis_mcg_destroy(ctx, m); return st; }
     if (!A_D) m->Z = m->R; // z aliases r without a preconditioner
     *out = m;
+    return BIS_OK;
+}
+
+bis_status bis_mcg_set_preconditioner(bis_ctx *ctx, bis_mcg *m, int precond_type, const bis_mat *L_strict, const bis_mat *U_strict,
+                                      const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D,
+                                      int outer_iters, int inner_iters) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_ILU0_ITER && outer_iters >= 1 && inner_iters >= 0,
+                "bis_mcg_set_preconditioner: bad arguments");
+    BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0, "bis_mcg_set_preconditioner: call it before bis_mcg_init / bis_mcg_iterate");
+    if (precond_type == BIS_PC_TWO_STAGE_GS || precond_type == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {
+        ctx->err = "bis_mcg_set_preconditioner: the two-stage Gauss-Seidel types have no multi-vector form";
+        return BIS_ERR_UNSUPPORTED;
+    }
+    if (outer_iters != 1) {
+        ctx->err = "bis_mcg_set_preconditioner: outer_iters must be 1 on interleaved blocks";
+        return BIS_ERR_UNSUPPORTED;
+    }
+    // the operands the type reads (bis_mapply_preconditioner would refuse them only at bis_mcg_init)
+    const bool lower = precond_type == BIS_PC_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || precond_type == BIS_PC_ILU0 ||
+                       precond_type == BIS_PC_ILU0_ITER;
+    const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
+                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
+    const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
+    BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mcg_set_preconditioner: the type needs a triangle that is null");
+    BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n), "bis_mcg_set_preconditioner: a triangle of another size");
+    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
+                                   (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
+                "bis_mcg_set_preconditioner: the type needs a diagonal that is null");
+    // every allocation first: a failure leaves the handle as it was
+    const int64_t nk = m->n * m->k;
+    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu;
+    double *z = nullptr, *tmp = nullptr, *work = nullptr;
+    bis_status st = BIS_OK;
+    if (m->Z == m->R) st = bis_vec_alloc(ctx, nk, &z); // z aliased r (no preconditioner at creation): it needs its own storage now
+    if (st == BIS_OK && need_tmp && !m->pc_tmp) st = bis_vec_alloc(ctx, nk, &tmp);
+    if (st == BIS_OK && precond_type == BIS_PC_ILU0_ITER && !m->pc_work) st = bis_vec_alloc(ctx, nk, &work);
+    if (st != BIS_OK) { hipFree(z); hipFree(tmp); hipFree(work); return st; }
+    if (z) m->Z = z;
+    if (tmp) m->pc_tmp = tmp;
+    if (work) m->pc_work = work;
+    m->pc = precond_type;
+    m->pcL = L_strict; m->pcU = U_strict;
+    m->pcAD = A_D; m->pcADinv = A_D_inv; m->pcLD = L_D; m->pcUD = U_D;
+    m->pc_inner = inner_iters;
     return BIS_OK;
 }
 
@@ -264,6 +419,8 @@ bis_status bis_mcg_destroy(bis_ctx *ctx, bis_mcg *m) {
     hipFree(m->hist);
     hipFree(m->flags);
     hipFree(m->counters);
+    hipFree(m->pc_tmp);
+    hipFree(m->pc_work);
     delete m;
     return BIS_OK;
 }
@@ -282,12 +439,22 @@ bis_status bis_mcg_init(bis_ctx *ctx, bis_mcg *m, double tol, double *r0_norms_h
     if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, m->X, m->T, k); // init_residual, cg.hpp:100-118
     if (st != BIS_OK) return st;
     const int g = mcg_grid(n, k);
+    if (m->pc >= 0) { // general preconditioner: r0 and (r,r), z0 = M^-1 r0, then p0 = z0, (r,z) and the start of the solve
+        hipLaunchKernelGGL(mcg_update_pc_kernel<true>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->B, m->R,
+                           ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet);
+        st = mcg_apply_pc(ctx, m);
+        if (st != BIS_OK) return st;
+        hipLaunchKernelGGL(mcg_rz_kernel<true>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->R, m->Z, m->P,
+                           ctx->partials, (size_t)kMaxReduceBlocks, m->counters + 2 * kCounterSet, m->hist, m->hist_cap, tol);
+    } else {
 #define BIS_MCG_INIT(J)                                                                                                      \
     hipLaunchKernelGGL((mcg_update_kernel<J, true>), dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->A_D,  \
                        m->B, m->R, m->Z, m->P, ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet, m->hist,  \
                        m->hist_cap, tol)
     if (m->A_D) BIS_MCG_INIT(true); else BIS_MCG_INIT(false);
 #undef BIS_MCG_INIT
+    }
+    m->initialised = true;
     BIS_HIP_CHECK(ctx, hipGetLastError());
     double norms[kMaxK] = {0};
     for (int j = 0; j < k; ++j)
@@ -314,12 +481,21 @@ bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters) {
         if (st != BIS_OK) { m->enqueued += done; return st; }
         hipLaunchKernelGGL(mcg_pap_kernel, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->T, m->P, m->sc, m->flags, ctx->partials,
                            (size_t)kMaxReduceBlocks, m->counters);
+        if (m->pc >= 0) { // general preconditioner: bis_cg.hip's schedule (cg_enqueue_iteration, cg->pc >= 0) per column
+            hipLaunchKernelGGL(mcg_update_pc_kernel<false>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->B, m->R,
+                               ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet);
+            st = mcg_apply_pc(ctx, m);
+            if (st != BIS_OK) { m->enqueued += done; return st; }
+            hipLaunchKernelGGL(mcg_rz_kernel<false>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->R, m->Z, m->P,
+                               ctx->partials, (size_t)kMaxReduceBlocks, m->counters + 2 * kCounterSet, m->hist, m->hist_cap, 0.0);
+        } else {
 #define BIS_MCG_UPDATE(J)                                                                                                    \
     hipLaunchKernelGGL((mcg_update_kernel<J, false>), dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->A_D, \
                        m->B, m->R, m->Z, m->P, ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet, m->hist,  \
                        m->hist_cap, 0.0)
         if (m->A_D) BIS_MCG_UPDATE(true); else BIS_MCG_UPDATE(false);
 #undef BIS_MCG_UPDATE
+        }
         hipLaunchKernelGGL(mcg_p_update_kernel, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, it, m->Z, m->X, m->P);
     }
     BIS_HIP_CHECK(ctx, hipGetLastError());

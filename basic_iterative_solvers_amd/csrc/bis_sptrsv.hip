@@ -56,6 +56,7 @@
 // HBM traffic ~ 12*nnz_T + 28*N algorithmic (+ 24*N for the sentinel scratch);
 // the level-scheduled solve is latency-bound on stencils: one cross-CU hand-off (~3 us) per level.
 #include "bis_internal.hpp"
+#include "bis_trsv_level.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -115,6 +116,8 @@ void bis_trsv_drop(bis_mat *A, bool chains) {
         s.tiled_tried = false;
         bis_trsv_plan_destroy(s.level);
         s.level = nullptr;
+        bis_trsm_plan_destroy(s.multi);
+        s.multi = nullptr;
         if (!chains) continue;
         bis_trsv_chain_destroy(s.chain);
         s.chain = nullptr;
@@ -124,22 +127,13 @@ void bis_trsv_drop(bis_mat *A, bool chains) {
 
 bool bis_trsv_holds_plans(const bis_mat *A) {
     for (const bis_trsv_side &s : A->trsv)
-        if (s.level || s.tiled || s.chain) return true;
+        if (s.level || s.tiled || s.chain || s.multi) return true;
     return false;
 }
 
 namespace {
 
-constexpr unsigned long long kSentinel = 0x7FF85EA71E55C0DEull; // quiet NaN + payload
-constexpr unsigned long long kCanonNaN = 0x7FF8000000000000ull;
 constexpr int kTrsvT = 256;
-constexpr unsigned kSpinLimit = 1u << 20; // polls of one row before it gives up and publishes NaN (about a second)
-constexpr unsigned kFaultPollMask = 1023u; // a waiting row reads the context's fault word every 1024 polls: once ANY wait of the
-                                           // sweep has given up, every other wait ends within a millisecond and later rows do not
-                                           // wait at all -- a starved or lost hand-off drains the grid at once instead of row by row
-__device__ __forceinline__ bool fault_raised(const unsigned *fault) {
-    return __hip_atomic_load(fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
-}
 constexpr int kWaveBlocksPerCU = 4;       // wave-per-row kernel: resident workgroups per CU the launch bound guarantees
 
 // ... and the sweep's ticket counter / elected XCD (none yet): set on the device, in stream order by construction
@@ -387,20 +381,6 @@ __global__ __launch_bounds__(kTrsvT, kWaveBlocksPerCU) void sptrsv_wave_kernel(
         }
     }
 }
-
-__global__ __launch_bounds__(256) void invert_perm_kernel(const int32_t *__restrict__ perm, int64_t n,
-                                                          int32_t *__restrict__ inv) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) inv[perm[i]] = (int32_t)i;
-}
-
-__global__ __launch_bounds__(256) void cols_to_positions_kernel(const int32_t *__restrict__ col,
-                                                                const int32_t *__restrict__ inv,
-                                                                int64_t nnz, int32_t *__restrict__ pcol) {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < nnz; k += stride) pcol[k] = inv[col[k]];
-}
-
 
 // Few, wide levels (multi-colour orderings: 2-16 levels of 10^5..10^7 rows):
 // one plain launch per level, one lane per row, no flags and no polling -- the

@@ -496,6 +496,54 @@ BIS_API bis_status bis_apply_preconditioner(
     const double *L_D, const double *U_D, double *output, double *input,
     double *tmp, double *work, int outer_iters, int inner_iters);
 
+/* ---- triangular sweeps and the preconditioner apply on several right-hand sides (no reference counterpart) ----
+ * bis_spmm's layout throughout: n x n_rhs interleaved blocks, V[i*n_rhs + j], 1 <= n_rhs <= 8; D, D_inv, A_D ... are
+ * plain n-vectors shared by all columns.
+ *
+ * bis_sptrsm / bis_bsptrsm: X_j = (D + T_strict)^-1 B_j for a strictly lower / upper triangular T_strict.  Arithmetic:
+ * for every row r in dependency order and every column j, acc = 0.0; for the row's entries e in CRS storage order
+ * acc = fma(val[e], X[col[e]*n_rhs + j], acc); then X[r*n_rhs + j] = (B[r*n_rhs + j] - acc) / D[r] -- native_sptrsv's
+ * arithmetic (kernels.hpp:54-117) with the product and the sum fused, on every matrix.  Column j equals bis_sptrsv /
+ * bis_bsptrsv on column j bit for bit wherever the single-vector sweep runs that chain: its tiled, chained, per-level,
+ * wave-per-row and lane-per-row forms.  Its row-block form (a triangle of at most 64 contiguous blocks of mutually
+ * independent rows: spmv_rowblock_kernel with the triangular epilogue) rounds each product before it adds, so there the
+ * two agree bit for bit only where the products are exact (HPCG's and the FDM stencils' -1 entries), and to rounding
+ * otherwise.  The columns never mix.
+ * X may alias B.  n_rhs == 1 forwards to bis_sptrsv / bis_bsptrsv.  BIS_ERR_INVALID: n_rhs outside 1..8, null
+ * pointers, a triangle that is not strictly lower / upper; n_rows == 0: BIS_OK.  Stream-ordered, non-blocking; nothing
+ * is allocated after the first call on a side (which analyses the triangle: a plan of the multi-vector sweeps' own,
+ * independent of the single-vector sweep's) -- except that the persistent form's scratch (8n + 8 words) and position
+ * table are made at that form's first launch, which is a later call only where trsm_form switches forms.  Level-scheduled forms only -- one launch per level for triangles of at
+ * most 64 levels, one persistent launch (a wave per row, lanes = (entry, column)) for every other; option trsm_form:
+ * 1 / 2 forces the first / second.  A wait of the persistent form that gives up raises the context's fault word: the
+ * next blocking call returns BIS_ERR_SYNC.  Inside a device schedule that has stopped the launches are no-ops.
+ * bis_mat_sweepm_kernel: what the last multi-vector sweep of that side launched, with its instance
+ * ("trsm_wave_kernel K=8 RP=32", "trsm_level_kernel K=3 RP=32", "bis_sptrsv K=1" / "bis_bsptrsv K=1"; static string,
+ * "" before the first). */
+BIS_API bis_status bis_sptrsm(bis_ctx *ctx, const bis_mat *L_strict, double *X, const double *D, const double *B, int n_rhs);
+BIS_API bis_status bis_bsptrsm(bis_ctx *ctx, const bis_mat *U_strict, double *X, const double *D, const double *B, int n_rhs);
+BIS_API const char *bis_mat_sweepm_kernel(const bis_mat *T, int backward);
+/* R[i,j] = A[i,j] / (1.0 * D[i]) (elemwise_div_vectors per column) and R[i,j] = A[i,j] * 1.0 * D[i] (elemwise_mult_vectors
+ * per column).  R may alias A. */
+BIS_API bis_status bis_mvec_div_diag(bis_ctx *ctx, double *R, const double *A, const double *D, int64_t n, int n_rhs);
+BIS_API bis_status bis_mvec_mul_diag(bis_ctx *ctx, double *R, const double *A, const double *D, int64_t n, int n_rhs);
+/* bis_itrsv on every column: the same recurrence, the product from bis_spmm, one elementwise launch per step for
+ * x = (b - s) * D_inv (subtraction and multiplication rounded separately).  Column j equals bis_itrsv on column j bit
+ * for bit wherever bis_spmm's column j equals bis_spmv's: every matrix that does not run the wave-per-row SpMV.  X and
+ * WORK are n x n_rhs blocks; the alias rules are bis_itrsv's.  n_rhs == 1 forwards to bis_itrsv. */
+BIS_API bis_status bis_mitrsv(bis_ctx *ctx, const bis_mat *T_strict, const double *D_inv, const double *B, double *X,
+                              double *WORK, int n_sweeps, int n_rhs);
+/* bis_apply_preconditioner, call for call, on interleaved blocks: NONE a copy, JACOBI bis_mvec_div_diag, GS / BGS one
+ * sweep, SGS sweep + bis_mvec_mul_diag + sweep, ILU0 two sweeps, ILU0_ITER two bis_mitrsv (scratch and alias rules of the
+ * single-vector case; OUT may alias IN).  Column j equals bis_apply_preconditioner on column j bit for bit (the sweeps:
+ * with bis_sptrsm's proviso; ILU0_ITER: with bis_mitrsv's).  BIS_PC_TWO_STAGE_GS, BIS_PC_SYMMETRIC_TWO_STAGE_GS and outer_iters != 1:
+ * BIS_ERR_UNSUPPORTED.  TMP, WORK: n x n_rhs blocks, needed by SGS / ILU0 / ILU0_ITER (TMP) and ILU0_ITER (WORK). */
+BIS_API bis_status bis_mapply_preconditioner(
+    bis_ctx *ctx, int precond_type, int64_t n, int n_rhs, const bis_mat *L_strict,
+    const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
+    const double *L_D, const double *U_D, double *OUT, double *IN,
+    double *TMP, double *WORK, int outer_iters, int inner_iters);
+
 /* ---- named kernels: the reference's plugin protocol --------------------------
  * The reference's accelerator seam (SMAX) registers each kernel once under a
  * name with persistent operands, runs it by name, and rebinds operands after
@@ -611,6 +659,16 @@ BIS_API bis_status bis_cg_status(bis_ctx *ctx, bis_cg *cg, int *iters,
 typedef struct bis_mcg bis_mcg;
 BIS_API bis_status bis_mcg_create(bis_ctx *ctx, const bis_mat *A, const double *A_D, const double *B, double *X,
                                   int n_rhs, bis_mcg **out);
+/* General preconditioner, as bis_cg_set_preconditioner: Z = M^-1 R through bis_mapply_preconditioner.  Pass B then
+ * updates R and (r,r) only; the apply, the k sums (r_j, z_j) with the per-column bookkeeping, and pass C follow.  The
+ * handle owns the Z, TMP and WORK blocks the type needs.  Call before bis_mcg_init: BIS_ERR_INVALID afterwards; the
+ * two-stage types and outer_iters != 1: BIS_ERR_UNSUPPORTED.  A stopped column stays frozen as without the call (the
+ * apply may still compute its z, which nothing reads). */
+BIS_API bis_status bis_mcg_set_preconditioner(bis_ctx *ctx, bis_mcg *m, int precond_type,
+                                              const bis_mat *L_strict, const bis_mat *U_strict,
+                                              const double *A_D, const double *A_D_inv,
+                                              const double *L_D, const double *U_D,
+                                              int outer_iters, int inner_iters);
 /* r0 = b - A x0, z0, p0 per column; r0_norms_host (n_rhs entries, may be NULL) receives ||r0_j||_2 (blocking) */
 BIS_API bis_status bis_mcg_init(bis_ctx *ctx, bis_mcg *m, double tol, double *r0_norms_host);
 BIS_API bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters); /* non-blocking */
