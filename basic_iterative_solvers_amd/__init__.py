@@ -373,6 +373,9 @@ class Context:
     def mcg(self, A, B, X, k, A_D=None):
         return MCG(self, A, B, X, k, A_D)
 
+    def mbicgstab(self, A, B, X, k):
+        return MBiCGSTAB(self, A, B, X, k)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -601,6 +604,46 @@ class MCG:
     def free(self):
         if self.h:
             self.ctx.lib.bis_mcg_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class MBiCGSTAB:
+    """k BiCGSTAB solves in lock-step (bis_mbicgstab_*): B, X are n x k interleaved device blocks; two SpMMs and two
+    preconditioner applies per iteration for all columns."""
+
+    def __init__(self, ctx, A, B, X, k):
+        self.ctx, self.k = ctx, int(k)
+        self.h = C.c_void_p()
+        self._keep = (A, B, X)
+        ctx.check(ctx.lib.bis_mbicgstab_create(ctx.h, A.h, C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k), C.byref(self.h)))
+
+    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
+        self.ctx.check(self.ctx.lib.bis_mbicgstab_set_preconditioner(
+            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
+
+    def init(self, tol):
+        r0 = np.zeros(self.k)
+        self.ctx.check(self.ctx.lib.bis_mbicgstab_init(self.ctx.h, self.h, C.c_double(tol), r0.ctypes))
+        return r0
+
+    def iterate(self, n):
+        self.ctx.check(self.ctx.lib.bis_mbicgstab_iterate(self.ctx.h, self.h, C.c_int(int(n))))
+
+    def status(self, j, hist_cap=4096):
+        iters, conv = C.c_int(), C.c_int()
+        hist = np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_mbicgstab_status(self.ctx.h, self.h, C.c_int(int(j)), C.byref(iters), C.byref(conv),
+                                                         hist.ctypes, C.c_int(hist_cap)))
+        return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_mbicgstab_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 

@@ -20,7 +20,7 @@
 // (multi-vector sweeps, bis_sptrsm.hip), then the k sums (r_j, z_j) and the per-column bookkeeping (mcg_rz_kernel), then
 // pass C.  The sweeps and the elementwise kernels of the apply may still compute a frozen column's z: nothing of that
 // column is read afterwards.  Without the call, the None / Jacobi schedule above is launched exactly as before.
-#include "bis_internal.hpp"
+#include "bis_lockstep.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -52,11 +52,9 @@ struct bis_mcg {
 
 namespace {
 
+using namespace bis_lockstep;
+
 enum { M_RZ = 0, M_PAP, M_ALPHA, M_BETA, M_RR, M_STOP, M_RR_NEW /* general preconditioner: (r,r) between pass B and the bookkeeping */, M_COUNT = 8 };
-constexpr int kT = 256;
-constexpr int kMaxK = 8;
-constexpr int kMaxIters = 1 << 20;
-constexpr unsigned kCounterSet = 4 + kArriveSubs;
 
 // cg_book of bis_cg.hip for one column
 __device__ __forceinline__ void mcg_book(double rz_new, double rr, double *sc, int *flags, double *hist, int hist_cap) {
@@ -71,50 +69,6 @@ __device__ __forceinline__ void mcg_book(double rz_new, double rr, double *sc, i
     const bool conv = fabs(norm) < sc[M_STOP];
     const bool diverged = fabs(norm) > DBL_MAX || norm != norm;
     if (conv || diverged) { flags[1] = 1; flags[2] = conv ? 1 : 0; flags[3] = it; }
-}
-
-// per-column sums of a workgroup: lane t < act holds a partial of column t % k; thread 0 publishes the k (or 2 k) sums and
-// takes the ticket.  Returns (in every lane) whether this workgroup arrived last.
-template <int NV>
-__device__ __forceinline__ bool fold_and_arrive(const double (&v)[NV], int k, int act, double *lds /*[NV][kT]*/, double *partials,
-                                                size_t stride, unsigned *counter) {
-    __shared__ bool last;
-    __shared__ double sums[NV * kMaxK];
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) lds[q * kT + t] = v[q];
-    __syncthreads();
-    if (t < NV * k) { // lane (q, j): column j's partials in lane order
-        const int q = t / k, j = t - q * k;
-        double s = 0.0;
-        for (int i = j; i < act; i += k) s += lds[q * kT + i];
-        sums[t] = s;
-    }
-    __syncthreads();
-    if (t == 0) {
-        for (int i = 0; i < NV * k; ++i) publish(partials + (size_t)i * stride + blockIdx.x, sums[i]);
-        last = arrive_last2(counter, counter + 3, blockIdx.x, gridDim.x);
-    }
-    __syncthreads();
-    return last;
-}
-
-// the last workgroup: out[i] (valid in thread 0) = sum over the workgroups of value i's partials, in a fixed order: 16 lanes
-// per value (NV k <= 16 values), lane l sums the workgroups l, l + 16, ... in index order, thread 0 the 16 lane sums in lane order
-template <int NV>
-__device__ __forceinline__ void sum_partials(int k, const double *partials, size_t stride, double *lds /*[kT]*/, double (&out)[NV * kMaxK]) {
-    const int t = threadIdx.x, v = t >> 4, l = t & 15;
-    double a = 0.0;
-    if (v < NV * k)
-        for (int b = l; b < (int)gridDim.x; b += 16) a += fetch(partials + (size_t)v * stride + b);
-    lds[t] = a;
-    __syncthreads();
-    if (t == 0)
-        for (int i = 0; i < NV * k; ++i) {
-            double s = 0.0;
-            for (int q = 0; q < 16; ++q) s += lds[i * 16 + q];
-            out[i] = s;
-        }
 }
 
 // pass A': pap_j = (T_j, P_j)
@@ -323,12 +277,6 @@ inline bis_status mcg_apply_pc(bis_ctx *ctx, bis_mcg *m) {
                                      m->pc_tmp, m->pc_work, 1, m->pc_inner);
 }
 
-inline int mcg_grid(int64_t n, int k) {
-    const int act = (kT / k) * k;
-    int64_t g = (n * k + act - 1) / act;
-    return (int)std::min<int64_t>(std::max<int64_t>(g, 1), kMaxReduceBlocks);
-}
-
 } // namespace
 
 extern "C" {
@@ -438,7 +386,7 @@ bis_status bis_mcg_init(bis_ctx *ctx, bis_mcg *m, double tol, double *r0_norms_h
     bis_status st = bis_ensure_partials(ctx, (size_t)2 * kMaxK * kMaxReduceBlocks);
     if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, m->X, m->T, k); // init_residual, cg.hpp:100-118
     if (st != BIS_OK) return st;
-    const int g = mcg_grid(n, k);
+    const int g = lockstep_grid(n, k);
     if (m->pc >= 0) { // general preconditioner: r0 and (r,r), z0 = M^-1 r0, then p0 = z0, (r,z) and the start of the solve
         hipLaunchKernelGGL(mcg_update_pc_kernel<true>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->B, m->R,
                            ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet);
@@ -470,7 +418,7 @@ bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters) {
     const int64_t n = m->n;
     const int k = m->k;
     if (n == 0) return BIS_OK;
-    const int g = mcg_grid(n, k);
+    const int g = lockstep_grid(n, k);
     bis_status st = bis_ensure_partials(ctx, (size_t)2 * kMaxK * kMaxReduceBlocks);
     if (st != BIS_OK) return st;
     ctx->spmv_stop = m->flags; // the SpMM (k == 1: the SpMV) returns at once when every column has stopped

@@ -677,6 +677,46 @@ BIS_API bis_status bis_mcg_status(bis_ctx *ctx, bis_mcg *m, int j, int *iters, i
                                   int hist_cap);
 BIS_API bis_status bis_mcg_destroy(bis_ctx *ctx, bis_mcg *m);
 
+/* ---- k BiCGSTAB solves in lock-step (no reference counterpart) -----------------
+ * Per column j the left-preconditioned iteration of methods/bicgstab.hpp:8-83 with
+ * its init (:147-169: the shadow residual and p_0 are the PRECONDITIONED initial
+ * residual, rho_0 = (r_0, M^-1 r_0)), the recorded norm ||r_j|| and the stop test
+ * (threshold tol * ||r0_j||) of solver.hpp:177-192.  One iteration issues two
+ * bis_mapply_preconditioner and two bis_spmm calls for all columns, and five
+ * elementwise / reduction passes over n x n_rhs blocks between them; the
+ * elementwise arithmetic is that of bis_subtract_vectors / bis_sum_vectors (one
+ * fma) and bis_scalar_ratio_product.  Scalars, histories and flags live on the
+ * device per column; nothing is read back inside bis_mbicgstab_iterate.  Layout,
+ * reductions (last arriver, index order: deterministic, not bis_dot's tree) and the
+ * independence of the columns are bis_mcg_*'s: no bit of a column depends on
+ * another column's data; parity with a BiCGSTAB made of the single-vector calls
+ * holds at the history gate, not bit for bit.  A column that has stopped is frozen:
+ * the stopping iteration has updated its x (the reference's x_new of that
+ * iteration), after that nothing of it changes; when every column has stopped,
+ * every later launch is a no-op.  A breakdown (rho, (r0~, v) or (z, z) reaching 0)
+ * gives a non-finite norm: that column stops with converged = 0, the others go on.
+ * Arguments, error codes and the order of calls are bis_mcg_*'s, call for call:
+ * A square, 1 <= n_rhs <= 8; B, X n x n_rhs interleaved, X holds the start vectors
+ * and is updated in place; set_preconditioner before init (BIS_ERR_INVALID after),
+ * two-stage types and outer_iters != 1 BIS_ERR_UNSUPPORTED, a missing operand
+ * BIS_ERR_INVALID; without the call the solve is unpreconditioned (and keeps no
+ * Y / S~ blocks: Y is P, S~ is S).  n = 0: BIS_OK, nothing is launched. */
+typedef struct bis_mbicgstab bis_mbicgstab;
+BIS_API bis_status bis_mbicgstab_create(bis_ctx *ctx, const bis_mat *A, const double *B, double *X, int n_rhs,
+                                        bis_mbicgstab **out);
+BIS_API bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab *m, int precond_type,
+                                                    const bis_mat *L_strict, const bis_mat *U_strict,
+                                                    const double *A_D, const double *A_D_inv,
+                                                    const double *L_D, const double *U_D,
+                                                    int outer_iters, int inner_iters);
+/* r0_norms_host (n_rhs entries, may be NULL) receives ||r0_j||_2 (blocking) */
+BIS_API bis_status bis_mbicgstab_init(bis_ctx *ctx, bis_mbicgstab *m, double tol, double *r0_norms_host);
+BIS_API bis_status bis_mbicgstab_iterate(bis_ctx *ctx, bis_mbicgstab *m, int n_iters); /* non-blocking */
+/* blocking: column j's iterations, converged flag and residual history [0..iters] */
+BIS_API bis_status bis_mbicgstab_status(bis_ctx *ctx, bis_mbicgstab *m, int j, int *iters, int *converged,
+                                        double *hist_host, int hist_cap);
+BIS_API bis_status bis_mbicgstab_destroy(bis_ctx *ctx, bis_mbicgstab *m);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
