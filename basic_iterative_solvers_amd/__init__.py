@@ -376,6 +376,9 @@ class Context:
     def mbicgstab(self, A, B, X, k):
         return MBiCGSTAB(self, A, B, X, k)
 
+    def mgmres(self, A, B, X, k, restart=10):
+        return MGMRES(self, A, B, X, k, restart)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -644,6 +647,53 @@ class MBiCGSTAB:
     def free(self):
         if self.h:
             self.ctx.lib.bis_mbicgstab_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class MGMRES:
+    """k restarted GMRES(restart) solves in lock-step (bis_mgmres_*): B, X are n x k interleaved device blocks; one SpMM and one
+    preconditioner apply per iteration for all columns, the Gram-Schmidt coefficients and the Givens algebra stay on the
+    device.  X of a live column is x_old of its cycle: `solution` gives the explicit iterate."""
+
+    def __init__(self, ctx, A, B, X, k, restart=10):
+        self.ctx, self.k, self.restart = ctx, int(k), int(restart)
+        self.h = C.c_void_p()
+        self._keep = (A, B, X)
+        ctx.check(ctx.lib.bis_mgmres_create(ctx.h, A.h, C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k),
+                                            C.c_int(self.restart), C.byref(self.h)))
+
+    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
+        self.ctx.check(self.ctx.lib.bis_mgmres_set_preconditioner(
+            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
+
+    def init(self, tol):
+        r0 = np.zeros(self.k)
+        self.ctx.check(self.ctx.lib.bis_mgmres_init(self.ctx.h, self.h, C.c_double(tol), r0.ctypes))
+        return r0
+
+    def iterate(self, n):
+        self.ctx.check(self.ctx.lib.bis_mgmres_iterate(self.ctx.h, self.h, C.c_int(int(n))))
+
+    def status(self, j, hist_cap=4096):
+        """(iterations, converged, history): the history has iterations + 1 + restarts entries (n_hist of bis_mgmres_status)."""
+        iters, conv, n_hist = C.c_int(), C.c_int(), C.c_int()
+        hist = np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_mgmres_status(self.ctx.h, self.h, C.c_int(int(j)), C.byref(iters), C.byref(conv),
+                                                      C.byref(n_hist), hist.ctypes, C.c_int(hist_cap)))
+        return iters.value, bool(conv.value), hist[:min(n_hist.value, hist_cap)].copy()
+
+    def solution(self, out):
+        """The explicit x of every column into the n x k block `out` (bis_mgmres_solution); the solve does not change."""
+        self.ctx.check(self.ctx.lib.bis_mgmres_solution(self.ctx.h, self.h, C.c_void_p(out.ptr)))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_mgmres_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 

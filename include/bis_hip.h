@@ -717,6 +717,71 @@ BIS_API bis_status bis_mbicgstab_status(bis_ctx *ctx, bis_mbicgstab *m, int j, i
                                         double *hist_host, int hist_cap);
 BIS_API bis_status bis_mbicgstab_destroy(bis_ctx *ctx, bis_mbicgstab *m);
 
+/* ---- k restarted GMRES(m) solves in lock-step (no reference counterpart) -------
+ * Per column j the left-preconditioned GMRES(m) of methods/gmres.hpp: init
+ * R = B - A X, history entry 0 the UNPRECONDITIONED ||R_j||, threshold
+ * tol * ||R_j||, then R = M^-1 R, beta_j = ||R_j||, V_0 = R / beta_j.  At position
+ * n of a cycle (n = iterations mod restart_len, the same for every live column):
+ * W = M^-1 A V_n, modified Gram-Schmidt in the reference's order (h_i = (W, V_i),
+ * W -= h_i V_i, i = 0 .. n; one fma per element, fma-accumulated dots),
+ * h_{n+1} = ||W||, V_{n+1} = W / h_{n+1}; the new Hessenberg column is rotated by
+ * the stored Givens rotations, the new one is c = a / den, s = b / den with
+ * den = sqrt(a^2 + b^2); the history entry is |g_{n+1}|, the estimate of the
+ * preconditioned residual; the stop test is bis_mcg_*'s (< threshold, non-finite,
+ * NaN).  At the end of a cycle the columns that go on restart: y by back
+ * substitution (y[n] = 0 where the reference reads one past the end),
+ * X += sum y_i V_i, R = M^-1 (B - A X), beta_j = ||R_j||, which is written as ONE
+ * MORE history entry (Solver::init_residual) and tested against the threshold,
+ * V_0 = R / beta_j.  So a column's history has iters + 1 + restarts entries:
+ * bis_mgmres_status returns that count as n_hist.
+ * One iteration at position n issues one bis_spmm, one bis_mapply_preconditioner
+ * (in place), n + 2 fused Gram-Schmidt / reduction passes and one scale for all
+ * columns (56 + 32 n bytes per row and column besides the SpMM and the apply);
+ * coefficients, rotations, g, y, histories and flags live on the device per column
+ * and nothing is read back inside bis_mgmres_iterate.  Layout, reductions (last
+ * arriver, index order: deterministic, not bis_dot's tree) and the independence of
+ * the columns are bis_mcg_*'s: no bit of a column depends on another column's data
+ * (its bits depend on n, n_rhs, restart_len and its own data); parity with a GMRES
+ * made of the single-vector calls holds at the history gate, not bit for bit.
+ * X is only ever updated by adding V y: while a column is live inside a cycle its
+ * X is x_old (bis_mgmres_solution gives the explicit iterate).  A column that stops
+ * gets the y of its own cycle's steps added to X before the bis_mgmres_iterate call
+ * that stopped it has enqueued its last kernel; after that nothing of it changes.
+ * When every column has stopped, every later launch is a no-op.  b_j = 0 with
+ * x0_j = 0 (beta = 0) stops at iteration 1, not converged; a lucky breakdown
+ * (h_{n+1} = 0) gives the estimate 0 and converges in that iteration.
+ * Memory: the basis is restart_len + 1 blocks, one more block W, so
+ * (restart_len + 2) n n_rhs doubles, plus at most two blocks of scratch for the
+ * preconditioner (SGS, ILU0: one; ILU0_ITER: two) and
+ * n_rhs (restart_len^2 + 6 restart_len + 5) doubles of per-column state.
+ * Arguments, error codes and the order of calls are bis_mbicgstab_*'s: A square,
+ * 1 <= n_rhs <= 8, 1 <= restart_len <= 64 (bis_multi_axpy's limit); B, X
+ * n x n_rhs interleaved, X holds the start vectors and is updated in place;
+ * set_preconditioner before init (BIS_ERR_INVALID after), two-stage types and
+ * outer_iters != 1 BIS_ERR_UNSUPPORTED, a missing operand BIS_ERR_INVALID; without
+ * the call the solve is unpreconditioned.  n = 0: BIS_OK, nothing is launched. */
+typedef struct bis_mgmres bis_mgmres;
+BIS_API bis_status bis_mgmres_create(bis_ctx *ctx, const bis_mat *A, const double *B, double *X, int n_rhs,
+                                     int restart_len, bis_mgmres **out);
+BIS_API bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precond_type,
+                                                 const bis_mat *L_strict, const bis_mat *U_strict,
+                                                 const double *A_D, const double *A_D_inv,
+                                                 const double *L_D, const double *U_D,
+                                                 int outer_iters, int inner_iters);
+/* r0_norms_host (n_rhs entries, may be NULL) receives the unpreconditioned ||r0_j||_2 (blocking) */
+BIS_API bis_status bis_mgmres_init(bis_ctx *ctx, bis_mgmres *m, double tol, double *r0_norms_host);
+/* non-blocking; the cycle position persists across calls (no call boundary restarts a cycle) */
+BIS_API bis_status bis_mgmres_iterate(bis_ctx *ctx, bis_mgmres *m, int n_iters);
+/* blocking: the explicit x of every column into X_out (n x n_rhs interleaved, not X itself): X_j for a stopped column,
+ * X_j + V y at the current step for a live one (the reference's save_x_star for a run that ends on an iteration
+ * budget).  The handle's state does not change. */
+BIS_API bis_status bis_mgmres_solution(bis_ctx *ctx, bis_mgmres *m, double *X_out);
+/* blocking: column j's iterations, converged flag, the number of history entries (iters + 1 + restarts) and the
+ * first min(n_hist, hist_cap) of them */
+BIS_API bis_status bis_mgmres_status(bis_ctx *ctx, bis_mgmres *m, int j, int *iters, int *converged, int *n_hist,
+                                     double *hist_host, int hist_cap);
+BIS_API bis_status bis_mgmres_destroy(bis_ctx *ctx, bis_mgmres *m);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
