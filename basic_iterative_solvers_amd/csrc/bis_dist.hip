@@ -667,10 +667,10 @@ bis_status bis_dist_set_send_lists(bis_ctx *ctx, bis_dist *d, const int64_t *sen
                                    const int32_t *send_cols_global) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, d && send_counts, "bis_dist_set_send_lists: bad arguments");
+    // everything is checked before anything of the handle changes: a refused call leaves the lists of the last good one
     int64_t total = 0;
     for (int p = 0; p < d->n_ranks; ++p) {
         BIS_REQUIRE(ctx, send_counts[p] >= 0, "bis_dist_set_send_lists: negative count");
-        d->send_counts[p] = send_counts[p];
         total += send_counts[p];
     }
     BIS_REQUIRE(ctx, total == 0 || send_cols_global, "bis_dist_set_send_lists: null list");
@@ -686,9 +686,12 @@ bis_status bis_dist_set_send_lists(bis_ctx *ctx, bis_dist *d, const int64_t *sen
     hipFree(d->sendbuf);
     d->send_idx = nullptr;
     d->sendbuf = nullptr;
+    d->n_send = 0;
+    std::fill(d->send_counts.begin(), d->send_counts.end(), 0);
     BIS_HIP_CHECK(ctx, hipMalloc(&d->send_idx, sizeof(int32_t) * idx.size()));
     BIS_HIP_CHECK(ctx, hipMalloc(&d->sendbuf, sizeof(double) * idx.size()));
     BIS_HIP_CHECK(ctx, hipMemcpy(d->send_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
+    d->send_counts.assign(send_counts, send_counts + d->n_ranks);
     d->n_send = total;
     return BIS_OK;
 }
