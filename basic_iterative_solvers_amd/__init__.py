@@ -16,7 +16,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "lib", "libbis_hip.so")
 
-PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8})
+PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8, "fsai": 9})
 
 _lib = None
 
@@ -42,6 +42,7 @@ def load_library():
         _lib.bis_itrsv_kernel.restype = C.c_char_p
         _lib.bis_mat_spmm_kernel.restype = C.c_char_p
         _lib.bis_mat_sweepm_kernel.restype = C.c_char_p
+        _lib.bis_mat_fsai_kernel.restype = C.c_char_p
     return _lib
 
 
@@ -241,6 +242,13 @@ class Context:
                                          C.byref(hl), C.byref(hu), C.c_void_p(L_D.ptr),
                                          C.c_void_p(U_D.ptr)))
         return Mat(self, hl), L_D, Mat(self, hu), U_D
+
+    def fsai(self, A):
+        """(G, Gt, n_fallback): the factorized sparse approximate inverse of A on the pattern of tril(A), M^-1 = Gt G
+        (bis_mat_fsai); preconditioner "fsai" takes Ls=G, Us=Gt.  n_fallback counts the rows that became e_i / sqrt(|a_ii|)."""
+        hg, hgt, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self.check(self.lib.bis_mat_fsai(self.h, A.h, C.byref(hg), C.byref(hgt), C.byref(nf)))
+        return Mat(self, hg), Mat(self, hgt), nf.value
 
     # ---- kernels (kernels.hpp names) ---------------------------------------
     def spmv(self, A, x, y):
@@ -506,6 +514,11 @@ class Mat:
     def ilu0_kernel(self):
         """Name of the elimination kernel that factorised this ILU(0) L factor (bis_mat_ilu0_kernel); "" for other matrices."""
         return self.ctx.lib.bis_mat_ilu0_kernel(self.h).decode()
+
+    def fsai_kernel(self):
+        """The instance of fsai_rows_kernel that computed this FSAI factor G, e.g. "fsai_rows_kernel M=32 RP=32"
+        (bis_mat_fsai_kernel); "" for other matrices."""
+        return self.ctx.lib.bis_mat_fsai_kernel(self.h).decode()
 
     def itrsv_kernel(self):
         """Name of the path the last bis_itrsv step on this triangle took (bis_itrsv_kernel): "itrsv_fused_rowblock" or

@@ -453,6 +453,39 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
 
 } // namespace
 
+bis_status bis_mat_sorted_copy(bis_ctx *ctx, const bis_mat *A, bis_mat **W_out, int64_t **dpos_out, int64_t **ustart_out) {
+    const int64_t n = A->n_rows;
+    bis_mat *W = nullptr;
+    bis_status st = bis_mat_alloc(ctx, n, A->n_cols, A->nnz, A->rp64, &W);
+    if (st != BIS_OK) return st;
+    int64_t *dpos = nullptr, *ustart = nullptr;
+    const size_t rpw = A->rp64 ? sizeof(int64_t) : sizeof(int32_t);
+    hipError_t e = hipMalloc(&dpos, sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1));
+    if (e == hipSuccess) e = hipMalloc(&ustart, sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1));
+    if (e == hipSuccess) e = hipMemcpyAsync(W->row_ptr, A->row_ptr, rpw * (size_t)(n + 1), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && n > 0) {
+        const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, 1 << 22));
+        if (A->rp64)
+            hipLaunchKernelGGL(sort_rows_wave_kernel<int64_t>, grid, dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->val, n,
+                               W->col, W->val, dpos, ustart);
+        else
+            hipLaunchKernelGGL(sort_rows_wave_kernel<int32_t>, grid, dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, A->val, n,
+                               W->col, W->val, dpos, ustart);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        ctx->err = std::string("bis_mat_sorted_copy: ") + hipGetErrorString(e);
+        hipFree(dpos);
+        hipFree(ustart);
+        bis_mat_destroy(ctx, W);
+        return BIS_ERR_HIP;
+    }
+    *W_out = W;
+    *dpos_out = dpos;
+    *ustart_out = ustart;
+    return BIS_OK;
+}
+
 extern "C" {
 
 const char *bis_mat_ilu0_kernel(const bis_mat *L_strict) { return L_strict ? L_strict->ilu0_kernel : ""; }

@@ -220,6 +220,7 @@ struct bis_mat {
     const char *ilu0_kernel = "";           // the elimination kernel that made this ILU(0) L factor (bis_mat_ilu0_kernel)
     const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
     const char *spmm_kernel = "";           // the path and template instance the last bis_spmm on this matrix launched (bis_mat_spmm_kernel)
+    const char *fsai_kernel = "";           // the instance of fsai_rows_kernel that computed this FSAI factor G (bis_mat_fsai_kernel)
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \
@@ -430,6 +431,10 @@ bool bis_trsv_holds_plans(const bis_mat *A); // some direction holds a level, ti
 void bis_trsv_plan_adopt(bis_mat *to, bis_mat *from, bool backward);
 bis_status bis_mat_split_strict_impl(bis_ctx *ctx, const bis_mat *A, bis_mat **L_strict,
                                      bis_mat **U_strict, double *D, double *D_inv, bool check_diag);
+// W = A with ascending columns inside each row (bis_ilu0.hip's sort, stable for repeated columns; W is not finalized), and
+// per row the position of its first diagonal entry (-1: none) and of its first entry right of the diagonal.  The caller
+// destroys W and frees the two device arrays.
+bis_status bis_mat_sorted_copy(bis_ctx *ctx, const bis_mat *A, bis_mat **W, int64_t **dpos, int64_t **ustart);
 // tiled natural-order sweep (bis_trsv_tiled.hip); *out stays null when the matrix does not qualify
 bis_status bis_trsv_tiled_build(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_tiled **out);
 bis_status bis_trsv_tiled_solve(bis_ctx *ctx, bis_trsv_tiled *p, double *x, const double *D, const double *b);

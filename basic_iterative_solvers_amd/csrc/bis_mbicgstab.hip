@@ -277,7 +277,7 @@ bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab *m, int 
                                             const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                             const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_ILU0_ITER && outer_iters >= 1 && inner_iters >= 0,
+    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_FSAI && outer_iters >= 1 && inner_iters >= 0,
                 "bis_mbicgstab_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0,
                 "bis_mbicgstab_set_preconditioner: call it before bis_mbicgstab_init / bis_mbicgstab_iterate");
@@ -291,20 +291,20 @@ bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab *m, int 
     }
     // the operands the type reads (bis_mapply_preconditioner would refuse them only at bis_mbicgstab_init)
     const bool lower = precond_type == BIS_PC_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || precond_type == BIS_PC_ILU0 ||
-                       precond_type == BIS_PC_ILU0_ITER;
+                       precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
     const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
+                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
     const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
     BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mbicgstab_set_preconditioner: the type needs a triangle that is null");
     BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n),
                 "bis_mbicgstab_set_preconditioner: a triangle of another size");
-    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
+    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
                                    (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
                 "bis_mbicgstab_set_preconditioner: the type needs a diagonal that is null");
     // every allocation first: a failure leaves the handle as it was
     const int64_t nk = m->n * m->k;
     const bool need_blocks = precond_type != BIS_PC_NONE;
-    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu;
+    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu || precond_type == BIS_PC_FSAI; // (FSAI: the factors and TMP only)
     double *y = nullptr, *s_t = nullptr, *tmp = nullptr, *work = nullptr;
     bis_status st = BIS_OK;
     if (need_blocks && !m->Y) st = bis_vec_alloc(ctx, nk, &y);

@@ -400,7 +400,7 @@ bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precon
                                          const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_ILU0_ITER && outer_iters >= 1 && inner_iters >= 0,
+    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_FSAI && outer_iters >= 1 && inner_iters >= 0,
                 "bis_mgmres_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0,
                 "bis_mgmres_set_preconditioner: call it before bis_mgmres_init / bis_mgmres_iterate");
@@ -414,19 +414,19 @@ bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precon
     }
     // the operands the type reads (bis_mapply_preconditioner would refuse them only at bis_mgmres_init)
     const bool lower = precond_type == BIS_PC_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || precond_type == BIS_PC_ILU0 ||
-                       precond_type == BIS_PC_ILU0_ITER;
+                       precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
     const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
+                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
     const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
     BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mgmres_set_preconditioner: the type needs a triangle that is null");
     BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n),
                 "bis_mgmres_set_preconditioner: a triangle of another size");
-    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
+    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
                                    (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
                 "bis_mgmres_set_preconditioner: the type needs a diagonal that is null");
     // every allocation first: a failure leaves the handle as it was
     const int64_t nk = m->n * m->k;
-    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu;
+    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu || precond_type == BIS_PC_FSAI; // (FSAI: the factors and TMP only)
     double *tmp = nullptr, *work = nullptr;
     bis_status st = BIS_OK;
     if (need_tmp && !m->pc_tmp) st = bis_vec_alloc(ctx, nk, &tmp);

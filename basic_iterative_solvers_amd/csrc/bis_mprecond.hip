@@ -88,7 +88,7 @@ bis_status bis_mapply_preconditioner(bis_ctx *ctx, int pc, int64_t n, int n_rhs,
                                      const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D, double *OUT,
                                      double *IN, double *TMP, double *WORK, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1 && pc >= BIS_PC_NONE && pc <= BIS_PC_ILU0_ITER, "bis_mapply_preconditioner: bad arguments");
+    BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1 && pc >= BIS_PC_NONE && pc <= BIS_PC_FSAI, "bis_mapply_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, n_rhs >= 1 && n_rhs <= kMpMaxK, "bis_mapply_preconditioner: n_rhs must be between 1 and 8");
     if (pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {
         ctx->err = "bis_mapply_preconditioner: the two-stage Gauss-Seidel types have no multi-vector form";
@@ -127,6 +127,13 @@ bis_status bis_mapply_preconditioner(bis_ctx *ctx, int pc, int64_t n, int n_rhs,
                     "bis_mapply_preconditioner: ILU0_ITER needs both factors, inner_iters >= 0, and TMP, WORK distinct from each other, OUT and IN");
         bis_status st = bis_mitrsv(ctx, L_strict, L_D, IN, TMP, WORK, inner_iters, k);
         if (st == BIS_OK) st = bis_mitrsv(ctx, U_strict, A_D_inv, TMP, OUT, WORK, inner_iters, k);
+        return st;
+    }
+    case BIS_PC_FSAI: { // OUT = Gt (G IN), two bis_spmm: G in L_strict, Gt in U_strict (bis_mat_fsai)
+        BIS_REQUIRE(ctx, L_strict && U_strict && (n == 0 || (TMP && TMP != OUT && TMP != IN)),
+                    "bis_mapply_preconditioner: FSAI needs both factors and TMP distinct from OUT and IN");
+        bis_status st = bis_spmm_launch(ctx, L_strict, IN, TMP, k);
+        if (st == BIS_OK) st = bis_spmm_launch(ctx, U_strict, TMP, OUT, k);
         return st;
     }
     default:

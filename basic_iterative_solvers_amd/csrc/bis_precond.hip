@@ -1,5 +1,6 @@
 // bis_precond.hip -- the preconditioner dispatcher (reference kernels.hpp:312-414) over the library's own kernels: the
-// triangular sweeps (bis_sptrsv.hip), the iterative triangular solves (bis_itrsv.hip), SpMV and the vector kernels.
+// triangular sweeps (bis_sptrsv.hip), the iterative triangular solves (bis_itrsv.hip), SpMV (the FSAI factors of
+// bis_fsai.hip) and the vector kernels.
 #include "bis_internal.hpp"
 
 #include <algorithm>
@@ -34,6 +35,9 @@ bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_m
         BIS_REQUIRE(ctx, L_strict && U_strict && inner_iters >= 0 && (n == 0 || (tmp && work && tmp != work && tmp != output &&
                          tmp != input && work != output && work != input)),
                     "bis_apply_preconditioner: ILU0_ITER needs both factors, inner_iters >= 0, and tmp, work distinct from each other, output and input");
+    if (pc == BIS_PC_FSAI)
+        BIS_REQUIRE(ctx, L_strict && U_strict && (n == 0 || (tmp && tmp != output && tmp != input)),
+                    "bis_apply_preconditioner: FSAI needs both factors and tmp distinct from output and input");
     double *input_storage = nullptr;
     bis_status st = BIS_OK;
     if (outer_iters > 1) { // :348-352 (the one place the reference allocates in a kernel)
@@ -75,6 +79,10 @@ bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_m
         case BIS_PC_ILU0_ITER: // (not in the reference) both solves as bis_itrsv; A_D_inv carries 1 / U_D
             st = bis_itrsv(ctx, L_strict, L_D, input, tmp, work, inner_iters);
             if (st == BIS_OK) st = bis_itrsv(ctx, U_strict, A_D_inv, tmp, output, work, inner_iters);
+            break;
+        case BIS_PC_FSAI: // (not in the reference) output = Gt (G input): G in L_strict, Gt in U_strict (bis_mat_fsai)
+            st = bis_spmv(ctx, L_strict, input, tmp);
+            if (st == BIS_OK) st = bis_spmv(ctx, U_strict, tmp, output);
             break;
         default:
             st = bis_copy_vector(ctx, output, input, n);                           // :398

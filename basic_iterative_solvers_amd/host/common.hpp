@@ -51,9 +51,9 @@
 using Interface = void *; // the SMAX seam of the reference (common.hpp:18-24) is the C ABI here
 #define SMAX_ARGS(...)
 
-enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8) is this build's addition
+enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8) and FSAI (9) are this build's additions
     None, Jacobi, GaussSeidel, BackwardsGaussSeidel, SymmetricGaussSeidel, TwoStageGS,
-    SymmetricTwoStageGS, ILU0, ILU0Iter
+    SymmetricTwoStageGS, ILU0, ILU0Iter, FSAI
 };
 
 // -inner K: inner sweeps of the two-stage Gauss-Seidel types and of -p ilu0it, at run time; the default is the
@@ -66,6 +66,7 @@ inline std::string to_string(PrecondType t) {
                               "symmetric-gauss-seidel", "two-stage gauss-seidel",
                               "symmetric two-stage gauss-seidel", "incomplete LU(0)"};
     if (t == PrecondType::ILU0Iter) return "incomplete LU(0), iterative solves (" + std::to_string(precond_inner_iters()) + ")";
+    if (t == PrecondType::FSAI) return "factorized sparse approximate inverse";
     return n[static_cast<int>(t)];
 }
 inline std::string to_string(SolverType t) {

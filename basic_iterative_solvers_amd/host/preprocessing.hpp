@@ -1,8 +1,8 @@
 // preprocessing.hpp -- setup phase, reference preprocessing.hpp:26-100:
 // allocate + initialise the solver's vectors, optional symmetric diagonal
 // scaling, split A into its strict triangles and diagonal (on the device for
-// generated matrices, on the host for file input), optional ILU(0), initial
-// residual and stopping criterion.
+// generated matrices, on the host for file input), optional ILU(0) or FSAI
+// factors, initial residual and stopping criterion.
 #pragma once
 
 #include "common.hpp"
@@ -49,6 +49,17 @@ inline void factor_LU(Solver *s) {
         s->U_strict->adopt(Us);
         // -p ilu0it multiplies by the pivots' reciprocals: A_D_inv carries 1 / U_D for that type (L_D is the vector of ones)
         if (s->preconditioner == PrecondType::ILU0Iter) elemwise_div_vectors(s->A_D_inv, s->L_D, s->U_D, s->N);
+    }
+    if (s->preconditioner == PrecondType::FSAI) {
+        // -p fsai: G and Gt = G^T take the places of the strict triangles (bis_apply_preconditioner reads them as two SpMVs)
+        bis_mat *G = nullptr, *Gt = nullptr;
+        int64_t n_fallback = 0;
+        bis::check(bis_mat_fsai(bis::ctx(), s->A->dev, &G, &Gt, &n_fallback), "bis_mat_fsai");
+        s->L_strict->free_host();
+        s->U_strict->free_host();
+        s->L_strict->adopt(G);
+        s->U_strict->adopt(Gt);
+        if (n_fallback != 0) std::cout << "fsai: " << n_fallback << " rows fell back to 1/sqrt(|a_ii|)" << std::endl;
     }
 }
 

@@ -6,7 +6,8 @@
 //     hpcg:N | hpcg:NX,NY,NZ | anderson:L[,shift=S][,W=w][,t=t][,seed=k] | fem:NX[,NY,NZ][,keep=K][,seed=k] | unstr:NX[,NY,NZ][,keep=K][,seed=k]
 // and `-unfused` / `-dev K` select the kernel-by-kernel CG and the device;
 // `-perm mc` applies the multi-colour reordering of utilities/permute.hpp; `-p ilu0it` is ILU(0) with iterative
-// triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st).
+// triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st); `-p fsai` is the
+// factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs.
 #pragma once
 
 #include <sys/stat.h>
@@ -48,14 +49,16 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 {"j", PrecondType::Jacobi}, {"gs", PrecondType::GaussSeidel},
                 {"bgs", PrecondType::BackwardsGaussSeidel}, {"sgs", PrecondType::SymmetricGaussSeidel},
                 {"2st", PrecondType::TwoStageGS}, {"s2st", PrecondType::SymmetricTwoStageGS},
-                {"ilu0", PrecondType::ILU0}, {"ilu0it", PrecondType::ILU0Iter}};
+                {"ilu0", PrecondType::ILU0}, {"ilu0it", PrecondType::ILU0Iter},
+                {"fsai", PrecondType::FSAI}};
             auto it = pcs.find(pt);
             if (it == pcs.end()) {
                 fprintf(stderr, "ERROR: assign_cli_inputs: Please choose an available preconditioner type: "
                                 "\n-p j (Jacobi)\n-p gs (Gauss-Seidel)\n-p bgs (Backwards Gauss-Seidel)"
                                 "\n-p sgs (Symmetric Gauss-Seidel)\n-p 2st (2 Stage Gauss-Seidel)"
                                 "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)"
-                                "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)\n");
+                                "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)"
+                                "\n-p fsai (Factorized sparse approximate inverse on the pattern of tril(A))\n");
                 exit(EXIT_FAILURE);
             }
             a->preconditioner = it->second;

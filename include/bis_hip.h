@@ -66,7 +66,9 @@ enum {
     BIS_PC_SYMMETRIC_TWO_STAGE_GS = 6,
     BIS_PC_ILU0 = 7,
     /* not in the reference: ILU(0) whose two triangular solves are bis_itrsv with inner_iters steps each */
-    BIS_PC_ILU0_ITER = 8
+    BIS_PC_ILU0_ITER = 8,
+    /* not in the reference: factorized sparse approximate inverse, M^-1 = Gt G with the factors of bis_mat_fsai */
+    BIS_PC_FSAI = 9
 };
 
 typedef struct bis_ctx bis_ctx; /* device + stream + scratch (SMAX::Interface
@@ -332,6 +334,25 @@ BIS_API bis_status bis_mat_ilu0(bis_ctx *ctx, const bis_mat *A, double pivot_tol
  * or "ilu0_level_kernel" (static string; "" for any other matrix). */
 BIS_API const char *bis_mat_ilu0_kernel(const bis_mat *L_strict);
 
+/* Factorized sparse approximate inverse (FSAI, Kolotilina-Yeremin) on the pattern of tril(A); no reference counterpart.
+ * Only the entries of A with column <= row are read; the result is the FSAI of the symmetric matrix they define.  For row
+ * i let J be the columns <= i of row i in ascending order (the last one is i, |J| = m <= 64) and S = A[J,J], S[p,q]
+ * (q <= p) taken from row J[p], column J[q], an absent entry counting as 0.  With S = C C^T (Cholesky, fp64) row i of G on
+ * the columns J is g = C^-T e_m (one back substitution on the last unit vector; g = y / sqrt(y_m) for S y = e_m), so that
+ * diag(G A G^T) = 1 and M^-1 = G^T G is symmetric positive definite.  A row one of whose pivots is <= 0 or not finite
+ * becomes e_i / sqrt(|a_ii|) (on the same pattern, the other entries 0) and counts in *n_fallback_rows (may be NULL).
+ * G is lower triangular with its diagonal and Gt = G^T upper triangular; both are ordinary matrices with ascending
+ * columns and A's row-pointer width, without a grid hint: bis_spmv / bis_spmm apply them, BIS_PC_FSAI takes G as L_strict
+ * and Gt as U_strict.  The rows are independent (one wave each, fsai_rows_kernel) and nothing is accumulated with
+ * floating-point atomics: two calls give the same bits, whatever the order of the entries inside A's rows.
+ * BIS_ERR_INVALID: null arguments, A not square or a row-range view; BIS_ERR_ZERO_DIAG: a row without a diagonal entry
+ * or with a_ii = 0; BIS_ERR_UNSUPPORTED: more than 64 entries left of and on the diagonal of a row, a column repeated
+ * inside a row, a pattern that is not structurally symmetric.  *G and *Gt are written on success only.  n = 0: BIS_OK.
+ * Blocking.  bis_mat_fsai_kernel: the instance that computed G, "fsai_rows_kernel M=32 RP=32" (M = 16, 32 or 64 by the
+ * longest lower row; static string, "" for any other matrix). */
+BIS_API bis_status bis_mat_fsai(bis_ctx *ctx, const bis_mat *A, bis_mat **G, bis_mat **Gt, int64_t *n_fallback_rows);
+BIS_API const char *bis_mat_fsai_kernel(const bis_mat *G);
+
 /* ---- the operator surface (kernels.hpp) ------------------------------------ */
 /* spmv / native_spmv, kernels.hpp:22-52: y = A x. */
 BIS_API bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x,
@@ -489,7 +510,10 @@ BIS_API const char *bis_itrsv_kernel(const bis_mat *T_strict);
  * A_D_inv argument carries 1 / U_D (bis_elemwise_div_vectors(A_D_inv, L_D, U_D) after bis_mat_ilu0); A_D and U_D are
  * not read.  Scratch: tmp holds the lower solve's result and work (n entries, as for the two-stage types) is the
  * alternate buffer of both solves; the steps finish in place, so no third buffer is needed.  tmp and work must be
- * distinct from each other and from output and input (BIS_ERR_INVALID); output may alias input. */
+ * distinct from each other and from output and input (BIS_ERR_INVALID); output may alias input.
+ * BIS_PC_FSAI (9): tmp = bis_spmv(L_strict, input), then output = bis_spmv(U_strict, tmp), with G in the L_strict and Gt
+ * in the U_strict argument (bis_mat_fsai).  The diagonal arguments and work are not read; tmp is required and must be
+ * distinct from input and output (BIS_ERR_INVALID); output may alias input. */
 BIS_API bis_status bis_apply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
@@ -537,7 +561,9 @@ BIS_API bis_status bis_mitrsv(bis_ctx *ctx, const bis_mat *T_strict, const doubl
  * sweep, SGS sweep + bis_mvec_mul_diag + sweep, ILU0 two sweeps, ILU0_ITER two bis_mitrsv (scratch and alias rules of the
  * single-vector case; OUT may alias IN).  Column j equals bis_apply_preconditioner on column j bit for bit (the sweeps:
  * with bis_sptrsm's proviso; ILU0_ITER: with bis_mitrsv's).  BIS_PC_TWO_STAGE_GS, BIS_PC_SYMMETRIC_TWO_STAGE_GS and outer_iters != 1:
- * BIS_ERR_UNSUPPORTED.  TMP, WORK: n x n_rhs blocks, needed by SGS / ILU0 / ILU0_ITER (TMP) and ILU0_ITER (WORK). */
+ * BIS_ERR_UNSUPPORTED.  TMP, WORK: n x n_rhs blocks, needed by SGS / ILU0 / ILU0_ITER / FSAI (TMP) and ILU0_ITER (WORK).
+ * FSAI: two bis_spmm, TMP distinct from IN and OUT; column j equals the single-vector apply wherever bis_spmm's column j
+ * equals bis_spmv's (every matrix that does not run the wave-per-row SpMV). */
 BIS_API bis_status bis_mapply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, int n_rhs, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
@@ -619,7 +645,9 @@ BIS_API bis_status bis_cg_destroy(bis_ctx *ctx, bis_cg *cg);
  * z = M^-1 r through bis_apply_preconditioner (kernels.hpp:336-414) with the
  * given operands (all LOCAL to this rank), instead of None / Jacobi.  Pass B
  * then updates r and (r,r) only; the sweep(s) and a stream-ordered (r,z) follow;
- * everything stays on the device as before.  Call before bis_cg_init. */
+ * everything stays on the device as before.  Call before bis_cg_init.
+ * BIS_PC_FSAI needs the two factors (G, Gt of bis_mat_fsai, of this rank's diagonal block on a distributed handle) and
+ * nothing else: no diagonals, no work vector. */
 BIS_API bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                              const bis_mat *L_strict, const bis_mat *U_strict,
                                              const double *A_D, const double *A_D_inv,
@@ -663,7 +691,8 @@ BIS_API bis_status bis_mcg_create(bis_ctx *ctx, const bis_mat *A, const double *
  * updates R and (r,r) only; the apply, the k sums (r_j, z_j) with the per-column bookkeeping, and pass C follow.  The
  * handle owns the Z, TMP and WORK blocks the type needs.  Call before bis_mcg_init: BIS_ERR_INVALID afterwards; the
  * two-stage types and outer_iters != 1: BIS_ERR_UNSUPPORTED.  A stopped column stays frozen as without the call (the
- * apply may still compute its z, which nothing reads). */
+ * apply may still compute its z, which nothing reads).  BIS_PC_FSAI (also in bis_mbicgstab_set_preconditioner and
+ * bis_mgmres_set_preconditioner): the two factors and the TMP block, no diagonals and no WORK. */
 BIS_API bis_status bis_mcg_set_preconditioner(bis_ctx *ctx, bis_mcg *m, int precond_type,
                                               const bis_mat *L_strict, const bis_mat *U_strict,
                                               const double *A_D, const double *A_D_inv,
