@@ -525,6 +525,13 @@ class Mat:
         "itrsv spmv+epilogue form=F"."""
         return self.ctx.lib.bis_itrsv_kernel(self.h).decode()
 
+    def round_f32(self):
+        """Round every value to fp32 in place in the fp64 CRS array and flag the matrix fp32-exact (bis_mat_round_f32): its SpMV
+        may then stream 4-byte values (form 8).  Returns the largest relative change of a value."""
+        m = C.c_double()
+        self.ctx.check(self.ctx.lib.bis_mat_round_f32(self.ctx.h, self.h, C.byref(m)))
+        return m.value
+
     def retune(self):
         """Rebuild everything derived from the CRS arrays (bis_mat_retune): required after writing values in place."""
         self.ctx.check(self.ctx.lib.bis_mat_retune(self.ctx.h, self.h))

@@ -125,6 +125,7 @@ struct bis_options {
     int spmv_win8_depth = -1;  // ... chunks requested ahead per lane: 1, 2, 3, 4 or 6 (default by block size)
     int spmv_win8_implicit = -1; // ... implied window slots in the slices of a stencil (0: every chunk keeps its slots; default on where >= half the chunks qualify)
     int spmv_win8_tune = -1;   // ... placement tuning of the stream at build time: up to k re-allocations, the fastest kept (default 12 for streams of >= 1 GiB; 0 off)
+    int spmv_win4 = -1;        // ... the same form with 4-byte values for a matrix that bis_mat_round_f32 flagged ("win4"): 0 off (such a matrix then streams win8), -1: default = on
     int spmv_sellwin_masks = -1; // 0: never the per-row pair masks (fmt 4: 4 bytes per ROW where the matrix has at most 32 (column - row, value) pairs)
     int device_share = -1;  // k > 1: this device is shared by k processes that all run persistent grids (several ranks on one GPU in a test
                             // or rehearsal): kernels that need their whole grid resident keep to 1/k of the device
@@ -204,6 +205,12 @@ struct bis_mat {
     int cs_state = 0;
     double cs_trial_ms[2] = {0.0, 0.0};        // the build-time trial: one pass / the K passes
     int sw8_state = 0;
+    // ... and with 4-byte values ("win4"), built only while f32_exact holds; state as above
+    struct bis_sellwin *sw4 = nullptr;
+    int sw4_state = 0;
+    // every value of val is exactly representable in binary32: set by bis_mat_round_f32, cleared by bis_mat_scale_sym and
+    // bis_mat_retune, inherited by row views (bis_mat_row_view) and by nothing else
+    bool f32_exact = false;
     // second table for the SpMV with the fused (y,w) epilogue (CG): larger blocks win there
     int32_t *blkf_row = nullptr;
     int64_t *blkf_nnz = nullptr;
@@ -395,23 +402,25 @@ bis_status bis_spmv_sellwin_launch(bis_ctx *ctx, const bis_mat *A, const double 
                                    double *partials, const int *stop, int remap_arg, int grid);
 void bis_spmv_sellwin_drop(bis_mat *A);
 // window + sliced-ELL form with the 8-byte values streamed (bis_spmv_sell.hip, "win8")
-bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A);
-int bis_spmv_win8_blocks(const bis_mat *A);
-int bis_spmv_win8_rows(const bis_mat *A);
-int64_t bis_spmv_win8_bytes(const bis_mat *A);
+// vb: bytes per streamed value -- 8, or 4 for the stream of a matrix flagged f32_exact ("win4", A->sw4); one code path
+bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A, int vb = 8);
+int bis_spmv_win8_blocks(const bis_mat *A, int vb = 8);
+int bis_spmv_win8_rows(const bis_mat *A, int vb = 8);
+int64_t bis_spmv_win8_bytes(const bis_mat *A, int vb = 8);
 bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x, double *y, int mode, const double *w,
-                                double *partials, const int *stop, int remap_arg, int grid);
-void bis_spmv_win8_drop(bis_mat *A);
+                                double *partials, const int *stop, int remap_arg, int grid, int vb = 8);
+void bis_spmv_win8_drop(bis_mat *A); // both streams
+int bis_spmv_win8_active(const bis_mat *A); // 4 where the 4-byte stream is built and the flag and options still select it, else 8
 bis_status bis_spmv_colslab_build(bis_ctx *ctx, const bis_mat *A, int K, std::vector<bis_mat *> &slabs, bool *ok);
 void bis_spmv_colslab_free(bis_ctx *ctx, std::vector<bis_mat *> &slabs);
 void bis_spmv_colslab_drop(bis_mat *A);
 int bis_spmv_remap_arg(int nb);
 int bis_spmv_grid(int nb);
-size_t bis_spmv_win8_stream_bytes(const bis_mat *A);
-bool bis_spmv_win8_implied(const bis_mat *A);         // the implied-slot layout was built
-double bis_spmv_win8_moved_bytes(const bis_mat *A);  // bytes a launch moves: the form's arrays, the windows' x granules, y
-bool bis_spmv_win8_fast(const bis_mat *A, double ms); // a launch of ms runs at the stream placement's fast level
-void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream); // returns the buffer that was in use
+size_t bis_spmv_win8_stream_bytes(const bis_mat *A, int vb = 8);
+bool bis_spmv_win8_implied(const bis_mat *A, int vb = 8);         // the implied-slot layout was built
+double bis_spmv_win8_moved_bytes(const bis_mat *A, int vb = 8);  // bytes a launch moves: the form's arrays, the windows' x granules, y
+bool bis_spmv_win8_fast(const bis_mat *A, double ms, int vb = 8); // a launch of ms runs at the stream placement's fast level
+void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream, int vb = 8); // returns the buffer that was in use
 // try to build the packed-column stream of table t (0 plain, 1 fused); A->pk_state[t] tells the outcome
 bis_status bis_spmv_try_pack(bis_ctx *ctx, bis_mat *A, int t);
 // free row-block tables, packed streams and window structures (not the CRS arrays)

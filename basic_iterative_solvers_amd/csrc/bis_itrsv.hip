@@ -9,7 +9,7 @@
 //
 // Two paths per step, chosen by the form the SpMV of T resolves to (bis_spmv.hip, spmv_resolve):
 //   * CRS-value row-block kernel: the step is that kernel's epilogue (MODE 3) -- T x_k is never written and read back;
-//   * every other form (dictionary forms, win8, column slabs, x-window, wave-per-row): the SpMV runs as it is into the
+//   * every other form (dictionary forms, win8 / win4, column slabs, x-window, wave-per-row): the SpMV runs as it is into the
 //     buffer x_{k+1} will occupy, and itrsv_epilogue_kernel finishes the step there in place: 32 B per row read, 8 written.
 // The row sum is bis_spmv's in both, the subtraction and the multiplication are rounded separately in both: the paths
 // agree bit for bit with each other and with bis_spmv followed by (b - y) * D_inv.
@@ -68,10 +68,10 @@ bis_status launch_epilogue(bis_ctx *ctx, double *x, const double *b, const doubl
 const char *epilogue_name(int form) {
     static const std::vector<std::string> names = [] {
         std::vector<std::string> v;
-        for (int f = 0; f <= 7; ++f) v.push_back("itrsv spmv+epilogue form=" + std::to_string(f));
+        for (int f = 0; f <= 8; ++f) v.push_back("itrsv spmv+epilogue form=" + std::to_string(f));
         return v;
     }();
-    return names[(size_t)std::max(0, std::min(form, 7))].c_str();
+    return names[(size_t)std::max(0, std::min(form, 8))].c_str();
 }
 
 } // namespace

@@ -496,6 +496,7 @@ bis_status bis_mat_row_view(bis_ctx *ctx, const bis_mat *A, int64_t ra, int64_t 
     V->row_ptr = (char *)A->row_ptr + w * ra;
     V->col = A->col;
     V->val = A->val;
+    V->f32_exact = A->f32_exact; // (the view streams the same values)
     bis_status st = bis_mat_finalize(ctx, V);
     if (st != BIS_OK) { delete V; return st; }
     *out = V;
@@ -661,6 +662,7 @@ BIS_API bis_status bis_mat_retune(bis_ctx *ctx, bis_mat *A) {
     BIS_REQUIRE(ctx, A, "bis_mat_retune: null matrix");
     BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     bis_mat_values_changed(A); // (the tuning tools may also have written the arrays through bis_mat_debug_ptrs)
+    A->f32_exact = false;      // ... so nothing is known about the values any more: the caller rounds again (bis_mat_round_f32)
     return bis_mat_finalize(ctx, A);
 }
 
@@ -715,23 +717,26 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
     // stream in fresh allocations, the earlier ones held so that the next lands elsewhere; the search ends at the first
     // candidate of the fast level (bis_spmv_win8_fast; the library runs the same search by itself when it builds the
     // stream -- bis_spmv_sell.hip w8_tune_placement -- so this normally finds the fast level in place).
-    if (st == BIS_OK && A->sw8_state == 1 && bis_spmv_win8_stream_bytes(A) > 0) {
+    // The 4-byte stream of a matrix flagged fp32-exact (form 8) is searched the same way, priced on its own bytes.
+    if (st == BIS_OK && (A->sw8_state == 1 || A->sw4_state == 1)) {
         int w8_form = 0;
-        if (bis_mat_spmv_stream_info(ctx, A, nullptr, nullptr, nullptr, &w8_form) == BIS_OK && w8_form == 6) {
-            const size_t bytes = bis_spmv_win8_stream_bytes(A);
+        if (bis_mat_spmv_stream_info(ctx, A, nullptr, nullptr, nullptr, &w8_form) == BIS_OK && (w8_form == 6 || w8_form == 8) &&
+            bis_spmv_win8_stream_bytes(A, w8_form == 8 ? 4 : 8) > 0) {
+            const int vb = w8_form == 8 ? 4 : 8;
+            const size_t bytes = bis_spmv_win8_stream_bytes(A, vb);
             std::vector<void *> losers;
-            auto fast_enough = [&](double ms) { return bis_spmv_win8_fast(A, ms); };
+            auto fast_enough = [&](double ms) { return bis_spmv_win8_fast(A, ms, vb); };
             for (int trial = 0; st == BIS_OK && trial < max_trials && !fast_enough(best); ++trial) {
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)4 << 30)) break; // keep 4 GiB for the caller
                 void *cand = nullptr;
                 if (hipMalloc(&cand, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-                void *cur = bis_spmv_win8_swap_stream(A, cand);
+                void *cur = bis_spmv_win8_swap_stream(A, cand, vb);
                 hipMemcpyAsync(cand, cur, bytes, hipMemcpyDeviceToDevice, ctx->stream);
                 double ms = 0.0;
                 st = measure(ms);
                 if (st == BIS_OK && ms < best) { best = ms; losers.push_back(cur); }
-                else { bis_spmv_win8_swap_stream(A, cur); losers.push_back(cand); }
+                else { bis_spmv_win8_swap_stream(A, cur, vb); losers.push_back(cand); }
             }
             hipStreamSynchronize(ctx->stream);
             for (void *l : losers) hipFree(l);

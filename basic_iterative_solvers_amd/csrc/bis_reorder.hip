@@ -374,6 +374,7 @@ bis_status bis_mat_scale_sym(bis_ctx *ctx, bis_mat *A, double *scale) {
     if (n == 0) return BIS_OK;
     BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); // sweeps in flight still read the plans dropped next
     bis_mat_values_changed(A); // the values change in place
+    A->f32_exact = false;      // ... and are no longer the binary32 values bis_mat_round_f32 left
     unsigned long long *status = (unsigned long long *)(ctx->scalars_dev + 32);
     BIS_HIP_CHECK(ctx, hipMemsetAsync(status, 0xFF, 8, ctx->stream));
     const unsigned grid = (unsigned)((n + 255) / 256);

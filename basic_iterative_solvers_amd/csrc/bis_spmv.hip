@@ -48,6 +48,9 @@
 //     public 4 / 5                   spmv_sellwin != 0, the plan applies; plain, fused      3: 1 B; 4: 4 B per ROW
 //   rowmajor (spmv_rowmajor_vd_      dictionary, lane per row, default variant, rows <= 40  3 B                       4 per 256 rows
 //     kernel), public 2 / 3          entries, <= 8 (32) column windows per 256 rows; all
+//   win4 ("win4 rows=R"), public 8   no dictionary, the matrix is flagged fp32-exact        6 B (4 B + a descriptor   4 per block of 256 R rows
+//                                    (bis_mat_round_f32), spmv_win4 != 0, spmv_win8 != 0,   per chunk: implied slots)
+//                                    default variant, the plan applies; plain, fused
 //   win8 ("win8 rows=R"), public 6   no dictionary, spmv_win8 != 0, default variant, the    10 B (8 B + a descriptor  4 per block of 256 R rows
 //                                    plan applies (<= 12 % padding); plain, fused           per chunk: implied slots)
 //   colslab ("colslab K=k"),         no dictionary, < 2^29 columns, spmv_colslab != 0,      12 B (10 B where every    4 per block of the last
@@ -1003,12 +1006,13 @@ const char *rowblock_name(int id, const SpmvArgs &a) {
     return names[(size_t)(u * 5 + pk) * 3 + br].c_str();
 }
 
-// "sellwin fmt=F", "win8 rows=R", "colslab K=k" (F 0..4, R 1..4, k up to 32)
+// "sellwin fmt=F", "win8 rows=R", "colslab K=k", "win4 rows=R" (F 0..4, R 1..4, k up to 32)
 const char *form_name(int kind, int v) {
-    static const std::vector<std::string> names[3] = {
+    static const std::vector<std::string> names[4] = {
         [] { std::vector<std::string> n; for (int i = 0; i <= 4; ++i) n.push_back("sellwin fmt=" + std::to_string(i)); return n; }(),
         [] { std::vector<std::string> n; for (int i = 0; i <= 4; ++i) n.push_back("win8 rows=" + std::to_string(i)); return n; }(),
-        [] { std::vector<std::string> n; for (int i = 0; i <= 32; ++i) n.push_back("colslab K=" + std::to_string(i)); return n; }()};
+        [] { std::vector<std::string> n; for (int i = 0; i <= 32; ++i) n.push_back("colslab K=" + std::to_string(i)); return n; }(),
+        [] { std::vector<std::string> n; for (int i = 0; i <= 4; ++i) n.push_back("win4 rows=" + std::to_string(i)); return n; }()};
     const std::vector<std::string> &t = names[kind];
     return t[(size_t)std::max(0, std::min(v, (int)t.size() - 1))].c_str();
 }
@@ -1310,7 +1314,7 @@ int bis_spmv_grid(int nb) { return grid_for_map(nb, remap_arg_for((nb + 7) & ~7)
 
 // ---- the form of a matrix' SpMV: resolved in ONE place (the table in the file header); launches and reports read the plan ----
 
-enum SpmvForm { kFormLongRows, kFormWindow, kFormSellwin, kFormRowmajor, kFormWin8, kFormColslab, kFormRowblockVd, kFormRowblock };
+enum SpmvForm { kFormLongRows, kFormWindow, kFormSellwin, kFormRowmajor, kFormWin4, kFormWin8, kFormColslab, kFormRowblockVd, kFormRowblock };
 
 struct SpmvPlan {
     SpmvForm form = kFormRowblock;
@@ -1474,6 +1478,17 @@ static bis_status spmv_resolve(bis_ctx *ctx, const bis_mat *A_c, int mode, SpmvP
             }
         }
         // (a matrix with a value dictionary keeps its dictionary kernels: 3 bytes per non-zero)
+        // (win4: only a matrix that bis_mat_round_f32 flagged; where the plan does not apply -- it is win8's -- the successors follow)
+        if (mode != 2 && !a.vcode && A->f32_exact && bis_opts().spmv_win4 != 0 && bis_opts().spmv_win8 != 0 && (v < 0 || v == 20)) {
+            if (bis_status st = bis_spmv_win8_try(ctx, A, 4)) return st;
+            if (const int nb = bis_spmv_win8_blocks(A, 4)) {
+                block_map(nb);
+                p->form = kFormWin4;
+                p->n_partials = mode == 1 ? nb * 4 : 0; // one per wave
+                p->name = form_name(3, bis_spmv_win8_rows(A, 4));
+                return BIS_OK;
+            }
+        }
         if (mode != 2 && !a.vcode && bis_opts().spmv_win8 != 0 && (v < 0 || v == 20)) {
             if (bis_status st = bis_spmv_win8_try(ctx, A)) return st;
             if (const int nb = bis_spmv_win8_blocks(A)) {
@@ -1532,6 +1547,8 @@ static bis_status spmv_launch_plan(bis_ctx *ctx, const bis_mat *A, const SpmvPla
     }
     case kFormSellwin:
         return bis_spmv_sellwin_launch(ctx, A, a.x, a.y, a.mode, a.w, a.partials, a.stop, a.remap_arg, a.grid);
+    case kFormWin4:
+        return bis_spmv_win8_launch(ctx, A, a.x, a.y, a.mode, a.w, a.partials, a.stop, a.remap_arg, a.grid, 4);
     case kFormWin8:
         return bis_spmv_win8_launch(ctx, A, a.x, a.y, a.mode, a.w, a.partials, a.stop, a.remap_arg, a.grid);
     case kFormRowmajor: {
@@ -1564,7 +1581,7 @@ static bis_status spmv_launch_plan(bis_ctx *ctx, const bis_mat *A, const SpmvPla
 // Upper bound on the partials one fused SpMV of A writes, over every form spmv_resolve can choose -- from the matrix' shape
 // and block tables alone, so that it holds before any form is built.  Row-block kernel: one per wave of a block of the fused
 // table (4; the 16 dates from workgroups of up to 1024 threads and is kept); x-window kernel: 4 per block of the plain table.
-// The forms on blocks of kSwRows R rows, R = 1, 2, 4 (lane-per-row dictionary: R = 1, 4 per block; win8: 4 per block; sellwin:
+// The forms on blocks of kSwRows R rows, R = 1, 2, 4 (lane-per-row dictionary: R = 1, 4 per block; win8 / win4: 4 per block; sellwin:
 // one per slice of kSwRows / 4 rows) write at most ceil(n / (kSwRows R)) 4 R <= n / (kSwRows / 4) + 4 kSwMaxR.  The slabs'
 // last pass runs on a table of no more blocks than A's own.
 size_t bis_spmv_partials_bound(const bis_mat *A) {
@@ -1627,7 +1644,7 @@ bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x, double *y) 
 // What the plain SpMV of A streams: the plan's form (and sellwin format) -> col_bytes, val_bytes, n_dict and the public form
 // number (include/bis_hip.h).  sellwin's formats: 0, 1 a 2-byte window slot and a 1-byte value code per non-zero; 2 one 16-bit
 // code (slot : 13 | value index : 3); 3 one byte, the index of the non-zero's (column - row, value) pair; 4 a 32-bit mask of
-// pairs per ROW.  win8 keeps col_bytes 2 also with implied slots (bis_mat_win8_layout tells the layouts apart).
+// pairs per ROW.  win8 and win4 keep col_bytes 2 also with implied slots (bis_mat_win8_layout tells the layouts apart).
 struct SpmvReport { int col_bytes, val_bytes, n_dict, form; };
 
 static bis_status spmv_report(bis_ctx *ctx, const bis_mat *A, SpmvPlan *p, SpmvReport *r) {
@@ -1644,6 +1661,7 @@ static bis_status spmv_report(bis_ctx *ctx, const bis_mat *A, SpmvPlan *p, SpmvR
         *r = {col_val[fmt][0], col_val[fmt][1], A->vd_n, A->vd_diag ? 5 : 4};
         break;
     }
+    case kFormWin4: *r = {2, 4, 0, 8}; break;
     case kFormWin8: *r = {2, 8, 0, 6}; break;
     case kFormColslab: {
         bool all_packed = true;
@@ -1662,7 +1680,7 @@ static bis_status spmv_report(bis_ctx *ctx, const bis_mat *A, SpmvPlan *p, SpmvR
 // internal (bis_itrsv.hip): one step x_new = (b - T x_old) * D_inv of the iterative triangular solve.  Where the plain SpMV
 // of T resolves to the CRS-value row-block kernel, that kernel runs with the step as its epilogue (MODE 3: the product is
 // never written and read back) and *form = -1; every other form -- the wave-per-row and x-window kernels, the dictionary
-// forms, win8, column slabs -- runs as it is, T x_old into x_new, *form = its public number (bis_mat_spmv_stream_info), and
+// forms, win8 / win4, column slabs -- runs as it is, T x_old into x_new, *form = its public number (bis_mat_spmv_stream_info), and
 // the caller's epilogue kernel finishes the step in place.
 bis_status bis_spmv_itrsv_step(bis_ctx *ctx, const bis_mat *T, const double *x_old, double *x_new, const double *b,
                                const double *D_inv, int *form) {
@@ -1716,6 +1734,7 @@ bis_status bis_mat_spmv_streamed_bytes(bis_ctx *ctx, const bis_mat *A, int64_t *
     case kFormRowblockVd: b += rowblock_bytes(A) + 2048; break;
     case kFormRowmajor: b += 3 * A->nnz + rp * (A->n_rows + 1) + (int64_t)A->rm_blocks * (A->rm_kind == 3 ? 128 : 32) + 2048; break;
     case kFormSellwin: b += bis_spmv_sellwin_bytes(A); break;
+    case kFormWin4: b += bis_spmv_win8_bytes(A, 4); break;
     case kFormWin8: b += bis_spmv_win8_bytes(A); break;
     case kFormColslab: // the slabs' CRS copies, and y read and written again by every pass after the first
         for (const bis_mat *B : *A->colslabs) b += rowblock_bytes(B);

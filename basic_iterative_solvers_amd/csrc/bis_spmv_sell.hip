@@ -68,6 +68,7 @@ struct bis_sellwin {
     int tune_trials = 0;             // win8: placement tuning at build time (re-allocations tried), the kernel's time on the first
     double tune_first_ms = 0.0, tune_kept_ms = 0.0; // allocation and on the one kept
     int R = 1;                       // rows per lane: a block is 256 R rows
+    int vb = 8;                      // win8: bytes per streamed value (4: the float stream of a matrix whose values are exact in binary32, "win4")
     bool diag = false;               // one value code stands for the row's own diagonal value (vdiag)
     int pad_idx = 0, diag_idx = 0;
 };
@@ -1260,7 +1261,12 @@ namespace {
 
 constexpr int kW8ChunkBytes = 2560;
 constexpr int kW8ValBytes = 2048; // a chunk of the implied-slot layout: its values only
-
+// win4: the same chunks with 4-byte values (VT = float): [64 x 4 slots][64 x 4 floats] = 1536 bytes, 1024 with implied slots
+template <typename VT> constexpr int w8_chunk_bytes() { return 512 + 256 * (int)sizeof(VT); }
+template <typename VT> constexpr int w8_val_bytes() { return 256 * (int)sizeof(VT); }
+static_assert(w8_chunk_bytes<double>() == kW8ChunkBytes && w8_val_bytes<double>() == kW8ValBytes, "the 8-byte stream's chunk sizes");
+inline size_t w8_chunk_bytes(int vb) { return 512 + 256 * (size_t)vb; }
+inline size_t w8_val_bytes(int vb) { return 256 * (size_t)vb; }
 
 constexpr int kW8Runs = 64;     // runs of the window per block at most (header: 2 x 64 words)
 constexpr int kW8GapMerge = 4;  // runs at most this many granules apart become one (the gap's x entries are copied too)
@@ -1420,7 +1426,9 @@ __global__ __launch_bounds__(256) void w8_plan_kernel(const RP *__restrict__ row
 // PHASE 2 (slice_rec = the exclusive scan of PHASE 1): the implied-slot layout, 2048-byte chunks of values only; an implicit slice's
 // chunk keeps its 4 slot bases (16 bits each, the lane's 8 (row - block_row0) is added modulo 2^16 by the kernel; 1 = a padding
 // entry, slot 0 in every lane) in desc[chunk], an explicit slice's chunk keeps its 512 bytes of slots in side[slice_rec[s] + k].
-template <typename RP, int PHASE>
+// VT = float (win4): the values are written as binary32, one 16-byte store of a lane's four -- exact on a matrix that
+// bis_mat_round_f32 flagged, the only ones that get this stream; the padding value is 1.0f.
+template <typename RP, int PHASE, typename VT = double>
 __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row_ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
                                                       int64_t n_rows, int R, const int32_t *__restrict__ hdr,
                                                       const int64_t *__restrict__ slice_chunk0, const uint16_t *__restrict__ row_of,
@@ -1482,14 +1490,22 @@ __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row
                 for (int q = 0; q < 4; ++q)
                     if (__ballot(base[q] != (unsigned)__builtin_amdgcn_readfirstlane((int)base[q])) != 0ull) implicit = false;
             } else if (PHASE == 0) {
-                unsigned char *p = stream + (size_t)(c0 + c) * kW8ChunkBytes;
+                unsigned char *p = stream + (size_t)(c0 + c) * w8_chunk_bytes<VT>();
                 *reinterpret_cast<uint2 *>(p + lane * 8) = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
-                *reinterpret_cast<double2 *>(p + 512 + lane * 16) = make_double2(vv[0], vv[1]);
-                *reinterpret_cast<double2 *>(p + 1536 + lane * 16) = make_double2(vv[2], vv[3]);
+                if constexpr (sizeof(VT) == 4) {
+                    *reinterpret_cast<float4 *>(p + 512 + lane * 16) = make_float4((float)vv[0], (float)vv[1], (float)vv[2], (float)vv[3]);
+                } else {
+                    *reinterpret_cast<double2 *>(p + 512 + lane * 16) = make_double2(vv[0], vv[1]);
+                    *reinterpret_cast<double2 *>(p + 1536 + lane * 16) = make_double2(vv[2], vv[3]);
+                }
             } else {
-                unsigned char *p = stream + (size_t)(c0 + c) * kW8ValBytes;
-                *reinterpret_cast<double2 *>(p + lane * 16) = make_double2(vv[0], vv[1]);
-                *reinterpret_cast<double2 *>(p + 1024 + lane * 16) = make_double2(vv[2], vv[3]);
+                unsigned char *p = stream + (size_t)(c0 + c) * w8_val_bytes<VT>();
+                if constexpr (sizeof(VT) == 4) {
+                    *reinterpret_cast<float4 *>(p + lane * 16) = make_float4((float)vv[0], (float)vv[1], (float)vv[2], (float)vv[3]);
+                } else {
+                    *reinterpret_cast<double2 *>(p + lane * 16) = make_double2(vv[0], vv[1]);
+                    *reinterpret_cast<double2 *>(p + 1024 + lane * 16) = make_double2(vv[2], vv[3]);
+                }
                 if (!implicit) *reinterpret_cast<uint2 *>(side + (size_t)(slice_rec[slice] + c) * 512 + lane * 8) = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
                 else if (lane == 0) desc[c0 + c] = make_uint2(base[0] | base[1] << 16, base[2] | base[3] << 16);
             }
@@ -1500,23 +1516,35 @@ __global__ __launch_bounds__(256) void w8_fill_kernel(const RP *__restrict__ row
 
 typedef double w8_v2d __attribute__((ext_vector_type(2)));
 typedef unsigned w8_v2u __attribute__((ext_vector_type(2)));
-struct W8Chunk { w8_v2u code; w8_v2d v0, v1; };
+typedef float w8_v4f __attribute__((ext_vector_type(4)));
+template <typename VT> struct W8Chunk { w8_v2u code; w8_v2d v0, v1; };
+template <> struct W8Chunk<float> { w8_v2u code; w8_v4f v; }; // win4: a lane's four values are ONE 16-byte load
 
-// one chunk of the stream for this lane: three non-temporal loads (the stream is read once per product)
-__device__ __forceinline__ W8Chunk w8_load(const unsigned char *__restrict__ stream, int64_t c, int lane) {
-    const unsigned char *p = stream + (size_t)c * kW8ChunkBytes;
-    W8Chunk ch;
+// one chunk of the stream for this lane: three non-temporal loads (the stream is read once per product); win4: two
+template <typename VT>
+__device__ __forceinline__ W8Chunk<VT> w8_load(const unsigned char *__restrict__ stream, int64_t c, int lane) {
+    const unsigned char *p = stream + (size_t)c * w8_chunk_bytes<VT>();
+    W8Chunk<VT> ch;
     ch.code = __builtin_nontemporal_load(reinterpret_cast<const w8_v2u *>(p + lane * 8));
-    ch.v0 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 512 + lane * 16));
-    ch.v1 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 1536 + lane * 16));
+    if constexpr (sizeof(VT) == 4) {
+        ch.v = __builtin_nontemporal_load(reinterpret_cast<const w8_v4f *>(p + 512 + lane * 16));
+    } else {
+        ch.v0 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 512 + lane * 16));
+        ch.v1 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 1536 + lane * 16));
+    }
     return ch;
 }
 
-// the implied-slot layout: a chunk's values (two non-temporal loads per lane, as above); its slots are loaded by the kernel
-__device__ __forceinline__ void w8_load_values(const unsigned char *__restrict__ stream, int64_t c, int lane, W8Chunk &ch) {
-    const unsigned char *p = stream + (size_t)c * kW8ValBytes;
-    ch.v0 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + lane * 16));
-    ch.v1 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 1024 + lane * 16));
+// the implied-slot layout: a chunk's values (two non-temporal loads per lane, as above; win4: one); its slots are loaded by the kernel
+template <typename VT>
+__device__ __forceinline__ void w8_load_values(const unsigned char *__restrict__ stream, int64_t c, int lane, W8Chunk<VT> &ch) {
+    const unsigned char *p = stream + (size_t)c * w8_val_bytes<VT>();
+    if constexpr (sizeof(VT) == 4) {
+        ch.v = __builtin_nontemporal_load(reinterpret_cast<const w8_v4f *>(p + lane * 16));
+    } else {
+        ch.v0 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + lane * 16));
+        ch.v1 = __builtin_nontemporal_load(reinterpret_cast<const w8_v2d *>(p + 1024 + lane * 16));
+    }
 }
 
 // the slots of a chunk of the implied-slot layout: code = 4 x 16-bit bases, off2 = (8 (row - block_row0)) x 0x10001 in an implicit
@@ -1528,13 +1556,26 @@ __device__ __forceinline__ unsigned w8_imply(unsigned code, unsigned off2) {
 }
 
 // acc += v_q * window[slot_q], q = 0..3, products and sums rounded separately (the CRS kernels' arithmetic)
-__device__ __forceinline__ void w8_consume(const unsigned char *win, const W8Chunk &ch, double &acc) {
+__device__ __forceinline__ void w8_consume(const unsigned char *win, const W8Chunk<double> &ch, double &acc) {
 #pragma clang fp contract(off)
     const double x0 = *reinterpret_cast<const double *>(win + (ch.code.x & 0xffffu));
     const double x1 = *reinterpret_cast<const double *>(win + (ch.code.x >> 16));
     const double x2 = *reinterpret_cast<const double *>(win + (ch.code.y & 0xffffu));
     const double x3 = *reinterpret_cast<const double *>(win + (ch.code.y >> 16));
     const double p0 = ch.v0.x * x0, p1 = ch.v0.y * x1, p2 = ch.v1.x * x2, p3 = ch.v1.y * x3;
+    acc = acc + p0;
+    acc = acc + p1;
+    acc = acc + p2;
+    acc = acc + p3;
+}
+// win4: the float is widened first (exact), so each product is the one of the fp64 CRS value the float was made from
+__device__ __forceinline__ void w8_consume(const unsigned char *win, const W8Chunk<float> &ch, double &acc) {
+#pragma clang fp contract(off)
+    const double x0 = *reinterpret_cast<const double *>(win + (ch.code.x & 0xffffu));
+    const double x1 = *reinterpret_cast<const double *>(win + (ch.code.x >> 16));
+    const double x2 = *reinterpret_cast<const double *>(win + (ch.code.y & 0xffffu));
+    const double x3 = *reinterpret_cast<const double *>(win + (ch.code.y >> 16));
+    const double p0 = (double)ch.v.x * x0, p1 = (double)ch.v.y * x1, p2 = (double)ch.v.z * x2, p3 = (double)ch.v.w * x3;
     acc = acc + p0;
     acc = acc + p1;
     acc = acc + p2;
@@ -1548,7 +1589,8 @@ __device__ __forceinline__ void w8_consume(const unsigned char *win, const W8Chu
 // the window is (they do not need it).  LDS: 16 bytes (the -0.0 slot), then the window.
 // IMPL: the implied-slot layout (w8_fill_kernel PHASE 2): a chunk's 8 slot bytes per lane come from desc[chunk] (the same 8 bytes
 // for every lane: implicit slice) or from its record in side (explicit slice), chosen per chunk by its slice (wave-uniform).
-template <int MODE, int R, int D, bool IMPL>
+// VT: the stream's value type, double, or float for win4 (chunks of 1536 / 1024 bytes, everything else the same).
+template <int MODE, int R, int D, bool IMPL, typename VT = double>
 __global__ __launch_bounds__(256) void spmv_win8_kernel(
     const double *x, double *__restrict__ y, int64_t n_rows, int64_t n_cols, int n_blocks, int remap_arg, const double *w,
     double *__restrict__ partials, const int *stop, const int32_t *__restrict__ hdr, const int64_t *__restrict__ slice_chunk0,
@@ -1595,9 +1637,9 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
         for (int r = 0; r < R; ++r) off2[r] = rec[r + 1] == rec[r] ? (unsigned)(rows_of[r] - block_row0) * 0x80008u : 0u;
     }
     auto load = [&](int64_t cc) {
-        if (!IMPL) return w8_load(stream, cc, lane);
-        W8Chunk ch;
-        w8_load_values(stream, cc, lane, ch);
+        if (!IMPL) return w8_load<VT>(stream, cc, lane);
+        W8Chunk<VT> ch;
+        w8_load_values<VT>(stream, cc, lane, ch);
         int64_t rs = 0, re = 0, cs = 0; // chunk cc lies in the wave's slice rr (cc = C0 of an empty wave: in none)
 #pragma unroll
         for (int rr = 0; rr < R; ++rr)
@@ -1606,7 +1648,7 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
         else ch.code = desc[cc];
         return ch;
     };
-    W8Chunk ring[D];
+    W8Chunk<VT> ring[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) ring[d] = load(min(C0 + d, c_last));
     // MODE 1: the dot's operand.  own_rank != nullptr: w is x at the rows' own columns (CG: w = x = p) -- where the block's window
@@ -1672,7 +1714,7 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             if (c < C1) {
-                W8Chunk cur = ring[d];
+                W8Chunk<VT> cur = ring[d];
                 ring[d] = load(min(c + D, c_last));
                 if (IMPL) {
                     cur.code.x = w8_imply(cur.code.x, cur_off);
@@ -1693,53 +1735,76 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
 
 } // namespace
 
-void bis_spmv_win8_drop(bis_mat *A) {
-    if (A->sw8) {
-        if (A->sw8->own_codes) A->sw8->codes = reinterpret_cast<uint32_t *>(A->sw8->own_codes); // (a redirected stream is the caller's memory: never freed here)
-        hipFree(A->sw8->hdr); hipFree(A->sw8->slice_chunk0); hipFree(A->sw8->own_rank); hipFree(A->sw8->codes); hipFree(A->sw8->row_of);
-        hipFree(A->sw8->slice_rec);
-        delete A->sw8;
-        A->sw8 = nullptr;
-    }
-    A->sw8_state = 0;
+// The 8-byte stream (vb = 8: A->sw8) and the 4-byte one (vb = 4, "win4": A->sw4) are two instances of one form: every function
+// below takes the value width and works on that instance.
+static inline bis_sellwin *&w8_ptr(bis_mat *A, int vb) { return vb == 4 ? A->sw4 : A->sw8; }
+static inline int &w8_state(bis_mat *A, int vb) { return vb == 4 ? A->sw4_state : A->sw8_state; }
+static inline const bis_sellwin *w8_get(const bis_mat *A, int vb) { // the usable instance, or null
+    return (vb == 4 ? A->sw4_state : A->sw8_state) == 1 ? (vb == 4 ? A->sw4 : A->sw8) : nullptr;
 }
 
-int bis_spmv_win8_blocks(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->n_blocks : 0; }
-int bis_spmv_win8_rows(const bis_mat *A) { return A->sw8_state == 1 ? A->sw8->R : 0; }
-bool bis_spmv_win8_implied(const bis_mat *A) { return A->sw8_state == 1 && A->sw8->slice_rec != nullptr; }
+static void w8_drop_one(bis_mat *A, int vb) {
+    if (bis_sellwin *&sw = w8_ptr(A, vb)) {
+        if (sw->own_codes) sw->codes = reinterpret_cast<uint32_t *>(sw->own_codes); // (a redirected stream is the caller's memory: never freed here)
+        hipFree(sw->hdr); hipFree(sw->slice_chunk0); hipFree(sw->own_rank); hipFree(sw->codes); hipFree(sw->row_of);
+        hipFree(sw->slice_rec);
+        delete sw;
+        sw = nullptr;
+    }
+    w8_state(A, vb) = 0;
+}
+
+void bis_spmv_win8_drop(bis_mat *A) {
+    w8_drop_one(A, 8);
+    w8_drop_one(A, 4);
+}
+
+// which of the two streams the reports without a context speak of (bis_mat_win8_layout, _tuning, _debug_stream): the 4-byte one
+// where it is built and spmv_resolve's conditions on the flag and the options still hold, else the 8-byte one
+int bis_spmv_win8_active(const bis_mat *A) {
+    return A->f32_exact && A->sw4_state == 1 && bis_opts().spmv_win4 != 0 && bis_opts().spmv_win8 != 0 ? 4 : 8;
+}
+
+int bis_spmv_win8_blocks(const bis_mat *A, int vb) { const bis_sellwin *sw = w8_get(A, vb); return sw ? sw->n_blocks : 0; }
+int bis_spmv_win8_rows(const bis_mat *A, int vb) { const bis_sellwin *sw = w8_get(A, vb); return sw ? sw->R : 0; }
+bool bis_spmv_win8_implied(const bis_mat *A, int vb) { const bis_sellwin *sw = w8_get(A, vb); return sw && sw->slice_rec != nullptr; }
 // bytes of the form's own arrays one launch reads: the stream (with its padding), block headers, slice offsets.  The implied-slot
 // layout: 2048 bytes of values per chunk, 8 bytes of slot bases per chunk of an implicit slice, 512 bytes of slots per chunk of an
-// explicit slice, and the slices' slot-record offsets
-int64_t bis_spmv_win8_bytes(const bis_mat *A) {
-    if (A->sw8_state != 1) return 0;
-    const bis_sellwin *sw = A->sw8;
+// explicit slice, and the slices' slot-record offsets.  win4: 1536 / 1024 bytes per chunk
+int64_t bis_spmv_win8_bytes(const bis_mat *A, int vb) {
+    const bis_sellwin *sw = w8_get(A, vb);
+    if (!sw) return 0;
     const int64_t meta = (int64_t)sw->n_blocks * (8 * kW8Runs + 2 * kSwRows * sw->R) + 8 * (sw->n_slices + 1);
-    if (!bis_spmv_win8_implied(A)) return sw->total_chunks * (int64_t)kW8ChunkBytes + meta;
-    return sw->total_chunks * (int64_t)kW8ValBytes + 8 * (sw->total_chunks - sw->expl_chunks) + 512 * sw->expl_chunks + meta + 8 * (sw->n_slices + 1);
+    if (!sw->slice_rec) return sw->total_chunks * (int64_t)w8_chunk_bytes(vb) + meta;
+    return sw->total_chunks * (int64_t)w8_val_bytes(vb) + 8 * (sw->total_chunks - sw->expl_chunks) + 512 * sw->expl_chunks + meta + 8 * (sw->n_slices + 1);
 }
 
 // placement tuning (bis_mat_tune_placement): the stream's size, and an exchange of the buffer the kernel reads (values and slots,
 // in either layout)
-size_t bis_spmv_win8_stream_bytes(const bis_mat *A) {
-    if (A->sw8_state != 1) return 0;
-    return bis_spmv_win8_implied(A) ? A->sw8->w8_end : (size_t)kW8ChunkBytes * (size_t)(A->sw8->total_chunks + 1);
+size_t bis_spmv_win8_stream_bytes(const bis_mat *A, int vb) {
+    const bis_sellwin *sw = w8_get(A, vb);
+    if (!sw) return 0;
+    return sw->slice_rec ? sw->w8_end : w8_chunk_bytes(vb) * (size_t)(sw->total_chunks + 1);
 }
 
 // the placement searches' test for the fast level of the stream's placement, priced on the bytes a launch moves (the same
 // measure for both layouts): the form's own arrays, the x granules copied into the blocks' windows, y.  HPCG-256 moves 5.43 GB
 // in today's layout (plain product: fast level 0.755-0.79 ms = 6.9-7.2 TB/s, slow 0.855-0.89 ms = 6.1-6.35) and 4.59 GB with implied
 // slots (fused product, as the search times it there: 0.664-0.688 ms = 6.7-6.9 TB/s on good allocations, 0.81 ms on bad ones);
-// 6.6 TB/s lies between the levels of either.
-double bis_spmv_win8_moved_bytes(const bis_mat *A) {
-    if (A->sw8_state != 1) return 0.0;
-    return (double)bis_spmv_win8_bytes(A) + 64.0 * (double)A->sw8->win_gran_sum + 8.0 * (double)A->n_rows;
+// 6.6 TB/s lies between the levels of either.  (The 4-byte stream is held to the same rate on its own, smaller, byte count: whether
+// it reaches that rate has not been measured -- docs/EXPERIMENTS.md section 23 -- and no other threshold is invented for it.)
+double bis_spmv_win8_moved_bytes(const bis_mat *A, int vb) {
+    const bis_sellwin *sw = w8_get(A, vb);
+    if (!sw) return 0.0;
+    return (double)bis_spmv_win8_bytes(A, vb) + 64.0 * (double)sw->win_gran_sum + 8.0 * (double)A->n_rows;
 }
-bool bis_spmv_win8_fast(const bis_mat *A, double ms) {
-    return A->sw8_state == 1 && ms > 0.0 && bis_spmv_win8_moved_bytes(A) / (ms * 1e-3) >= 6.6e12;
+bool bis_spmv_win8_fast(const bis_mat *A, double ms, int vb) {
+    return w8_get(A, vb) && ms > 0.0 && bis_spmv_win8_moved_bytes(A, vb) / (ms * 1e-3) >= 6.6e12;
 }
-void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream) {
-    void *old = A->sw8->codes;
-    A->sw8->codes = reinterpret_cast<uint32_t *>(stream);
+void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream, int vb) {
+    bis_sellwin *sw = w8_ptr(A, vb);
+    void *old = sw->codes;
+    sw->codes = reinterpret_cast<uint32_t *>(stream);
     return old;
 }
 
@@ -1749,8 +1814,8 @@ void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream) {
         if (e_ != hipSuccess) {                                                \
             (void)hipGetLastError();                                           \
             hipFree(slice_chunks); hipFree(tmp);                               \
-            bis_spmv_win8_drop(A);                                             \
-            A->sw8_state = -1;                                                 \
+            w8_drop_one(A, vb);                                                \
+            w8_state(A, vb) = -1;                                              \
             if (e_ == hipErrorOutOfMemory) return BIS_OK; /* the gather kernel stays */ \
             ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);      \
             return BIS_ERR_HIP;                                                \
@@ -1766,10 +1831,10 @@ void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream) {
 // in a row have been seen --; the earlier ones are
 // held so that the next one lands elsewhere; bounded by the free memory minus 8 GiB), each a device-to-device copy timed with
 // the kernel itself on a zero vector, and the search ends at the first allocation of the fast level.
-static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
-    bis_sellwin *sw = A->sw8;
-    const size_t bytes = bis_spmv_win8_stream_bytes(A);
-    // (the size test is on today's layout, 2560 bytes per chunk, in both layouts: the same matrices are searched)
+static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A, int vb) {
+    bis_sellwin *sw = w8_ptr(A, vb);
+    const size_t bytes = bis_spmv_win8_stream_bytes(A, vb);
+    // (the size test is on today's layout, 2560 bytes per chunk, in both layouts and for the 4-byte stream: the same matrices are searched)
     const int k = bis_opts().spmv_win8_tune >= 0 ? bis_opts().spmv_win8_tune : ((size_t)kW8ChunkBytes * (size_t)(sw->total_chunks + 1) >= ((size_t)1 << 30) ? 12 : 0);
     if (k <= 0) return BIS_OK;
     double *x = nullptr, *y = nullptr, *part = nullptr;
@@ -1791,14 +1856,14 @@ static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
     const int nb = sw->n_blocks, remap_arg = bis_spmv_remap_arg(nb), grid = bis_spmv_grid(nb);
     // the kernel timed: with implied slots the one CG runs (the fused (Ap, p) dot, w = x) -- the plain product's time did not tell
     // its placement level (HPCG-256: 0.635 ms plain on an allocation where the CG loop's fused launches took 0.81 ms)
-    const bool implied = bis_spmv_win8_implied(A);
+    const bool implied = bis_spmv_win8_implied(A, vb);
     const int mode = implied ? 1 : 0;
     const double *w = implied ? x + A->view_row0 : nullptr;
     double *partials = implied ? part : nullptr;
     auto measure = [&](double &ms) -> bool {
-        for (int i = 0; i < 2; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, mode, w, partials, nullptr, remap_arg, grid) != BIS_OK) return false;
+        for (int i = 0; i < 2; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, mode, w, partials, nullptr, remap_arg, grid, vb) != BIS_OK) return false;
         hipEventRecord(e0, ctx->stream);
-        for (int i = 0; i < 5; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, mode, w, partials, nullptr, remap_arg, grid) != BIS_OK) return false;
+        for (int i = 0; i < 5; ++i) if (bis_spmv_win8_launch(ctx, A, x, y, mode, w, partials, nullptr, remap_arg, grid, vb) != BIS_OK) return false;
         hipEventRecord(e1, ctx->stream);
         if (hipEventSynchronize(e1) != hipSuccess) return false;
         float f = 0.f;
@@ -1813,24 +1878,24 @@ static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
     // the slowest seen (ragged rows never reach the fast level's rate).  With implied slots the placements spread over more than
     // two levels (HPCG-256: 0.65-0.78 ms) and the 8 % rule stopped at middle ones (0.70-0.72 ms): there only the rate counts
     double slowest = best;
-    auto fast_enough = [&](double ms) { return bis_spmv_win8_fast(A, ms) || (!implied && ms <= 0.92 * slowest); };
+    auto fast_enough = [&](double ms) { return bis_spmv_win8_fast(A, ms, vb) || (!implied && ms <= 0.92 * slowest); };
     int trials = 0;
     for (; trials < k && !fast_enough(best); ++trials) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + ((size_t)8 << 30)) break;
         void *cand = nullptr;
         if (hipMalloc(&cand, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        void *cur = bis_spmv_win8_swap_stream(A, cand);
+        void *cur = bis_spmv_win8_swap_stream(A, cand, vb);
         hipMemcpyAsync(cand, cur, bytes, hipMemcpyDeviceToDevice, ctx->stream);
         double ms = 0.0;
-        if (!measure(ms)) { bis_spmv_win8_swap_stream(A, cur); losers.push_back(cand); cleanup(); ctx->err = "win8 placement tuning: launch failed"; return BIS_ERR_HIP; }
+        if (!measure(ms)) { bis_spmv_win8_swap_stream(A, cur, vb); losers.push_back(cand); cleanup(); ctx->err = "win8 placement tuning: launch failed"; return BIS_ERR_HIP; }
         slowest = std::max(slowest, ms);
         if (ms < best) { best = ms; losers.push_back(cur); }
-        else { bis_spmv_win8_swap_stream(A, cur); losers.push_back(cand); }
+        else { bis_spmv_win8_swap_stream(A, cur, vb); losers.push_back(cand); }
     }
     sw->tune_trials = trials;
     sw->tune_kept_ms = best;
-    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 placement: %d re-allocation(s) of %zu bytes tried, kernel %.4f ms on the first allocation, %.4f ms on the one kept (%.0f bytes moved: %.2f TB/s)\n", trials, bytes, sw->tune_first_ms, best, bis_spmv_win8_moved_bytes(A), bis_spmv_win8_moved_bytes(A) / (best * 1e9));
+    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 placement: %d re-allocation(s) of %zu bytes tried, kernel %.4f ms on the first allocation, %.4f ms on the one kept (%.0f bytes moved: %.2f TB/s)\n", trials, bytes, sw->tune_first_ms, best, bis_spmv_win8_moved_bytes(A, vb), bis_spmv_win8_moved_bytes(A, vb) / (best * 1e9));
     cleanup();
     return BIS_OK;
 }
@@ -1838,36 +1903,37 @@ static bis_status w8_tune_placement(bis_ctx *ctx, bis_mat *A) {
 // debugging / tuning aid (tools/win8_offsets.py): the stream's address and size; *set != NULL: read the stream from there from now
 // on (the caller owns that memory and has copied the stream into it; the library's own buffer stays allocated)
 extern "C" BIS_API bis_status bis_mat_win8_debug_stream(bis_mat *A, void **ptr, size_t *bytes, void *set) {
-    if (!A || A->sw8_state != 1) return BIS_ERR_INVALID;
-    bis_sellwin *sw = A->sw8;
+    const int vb = A ? bis_spmv_win8_active(A) : 8;
+    if (!A || !w8_get(A, vb)) return BIS_ERR_INVALID;
+    bis_sellwin *sw = w8_ptr(A, vb);
     if (ptr) *ptr = sw->own_codes ? sw->own_codes : (void *)sw->codes;
-    if (bytes) *bytes = bis_spmv_win8_stream_bytes(A);
+    if (bytes) *bytes = bis_spmv_win8_stream_bytes(A, vb);
     if (set) { if (!sw->own_codes) sw->own_codes = (void *)sw->codes; sw->codes = reinterpret_cast<uint32_t *>(set); }
     else if (sw->own_codes) { sw->codes = reinterpret_cast<uint32_t *>(sw->own_codes); sw->own_codes = nullptr; }
     return BIS_OK;
 }
 
 extern "C" BIS_API void bis_mat_win8_layout(const bis_mat *A, int64_t *chunks, int64_t *explicit_chunks, int64_t *slices, int *blocks, int *implied) {
-    const bool ok = A && A->sw8_state == 1;
-    if (chunks) *chunks = ok ? A->sw8->total_chunks : 0;
-    if (explicit_chunks) *explicit_chunks = ok ? A->sw8->expl_chunks : 0;
-    if (slices) *slices = ok ? A->sw8->n_slices : 0;
-    if (blocks) *blocks = ok ? A->sw8->n_blocks : 0;
-    if (implied) *implied = ok && bis_spmv_win8_implied(A);
+    const bis_sellwin *sw = A ? w8_get(A, bis_spmv_win8_active(A)) : nullptr;
+    if (chunks) *chunks = sw ? sw->total_chunks : 0;
+    if (explicit_chunks) *explicit_chunks = sw ? sw->expl_chunks : 0;
+    if (slices) *slices = sw ? sw->n_slices : 0;
+    if (blocks) *blocks = sw ? sw->n_blocks : 0;
+    if (implied) *implied = sw && sw->slice_rec != nullptr;
 }
 
 extern "C" BIS_API void bis_mat_win8_tuning(const bis_mat *A, int *trials, double *first_ms, double *kept_ms) {
-    const bool ok = A && A->sw8_state == 1;
-    if (trials) *trials = ok ? A->sw8->tune_trials : 0;
-    if (first_ms) *first_ms = ok ? A->sw8->tune_first_ms : 0.0;
-    if (kept_ms) *kept_ms = ok ? A->sw8->tune_kept_ms : 0.0;
+    const bis_sellwin *sw = A ? w8_get(A, bis_spmv_win8_active(A)) : nullptr;
+    if (trials) *trials = sw ? sw->tune_trials : 0;
+    if (first_ms) *first_ms = sw ? sw->tune_first_ms : 0.0;
+    if (kept_ms) *kept_ms = sw ? sw->tune_kept_ms : 0.0;
 }
 
-static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_large);
+static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_large, int vb);
 
-bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A) {
-    if (A->sw8_state != 0) return BIS_OK;
-    A->sw8_state = -1;
+bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A, int vb) {
+    if (w8_state(A, vb) != 0) return BIS_OK;
+    w8_state(A, vb) = -1;
     if (A->n_rows == 0 || A->nnz == 0 || A->n_cols >= ((int64_t)1 << 31) - 16) return BIS_OK;
     // default 4 rows per lane (blocks of 1024 rows): HPCG-256 0.78 ms against 0.86 with 2 and 1.20 with 1 -- the larger the block, the
     // fewer times an x entry is copied into some block's window (tools/win8_probe.py, profiles/r05_c_win8_probe.log).  Where a
@@ -1878,21 +1944,22 @@ bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A) {
     while (R > 1 && A->n_rows < (int64_t)kSwRows * R * 1024) R >>= 1;
     for (;; R >>= 1) {
         bool too_large = false;
-        if (bis_status st = w8_try_rows(ctx, A, R, &too_large)) return st;
-        if (A->sw8_state == 1 || !too_large || R == 1 || bis_opts().spmv_win8_rows > 0) return BIS_OK;
-        A->sw8_state = -1;
+        if (bis_status st = w8_try_rows(ctx, A, R, &too_large, vb)) return st;
+        if (w8_state(A, vb) == 1 || !too_large || R == 1 || bis_opts().spmv_win8_rows > 0) return BIS_OK;
+        w8_state(A, vb) = -1;
     }
 }
 
-static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_large) {
+static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_large, int vb) {
     *window_too_large = false;
     const int64_t nb64 = (A->n_rows + (int64_t)kSwRows * R - 1) / ((int64_t)kSwRows * R);
     if (nb64 > (int64_t)1 << 26) return BIS_OK;
     const int nb = (int)nb64;
     bis_sellwin *sw = new bis_sellwin;
-    A->sw8 = sw;
+    w8_ptr(A, vb) = sw;
     sw->n_blocks = nb;
     sw->R = R;
+    sw->vb = vb;
     sw->n_slices = (int64_t)nb * 4 * R;
     sw->fmt = 5;
     int32_t *slice_chunks = nullptr;
@@ -1933,15 +2000,15 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
     if (h[0] || (double)total * 256.0 > 1.12 * (double)A->nnz + 256.0 * 4 * 64) {
         if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 plan (R = %d): %s, %.1f %% padding: not used\n", R, h[0] ? "window not representable" : "representable", 100.0 * ((double)total * 256.0 / (double)A->nnz - 1.0));
         *window_too_large = h[0] != 0;
-        bis_spmv_win8_drop(A);
-        A->sw8_state = -1;
+        w8_drop_one(A, vb);
+        w8_state(A, vb) = -1;
         return BIS_OK;
     }
-#define W8_FILL(PHASE, STREAM, DESC, SIDE)                                                                                                        \
+#define W8_FILL(PHASE, VT, STREAM, DESC, SIDE)                                                                                                    \
     do {                                                                                                                                          \
-        if (A->rp64) hipLaunchKernelGGL((w8_fill_kernel<int64_t, PHASE>), dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, \
+        if (A->rp64) hipLaunchKernelGGL((w8_fill_kernel<int64_t, PHASE, VT>), dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, \
                                         A->val, A->n_rows, R, sw->hdr, sw->slice_chunk0, sw->row_of, STREAM, sw->slice_rec, DESC, SIDE);           \
-        else hipLaunchKernelGGL((w8_fill_kernel<int32_t, PHASE>), dim3(nb), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col,     \
+        else hipLaunchKernelGGL((w8_fill_kernel<int32_t, PHASE, VT>), dim3(nb), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, \
                                 A->val, A->n_rows, R, sw->hdr, sw->slice_chunk0, sw->row_of, STREAM, sw->slice_rec, DESC, SIDE);                   \
         W8_CHECK(hipGetLastError());                                                                                                              \
     } while (0)
@@ -1951,7 +2018,7 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
     if (bis_opts().spmv_win8_implicit != 0 && total > 0) {
         W8_CHECK(hipMalloc(&sw->slice_rec, sizeof(int64_t) * (size_t)ns1));
         W8_CHECK(hipMemsetAsync(sw->slice_rec, 0, sizeof(int64_t) * (size_t)ns1, ctx->stream));
-        W8_FILL(1, nullptr, nullptr, nullptr);
+        W8_FILL(1, double, nullptr, nullptr, nullptr); // (value-free: one instance serves both widths)
         tmp_bytes = 0;
         W8_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, sw->slice_rec, sw->slice_rec, (int64_t)0, (size_t)ns1, rocprim::plus<int64_t>(), ctx->stream));
         W8_CHECK(hipMalloc(&tmp, tmp_bytes));
@@ -1964,7 +2031,7 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
         else { hipFree(sw->slice_rec); sw->slice_rec = nullptr; }
     }
     unsigned char *stream = nullptr;
-    const size_t chunk_bytes = sw->slice_rec ? kW8ValBytes : kW8ChunkBytes;
+    const size_t chunk_bytes = sw->slice_rec ? w8_val_bytes(vb) : w8_chunk_bytes(vb);
     size_t stream_bytes = chunk_bytes * (size_t)(total + 1);
     if (sw->slice_rec) {
         sw->w8_desc = stream_bytes;
@@ -1976,21 +2043,23 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
     W8_CHECK(hipMemsetAsync(stream + (size_t)total * chunk_bytes, 0, chunk_bytes, ctx->stream));
     if (sw->slice_rec) {
         W8_CHECK(hipMemsetAsync(stream + sw->w8_desc, 0, sw->w8_side - sw->w8_desc, ctx->stream));
-        W8_FILL(2, stream, reinterpret_cast<uint2 *>(stream + sw->w8_desc), stream + sw->w8_side);
+        if (vb == 4) W8_FILL(2, float, stream, reinterpret_cast<uint2 *>(stream + sw->w8_desc), stream + sw->w8_side);
+        else W8_FILL(2, double, stream, reinterpret_cast<uint2 *>(stream + sw->w8_desc), stream + sw->w8_side);
     } else {
-        W8_FILL(0, stream, nullptr, nullptr);
+        if (vb == 4) W8_FILL(0, float, stream, nullptr, nullptr);
+        else W8_FILL(0, double, stream, nullptr, nullptr);
     }
 #undef W8_FILL
-    A->sw8_state = 1;
-    if (bis_status tst = w8_tune_placement(ctx, A)) return tst;
-    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win8 plan (R = %d): %d blocks, window <= %d granules (%zu bytes), %.1f %% padding: used; implied slots: %s, %.1f %% of %lld chunks implicit; stream at %p (%zu bytes), hdr %p\n", R, nb, sw->max_gran, (size_t)(2 + 8 * sw->max_gran) * 8, 100.0 * ((double)total * 256.0 / (double)A->nnz - 1.0), sw->slice_rec ? "built" : "not built", 100.0 * (double)(total - sw->expl_chunks) / (double)std::max<int64_t>(total, 1), (long long)total, (void *)sw->codes, bis_spmv_win8_stream_bytes(A), (void *)sw->hdr);
+    w8_state(A, vb) = 1;
+    if (bis_status tst = w8_tune_placement(ctx, A, vb)) return tst;
+    if (getenv("BIS_WIN8_STATS")) fprintf(stderr, "win%d plan (R = %d): %d blocks, window <= %d granules (%zu bytes), %.1f %% padding: used; implied slots: %s, %.1f %% of %lld chunks implicit; stream at %p (%zu bytes), hdr %p\n", vb, R, nb, sw->max_gran, (size_t)(2 + 8 * sw->max_gran) * 8, 100.0 * ((double)total * 256.0 / (double)A->nnz - 1.0), sw->slice_rec ? "built" : "not built", 100.0 * (double)(total - sw->expl_chunks) / (double)std::max<int64_t>(total, 1), (long long)total, (void *)sw->codes, bis_spmv_win8_stream_bytes(A, vb), (void *)sw->hdr);
     return BIS_OK;
 }
 #undef W8_CHECK
 
 bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x, double *y, int mode, const double *w,
-                                double *partials, const int *stop, int remap_arg, int grid) {
-    const bis_sellwin *sw = A->sw8;
+                                double *partials, const int *stop, int remap_arg, int grid, int vb) {
+    const bis_sellwin *sw = vb == 4 ? A->sw4 : A->sw8;
     const int x_al16 = ((uintptr_t)x & 15) == 0;
     const size_t lds = (size_t)(2 + 8 * sw->max_gran) * 8;
     const unsigned char *stream = reinterpret_cast<const unsigned char *>(sw->codes);
@@ -2000,8 +2069,9 @@ bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
     // (HPCG-256 0.861; 2: 0.945, 4: 1.030).  The waves of the other workgroups on the CU cover the rest of the latency.
     const bool ragged = (double)sw->total_chunks * 256.0 > 1.08 * (double)A->nnz;
     const int depth = bis_opts().spmv_win8_depth > 0 ? bis_opts().spmv_win8_depth : (sw->R == 4 ? (ragged ? 2 : 1) : 3);
-#define W8_L3(MODE, RR, DD) do { if (sw->slice_rec) W8_L4(MODE, RR, DD, true); else W8_L4(MODE, RR, DD, false); } while (0)
-#define W8_L4(MODE, RR, DD, IMPL) hipLaunchKernelGGL((spmv_win8_kernel<MODE, RR, DD, IMPL>), dim3(grid), dim3(256), lds, ctx->stream, x, y, A->n_rows, A->n_cols, \
+#define W8_L3(MODE, RR, DD) do { if (sw->slice_rec) W8_L5(MODE, RR, DD, true); else W8_L5(MODE, RR, DD, false); } while (0)
+#define W8_L5(MODE, RR, DD, IMPL) do { if (vb == 4) W8_L4(MODE, RR, DD, IMPL, float); else W8_L4(MODE, RR, DD, IMPL, double); } while (0)
+#define W8_L4(MODE, RR, DD, IMPL, VT) hipLaunchKernelGGL((spmv_win8_kernel<MODE, RR, DD, IMPL, VT>), dim3(grid), dim3(256), lds, ctx->stream, x, y, A->n_rows, A->n_cols, \
                                                sw->n_blocks, remap_arg, w, partials, stop, sw->hdr, sw->slice_chunk0, stream, x_al16, own, sw->row_of, \
                                                reinterpret_cast<const w8_v2u *>(stream + sw->w8_desc), stream + sw->w8_side, sw->slice_rec)
 #define W8_L2(MODE, RR) do { if (depth <= 1) W8_L3(MODE, RR, 1); else if (depth == 2) W8_L3(MODE, RR, 2); else if (depth == 3) W8_L3(MODE, RR, 3); else if (depth <= 5) W8_L3(MODE, RR, 4); else W8_L3(MODE, RR, 6); } while (0)
@@ -2011,6 +2081,7 @@ bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
 #undef W8_L2
 #undef W8_L3
 #undef W8_L4
+#undef W8_L5
     BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
 }

@@ -59,6 +59,9 @@ enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; 
 // -inner K: inner sweeps of the two-stage Gauss-Seidel types and of -p ilu0it, at run time; the default is the
 // compile-time PRECOND_INNER_ITERS, so a command line without the flag runs what it always ran
 inline int &precond_inner_iters() { static int k = PRECOND_INNER_ITERS; return k; }
+// -pprec 32|64: the values of the factors that -p fsai and -p ilu0it apply by SpMV are rounded to fp32 after the
+// factorisation (bis_mat_round_f32); 64, the default, leaves them as they are
+inline int &precond_value_bits() { static int b = 64; return b; }
 enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB };
 
 inline std::string to_string(PrecondType t) {
@@ -81,6 +84,7 @@ struct Args {
     PrecondType preconditioner{};
     int restart_length = 10;
     int inner_iters = PRECOND_INNER_ITERS; // -inner K (precond_inner_iters())
+    int pprec = 64;                        // -pprec 32|64 (precond_value_bits())
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

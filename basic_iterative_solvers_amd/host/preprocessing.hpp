@@ -24,6 +24,18 @@ inline void scale_mat(MatrixCRS *A, const double *s) { // preprocessing.hpp:15-2
 }
 
 // factor_LU, utilities/LU_factors.hpp:900-934
+// -pprec 32: the two matrices the preconditioner applies by SpMV, rounded to fp32 in place (bis_mat_round_f32); their SpMV
+// then streams 4-byte values.  Rounding is elementwise, so round(Gt) = round(G)^T bit for bit.
+inline void round_precond_factors(Solver *s) {
+    if (precond_value_bits() != 32) return;
+    double change = 0.0, worst = 0.0;
+    for (bis_mat *M : {s->L_strict->dev, s->U_strict->dev}) {
+        bis::check(bis_mat_round_f32(bis::ctx(), M, &change), "bis_mat_round_f32");
+        worst = change > worst ? change : worst;
+    }
+    std::cout << "preconditioner values rounded to fp32: max relative change " << worst << std::endl;
+}
+
 inline void factor_LU(Solver *s) {
     // split + diagonal on the device (bis_mat_split_strict: bit-identical to the reference's split_LU + peel_diag_crs,
     // tests/test_gpu_kernels.py), for generated and for file inputs alike; the host versions of utilities/LU_factors.hpp
@@ -49,6 +61,7 @@ inline void factor_LU(Solver *s) {
         s->U_strict->adopt(Us);
         // -p ilu0it multiplies by the pivots' reciprocals: A_D_inv carries 1 / U_D for that type (L_D is the vector of ones)
         if (s->preconditioner == PrecondType::ILU0Iter) elemwise_div_vectors(s->A_D_inv, s->L_D, s->U_D, s->N);
+        if (s->preconditioner == PrecondType::ILU0Iter) round_precond_factors(s); // (the diagonals L_D, U_D, 1 / U_D stay fp64)
     }
     if (s->preconditioner == PrecondType::FSAI) {
         // -p fsai: G and Gt = G^T take the places of the strict triangles (bis_apply_preconditioner reads them as two SpMVs)
@@ -60,6 +73,7 @@ inline void factor_LU(Solver *s) {
         s->L_strict->adopt(G);
         s->U_strict->adopt(Gt);
         if (n_fallback != 0) std::cout << "fsai: " << n_fallback << " rows fell back to 1/sqrt(|a_ii|)" << std::endl;
+        round_precond_factors(s);
     }
 }
 

@@ -7,7 +7,8 @@
 // and `-unfused` / `-dev K` select the kernel-by-kernel CG and the device;
 // `-perm mc` applies the multi-colour reordering of utilities/permute.hpp; `-p ilu0it` is ILU(0) with iterative
 // triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st); `-p fsai` is the
-// factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs.
+// factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs; `-pprec 32` rounds the factors those two
+// types apply by SpMV to fp32 (bis_mat_round_f32).
 #pragma once
 
 #include <sys/stat.h>
@@ -72,6 +73,14 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             }
             precond_inner_iters() = a->inner_iters;
         }
+        else if (arg == "-pprec" && i + 1 < argc) {
+            a->pprec = atoi(argv[++i]);
+            if (a->pprec != 32 && a->pprec != 64) {
+                fprintf(stderr, "ERROR: -pprec 32|64\n");
+                exit(EXIT_FAILURE);
+            }
+            precond_value_bits() = a->pprec;
+        }
         else if (arg == "-unfused") a->unfused = true;
         else if (arg == "-hostscalars") a->host_scalars = true;
         else if (arg == "-trsv" && i + 1 < argc) {
@@ -91,6 +100,11 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else if (arg == "-cache" && i + 1 < argc) a->crs_cache = argv[++i];
         else if (arg == "-dev" && i + 1 < argc) a->device = atoi(argv[++i]);
         else std::cout << "ERROR: assign_cli_inputs: Arguement \"" << arg << "\" not recongnized." << std::endl;
+    }
+    // the other types run exact sweeps on the fp64 arrays and would gain nothing from rounded values
+    if (a->pprec == 32 && a->preconditioner != PrecondType::FSAI && a->preconditioner != PrecondType::ILU0Iter) {
+        fprintf(stderr, "ERROR: -pprec 32 needs a preconditioner that is applied by SpMV: -p fsai or -p ilu0it\n");
+        exit(EXIT_FAILURE);
     }
 }
 

@@ -158,7 +158,10 @@ BIS_API int bis_mat_rp_width(const bis_mat *A);
  * (a 32-bit mask of pairs per ROW)), 6 = the window + sliced-ELL form with the
  * 8-byte values streamed (col_bytes 2: the window slot, also where the slots are
  * implied; matrices without a dictionary; option "spmv_win8" 0 switches it off),
- * 7 = the CRS-value kernel in K passes over column slabs (n_dict = K).  Form 0
+ * 7 = the CRS-value kernel in K passes over column slabs (n_dict = K), 8 = form 6
+ * with 4-byte values (col_bytes 2, val_bytes 4, "win4 rows=R"): only for a matrix
+ * that bis_mat_round_f32 flagged, on whose values the float stream is lossless;
+ * option "spmv_win4" 0 switches it off (the matrix then gets form 6).  Form 0
  * also covers the wave-per-row kernel of very long rows (col_bytes 4) and the
  * opt-in x-window kernel (col_bytes 2).  The report names what bis_spmv launches
  * and builds nothing else.
@@ -207,7 +210,9 @@ BIS_API bis_status bis_mat_retune(bis_ctx *ctx, bis_mat *A);
 BIS_API void bis_mat_win8_tuning(const bis_mat *A, int *trials, double *first_ms, double *kept_ms);
 /* The layout of that stream (zeros without one): its chunks (4 entries of 64 rows), the chunks that keep their
  * 2-byte window slots (all of them unless *implied), slices (64 rows), blocks; *implied = 1 where the slots of the
- * other chunks are implied by their rows (option "spmv_win8_implicit"): 2048 bytes per chunk instead of 2560. */
+ * other chunks are implied by their rows (option "spmv_win8_implicit"): 2048 bytes per chunk instead of 2560.
+ * Where the matrix runs form 8 (4-byte values) this, bis_mat_win8_tuning and bis_mat_win8_debug_stream speak of that
+ * stream: the same chunks at 1536 bytes, 1024 with implied slots. */
 BIS_API void bis_mat_win8_layout(const bis_mat *A, int64_t *chunks, int64_t *explicit_chunks, int64_t *slices, int *blocks, int *implied);
 /* Column slabs (the SpMV's form for a matrix WITHOUT locality: rows along which the slab index never falls --
  * ascending columns, the usual case --, a column stream that does not
@@ -287,6 +292,31 @@ BIS_API bis_status bis_mat_split_strict(bis_ctx *ctx, const bis_mat *A,
  * with the reference's message if |a_rr| < 1e-16.  The values only change, so
  * the packed column stream and the row-block tables stay valid. */
 BIS_API bis_status bis_mat_scale_sym(bis_ctx *ctx, bis_mat *A, double *scale);
+
+/* Single-precision preconditioner storage (not in the reference).  Rounds every
+ * value of A to binary32 IN PLACE in the fp64 CRS array: v becomes
+ * (double)(float)v -- IEEE round to nearest even, subnormals kept, -0.0 kept,
+ * NaN / Inf unchanged.  *max_rel_change (may be NULL): max |v32 - v| / |v| over
+ * the finite v != 0, reduced in a fixed order (the same bits on every run).
+ * A value that is finite in fp64 but not in fp32 makes the call fail with
+ * BIS_ERR_UNSUPPORTED and leaves the matrix untouched (a census pass runs before
+ * the rounding pass).  BIS_ERR_INVALID for a null matrix or a row-range view;
+ * nnz == 0 is BIS_OK.  Blocking; idempotent (a second call changes no bit and
+ * reports 0).
+ * This is the one lossy step, explicit and once only.  Everything derived from
+ * the values is dropped as by bis_mat_scale_sym, and the matrix is flagged
+ * fp32-exact: its SpMV may then stream 4-byte values (form 8 of
+ * bis_mat_spmv_stream_info), a lossless re-encoding on such values -- y is
+ * bit-identical to every other form on the rounded matrix.  bis_mat_scale_sym
+ * and bis_mat_retune clear the flag; row views inherit it; nothing else does
+ * (permutations, splits, factorisations give unflagged matrices: round again).
+ * No matrix is ever examined or rounded without this call.
+ * The fp64 CRS arrays stay, holding the rounded values, so sweeps, bis_spmm,
+ * downloads, ILU(0) and the row-block kernels work unchanged on the rounded
+ * matrix: the feature saves memory TRAFFIC of the SpMV, not memory.
+ * Meant for preconditioner factors (G, Gt of bis_mat_fsai; the strict triangles
+ * of bis_mat_ilu0 for BIS_PC_ILU0_ITER); the Krylov method stays in fp64. */
+BIS_API bis_status bis_mat_round_f32(bis_ctx *ctx, bis_mat *A, double *max_rel_change);
 
 /* Multi-colour symmetric reordering on the device (the
  * role of SMAX's permute_mat, utilities/smax_helpers.hpp:44-80): greedy
