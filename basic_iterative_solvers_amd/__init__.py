@@ -16,7 +16,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "lib", "libbis_hip.so")
 
-PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8, "fsai": 9})
+PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8, "fsai": 9, "mg": 10})
 
 _lib = None
 
@@ -43,6 +43,8 @@ def load_library():
         _lib.bis_mat_spmm_kernel.restype = C.c_char_p
         _lib.bis_mat_sweepm_kernel.restype = C.c_char_p
         _lib.bis_mat_fsai_kernel.restype = C.c_char_p
+        _lib.bis_mg_operand.restype = C.c_void_p
+        _lib.bis_mg_level_matrix.restype = C.c_void_p
     return _lib
 
 
@@ -249,6 +251,12 @@ class Context:
         hg, hgt, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
         self.check(self.lib.bis_mat_fsai(self.h, A.h, C.byref(hg), C.byref(hgt), C.byref(nf)))
         return Mat(self, hg), Mat(self, hgt), nf.value
+
+    def mg(self, A, **params):
+        """The aggregation multigrid hierarchy of A (bis_mg_create): an MG object.  Parameters: max_levels, coarse_limit,
+        coarsening (0 / "auto", 1 / "grid", 2 / "mis"), nu, coarse_sweeps, omega, coarse_scale.  Preconditioner "mg" takes
+        Ls=MG.operand."""
+        return MG(self, A, **params)
 
     # ---- kernels (kernels.hpp names) ---------------------------------------
     def spmv(self, A, x, y):
@@ -532,6 +540,12 @@ class Mat:
         self.ctx.check(self.ctx.lib.bis_mat_round_f32(self.ctx.h, self.h, C.byref(m)))
         return m.value
 
+    def grid_hint(self):
+        """(nx, ny, nz, dof) of the structured-grid hint the matrix carries (bis_mat_grid_hint); zeros without one."""
+        g = (C.c_int64 * 4)()
+        self.ctx.check(self.ctx.lib.bis_mat_grid_hint(self.h, g))
+        return tuple(g)
+
     def retune(self):
         """Rebuild everything derived from the CRS arrays (bis_mat_retune): required after writing values in place."""
         self.ctx.check(self.ctx.lib.bis_mat_retune(self.ctx.h, self.h))
@@ -550,6 +564,59 @@ class Mat:
     def free(self):
         if self.h:
             self.ctx.lib.bis_mat_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class MGParams(C.Structure):
+    """bis_mg_params."""
+    _fields_ = [("max_levels", C.c_int), ("coarse_limit", C.c_int64), ("coarsening", C.c_int), ("nu", C.c_int),
+                ("coarse_sweeps", C.c_int), ("omega", C.c_double), ("coarse_scale", C.c_double)]
+
+
+class MG:
+    """bis_mg: an aggregation multigrid hierarchy of A; one V-cycle is the preconditioner "mg" (pass `.operand` as Ls)."""
+
+    COARSENING = dict(auto=0, grid=1, mis=2)
+
+    def __init__(self, ctx, A, max_levels=10, coarse_limit=256, coarsening=0, nu=1, coarse_sweeps=4, omega=0.0, coarse_scale=1.0):
+        self.ctx, self._keep = ctx, A
+        self.h = C.c_void_p()
+        p = MGParams(int(max_levels), int(coarse_limit), int(self.COARSENING.get(coarsening, coarsening)), int(nu),
+                     int(coarse_sweeps), float(omega), float(coarse_scale))
+        ctx.check(ctx.lib.bis_mg_create(ctx.h, A.h, C.byref(p), C.byref(self.h)))
+        n = C.c_int()
+        rows, nnz, kinds = (C.c_int64 * 16)(), (C.c_int64 * 16)(), (C.c_int * 16)()
+        ctx.lib.bis_mg_info(self.h, C.byref(n), rows, nnz, kinds)
+        self.levels = n.value
+        self.rows, self.nnz, self.kinds = list(rows[:n.value]), list(nnz[:n.value]), list(kinds[:n.value])
+        self.operand = Mat(ctx, C.c_void_p(ctx.lib.bis_mg_operand(self.h)))
+
+    def level_matrix(self, l):
+        """Level l's matrix as a Mat the hierarchy owns (level 0: A)."""
+        h = self.ctx.lib.bis_mg_level_matrix(self.h, C.c_int(int(l)))
+        if not h:
+            raise BisError(f"MG.level_matrix: no level {l}")
+        return Mat(self.ctx, C.c_void_p(h))
+
+    def aggregates(self, l):
+        """agg[i] of every row of level l (numpy int32); the coarsest level has none."""
+        out = np.zeros(self.rows[l], dtype=np.int32)
+        self.ctx.check(self.ctx.lib.bis_mg_level_aggregates(self.ctx.h, self.h, C.c_int(int(l)), out.ctypes))
+        return out
+
+    def weights(self, l):
+        """The smoother weights w of level l (numpy float64)."""
+        out = np.zeros(self.rows[l], dtype=np.float64)
+        self.ctx.check(self.ctx.lib.bis_mg_level_weights(self.ctx.h, self.h, C.c_int(int(l)), out.ctypes))
+        return out
+
+    def apply(self, out, inp):
+        """out = M^-1 inp: one V-cycle (bis_mg_apply); out may alias inp."""
+        self.ctx.check(self.ctx.lib.bis_mg_apply(self.ctx.h, self.h, C.c_void_p(out.ptr), C.c_void_p(inp.ptr)))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_mg_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 

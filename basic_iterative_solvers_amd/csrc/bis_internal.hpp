@@ -228,6 +228,8 @@ struct bis_mat {
     const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
     const char *spmm_kernel = "";           // the path and template instance the last bis_spmm on this matrix launched (bis_mat_spmm_kernel)
     const char *fsai_kernel = "";           // the instance of fsai_rows_kernel that computed this FSAI factor G (bis_mat_fsai_kernel)
+    struct bis_mg *mg = nullptr;            // the hierarchy this matrix is the preconditioner operand of (bis_mg_operand): an n x n matrix without
+                                            // entries that the hierarchy owns; bis_mat_destroy leaves it alone
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \
@@ -444,6 +446,8 @@ bis_status bis_mat_split_strict_impl(bis_ctx *ctx, const bis_mat *A, bis_mat **L
 // per row the position of its first diagonal entry (-1: none) and of its first entry right of the diagonal.  The caller
 // destroys W and frees the two device arrays.
 bis_status bis_mat_sorted_copy(bis_ctx *ctx, const bis_mat *A, bis_mat **W, int64_t **dpos, int64_t **ustart);
+// every off-diagonal entry has its mirror and no row holds a column twice (bis_order.hip: the check of bis_mat_bfs_order).  Blocking.
+bis_status bis_mat_pattern_symmetric(bis_ctx *ctx, const bis_mat *A, bool *symmetric);
 // tiled natural-order sweep (bis_trsv_tiled.hip); *out stays null when the matrix does not qualify
 bis_status bis_trsv_tiled_build(bis_ctx *ctx, const bis_mat *T, bool backward, bis_trsv_tiled **out);
 bis_status bis_trsv_tiled_solve(bis_ctx *ctx, bis_trsv_tiled *p, double *x, const double *D, const double *b);

@@ -644,6 +644,7 @@ bis_status bis_mat_create64(bis_ctx *ctx, int64_t n_rows, int64_t n_cols, int64_
 bis_status bis_mat_destroy(bis_ctx *ctx, bis_mat *A) {
     BIS_CTX_OK(ctx);
     if (!A) return BIS_OK;
+    if (A->mg) return BIS_OK; // the operand of a multigrid hierarchy (bis_mg_operand) goes with bis_mg_destroy
     hipStreamSynchronize(ctx->stream);
     bis_trsv_drop(A, /*chains=*/true);
     if (!A->view) {
@@ -803,6 +804,12 @@ bis_status bis_mat_set_grid_hint(bis_mat *A, int64_t nx, int64_t ny, int64_t nz,
     if (!A) return BIS_ERR_INVALID;
     if (nx <= 0 || ny <= 0 || nz <= 0 || dof <= 0 || nx * ny * nz * dof != A->n_rows) return BIS_ERR_INVALID;
     A->grid[0] = nx; A->grid[1] = ny; A->grid[2] = nz; A->grid[3] = dof;
+    return BIS_OK;
+}
+
+bis_status bis_mat_grid_hint(const bis_mat *A, int64_t hint[4]) {
+    if (!A || !hint) return BIS_ERR_INVALID;
+    for (int k = 0; k < 4; ++k) hint[k] = A->grid[k];
     return BIS_OK;
 }
 

@@ -277,6 +277,7 @@ bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab *m, int 
                                             const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                             const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
+    if (precond_type == BIS_PC_MG) { ctx->err = "bis_mbicgstab_set_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
     BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_FSAI && outer_iters >= 1 && inner_iters >= 0,
                 "bis_mbicgstab_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0,

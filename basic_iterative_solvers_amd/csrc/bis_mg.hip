@@ -1,0 +1,681 @@
+// bis_mg.hip -- aggregation multigrid preconditioner (unsmoothed aggregation, V(nu,nu) with Jacobi-type smoothing); not in the
+// reference.  The definitions a restatement needs are in include/bis_hip.h; this file follows them step by step.
+//
+// Setup (bis_mg_create, blocking, all on the device): per level the smoother weights and the diagonal check, the aggregate
+// of every row (from the grid hint, or a maximal independent set of the off-diagonal pattern found in rounds with one
+// counter read per round), the members lists (a stable radix sort of (aggregate, row)), and the Galerkin operator
+// P^T A P for the piecewise-constant P: a stable 64-bit radix sort of (agg[r] << 32 | agg[c], value) over the fine entries,
+// then one lane per coarse entry sums its run left to right.  No floating-point atomics and no inter-workgroup waits: two
+// calls give the same bits.
+//
+// Apply (bis_mg_apply, stream-ordered, allocates nothing): per level bis_spmv and three streaming kernels -- relax
+// (x += w o (b - y), and its from-zero form x = w o b), restrict (r_c[I] = sum over the members of b_i - y_i, a lane per
+// aggregate) and prolong (x_i += scale e_c[agg[i]]).  Products, subtractions and additions are rounded separately.
+#include "bis_internal.hpp"
+
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+
+struct bis_mg_level {
+    const bis_mat *A = nullptr; // level 0: the caller's matrix; otherwise `owned`
+    bis_mat *owned = nullptr;
+    int64_t n = 0;
+    int kind = 0;               // aggregates towards the next level: 0 none (the coarsest level), 1 grid, 2 MIS
+    int64_t n_coarse = 0;
+    double *w = nullptr;        // smoother weights [n]
+    int32_t *agg = nullptr;     // [n] aggregate of every row
+    int32_t *agg_ptr = nullptr; // [n_coarse + 1]
+    int32_t *agg_idx = nullptr; // [n] members by aggregate, ascending rows inside one
+    double *x = nullptr, *b = nullptr, *y = nullptr; // cycle scratch; level 0 owns y only (x, b are the caller's vectors)
+};
+
+struct bis_mg {
+    bis_mg_params p;
+    std::vector<bis_mg_level> lv;
+    bis_mat *operand = nullptr;
+    double *b0 = nullptr; // level 0: the copy of the right-hand side when out aliases in
+};
+
+namespace {
+
+constexpr int kMgT = 256;
+constexpr int kMgMaxBlocks = 16384; // elementwise passes: the wide grid of bis_blas1.hip's kernels
+constexpr int kMgMaxLevels = 16;
+
+typedef double mg_v2d __attribute__((ext_vector_type(2)));
+typedef int mg_v2i __attribute__((ext_vector_type(2)));
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline int mg_grid(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + kMgT - 1) / kMgT, kMgMaxBlocks)); }
+
+// ---- the cycle's kernels -----------------------------------------------------------------------------------------------
+// x = w o b: the first sweep from x = 0 (one rounding).  Inputs are touched once per pass: non-temporal loads; the store
+// stays plain -- the next kernel (an SpMV, or the prolongation of the level above) reads what this one wrote.
+template <bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_relax0_kernel(double *x, const double *w, const double *b, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *x2 = reinterpret_cast<mg_v2d *>(x);
+        const mg_v2d *w2 = reinterpret_cast<const mg_v2d *>(w), *b2 = reinterpret_cast<const mg_v2d *>(b);
+        for (; i < n2; i += stride) {
+            const mg_v2d wv = __builtin_nontemporal_load(w2 + i), bv = __builtin_nontemporal_load(b2 + i);
+            mg_v2d r;
+            r.x = __dmul_rn(wv.x, bv.x);
+            r.y = __dmul_rn(wv.y, bv.y);
+            x2[i] = r;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = __dmul_rn(w[n - 1], b[n - 1]);
+    } else {
+        for (; i < n; i += stride) x[i] = __dmul_rn(__builtin_nontemporal_load(w + i), __builtin_nontemporal_load(b + i));
+    }
+}
+
+// x += w o (b - y), y = A x: t = b - y, u = w t, x = x + u, each rounded
+__device__ __forceinline__ double mg_relax1(double x, double w, double b, double y) { return __dadd_rn(x, __dmul_rn(w, __dsub_rn(b, y))); }
+
+template <bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_relax_kernel(double *x, const double *w, const double *b, const double *y, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *x2 = reinterpret_cast<mg_v2d *>(x);
+        const mg_v2d *w2 = reinterpret_cast<const mg_v2d *>(w), *b2 = reinterpret_cast<const mg_v2d *>(b),
+                     *y2 = reinterpret_cast<const mg_v2d *>(y);
+        for (; i < n2; i += stride) {
+            const mg_v2d xv = __builtin_nontemporal_load(x2 + i), wv = __builtin_nontemporal_load(w2 + i),
+                         bv = __builtin_nontemporal_load(b2 + i), yv = __builtin_nontemporal_load(y2 + i);
+            mg_v2d r;
+            r.x = mg_relax1(xv.x, wv.x, bv.x, yv.x);
+            r.y = mg_relax1(xv.y, wv.y, bv.y, yv.y);
+            x2[i] = r;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = mg_relax1(x[n - 1], w[n - 1], b[n - 1], y[n - 1]);
+    } else {
+        for (; i < n; i += stride)
+            x[i] = mg_relax1(__builtin_nontemporal_load(x + i), __builtin_nontemporal_load(w + i), __builtin_nontemporal_load(b + i),
+                             __builtin_nontemporal_load(y + i));
+    }
+}
+
+// r_c[I] = sum over the members i of aggregate I, ascending, of (b_i - y_i): a lane per aggregate, the first difference
+// starts the sum, every further one is added to it (each subtraction and each addition rounded)
+__global__ __launch_bounds__(kMgT) void mg_restrict_kernel(const int32_t *__restrict__ agg_ptr, const int32_t *__restrict__ agg_idx,
+                                                           const double *__restrict__ b, const double *__restrict__ y,
+                                                           double *__restrict__ rc, int64_t nc) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t I = (int64_t)blockIdx.x * kMgT + threadIdx.x; I < nc; I += stride) {
+        const int32_t s = agg_ptr[I], e = agg_ptr[I + 1];
+        double acc = 0.0;
+        for (int32_t k = s; k < e; ++k) {
+            const int32_t i = __builtin_nontemporal_load(agg_idx + k);
+            const double d = __dsub_rn(__builtin_nontemporal_load(b + i), __builtin_nontemporal_load(y + i));
+            acc = k == s ? d : __dadd_rn(acc, d);
+        }
+        rc[I] = acc;
+    }
+}
+
+// x_i += scale e_c[agg[i]] (the product rounded, then the sum)
+template <bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_prolong_kernel(double *x, const int32_t *__restrict__ agg, const double *__restrict__ ec,
+                                                          double scale, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *x2 = reinterpret_cast<mg_v2d *>(x);
+        const mg_v2i *a2 = reinterpret_cast<const mg_v2i *>(agg);
+        for (; i < n2; i += stride) {
+            const mg_v2d xv = __builtin_nontemporal_load(x2 + i);
+            const mg_v2i av = __builtin_nontemporal_load(a2 + i);
+            mg_v2d r;
+            r.x = __dadd_rn(xv.x, __dmul_rn(scale, ec[av.x]));
+            r.y = __dadd_rn(xv.y, __dmul_rn(scale, ec[av.y]));
+            x2[i] = r;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = __dadd_rn(x[n - 1], __dmul_rn(scale, ec[agg[n - 1]]));
+    } else {
+        for (; i < n; i += stride) x[i] = __dadd_rn(__builtin_nontemporal_load(x + i), __dmul_rn(scale, ec[agg[i]]));
+    }
+}
+
+bis_status launch_relax0(bis_ctx *ctx, double *x, const double *w, const double *b, int64_t n) {
+    const bool vec = aligned16(x) && aligned16(w) && aligned16(b) && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+    if (vec) hipLaunchKernelGGL((mg_relax0_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, w, b, n);
+    else hipLaunchKernelGGL((mg_relax0_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, w, b, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+bis_status launch_relax(bis_ctx *ctx, double *x, const double *w, const double *b, const double *y, int64_t n) {
+    const bool vec = aligned16(x) && aligned16(w) && aligned16(b) && aligned16(y) && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+    if (vec) hipLaunchKernelGGL((mg_relax_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, w, b, y, n);
+    else hipLaunchKernelGGL((mg_relax_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, w, b, y, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+bis_status launch_prolong(bis_ctx *ctx, double *x, const int32_t *agg, const double *ec, double scale, int64_t n) {
+    const bool vec = aligned16(x) && (reinterpret_cast<uintptr_t>(agg) & 7) == 0 && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+    if (vec) hipLaunchKernelGGL((mg_prolong_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, agg, ec, scale, n);
+    else hipLaunchKernelGGL((mg_prolong_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, agg, ec, scale, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+
+// ---- setup kernels -----------------------------------------------------------------------------------------------------
+// 32-bit mixing hash of the MIS key (include/bis_hip.h): two multiply-xorshift rounds
+__host__ __device__ __forceinline__ uint32_t mg_hash32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ unsigned long long mg_key(int32_t i) { return ((unsigned long long)mg_hash32((uint32_t)i) << 32) | (uint32_t)i; }
+
+enum { MG_AUX_BAD_DIAG, MG_AUX_UNDECIDED, MG_AUX_COUNT };
+
+// w_i and the diagonal check of one level: omega == 0: 1 / sum_j |a_ij| summed left to right in CRS order; omega > 0:
+// omega / a_ii (the first entry of the row on the diagonal).  A row without a diagonal entry, or with a zero there, is counted.
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_weights_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ col,
+                                                          const double *__restrict__ val, int64_t n, double omega, double *w,
+                                                          unsigned *aux) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        double sum = 0.0, d = 0.0;
+        bool have = false;
+        for (int64_t k = (int64_t)rp[i], e = (int64_t)rp[i + 1]; k < e; ++k) {
+            const double a = val[k];
+            sum = __dadd_rn(sum, fabs(a));
+            if (!have && (int64_t)col[k] == i) { d = a; have = true; }
+        }
+        if (!have || d == 0.0) { atomicAdd(&aux[MG_AUX_BAD_DIAG], 1u); w[i] = 0.0; }
+        else w[i] = omega > 0.0 ? omega / d : 1.0 / sum;
+    }
+}
+
+// row = ((z ny + y) nx + x) dof + d  ->  (((z/2) cy + y/2) cx + x/2) dof + d
+__global__ __launch_bounds__(kMgT) void mg_grid_agg_kernel(int64_t n, int64_t nx, int64_t ny, int64_t dof, int64_t cx, int64_t cy,
+                                                           int32_t *agg) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        const int64_t d = i % dof, node = i / dof;
+        const int64_t x = node % nx, t = node / nx, y = t % ny, z = t / ny;
+        agg[i] = (int32_t)((((z >> 1) * cy + (y >> 1)) * cx + (x >> 1)) * dof + d);
+    }
+}
+
+// MIS round, first half: an undecided row whose key is the largest among its undecided neighbours becomes a root of this
+// round (state = tag).  A neighbour that becomes a root in the same pass still counts as undecided (state 0 or tag: the same
+// decision whichever the reader sees), and two neighbours cannot both be the largest.  States: 0 undecided, 2 member,
+// >= 4 root (4 + the round it was found in).
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_mis_select_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ col, int64_t n, int *state,
+                                                             int tag) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        if (__hip_atomic_load(&state[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) continue;
+        const unsigned long long mine = mg_key((int32_t)i);
+        bool largest = true;
+        for (int64_t k = (int64_t)rp[i], e = (int64_t)rp[i + 1]; k < e && largest; ++k) {
+            const int32_t j = col[k];
+            if ((int64_t)j == i) continue;
+            const int sj = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((sj == 0 || sj == tag) && mg_key(j) > mine) largest = false;
+        }
+        if (largest) __hip_atomic_store(&state[i], tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// ... second half: an undecided row next to a root of this round becomes a member; the rows still undecided are counted
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_mis_join_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ col, int64_t n, int *state,
+                                                           int tag, unsigned *aux) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    unsigned left = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        if (__hip_atomic_load(&state[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) continue;
+        bool member = false;
+        for (int64_t k = (int64_t)rp[i], e = (int64_t)rp[i + 1]; k < e && !member; ++k) {
+            const int32_t j = col[k];
+            if ((int64_t)j == i) continue;
+            member = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tag;
+        }
+        if (member) __hip_atomic_store(&state[i], 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else ++left;
+    }
+    // one ticket per wave, not per row: the counter is one address (only "zero or not" is read, a saturated count would do)
+    for (int off = 32; off > 0; off >>= 1) left += __shfl_down(left, off, 64);
+    if ((threadIdx.x & 63) == 0 && left != 0) atomicAdd(&aux[MG_AUX_UNDECIDED], left);
+}
+__global__ __launch_bounds__(kMgT) void mg_root_flag_kernel(const int *__restrict__ state, int64_t n, int32_t *flag) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) flag[i] = state[i] >= 4 ? 1 : 0;
+}
+// roots are numbered by ascending row (root_no: the exclusive scan of the flags); a member joins the root neighbour with the
+// largest |a_ij|, the lowest column among equals
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_mis_assign_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ col,
+                                                             const double *__restrict__ val, int64_t n, const int *__restrict__ state,
+                                                             const int32_t *__restrict__ root_no, int32_t *agg) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        if (state[i] >= 4) { agg[i] = root_no[i]; continue; }
+        double best = -1.0;
+        int32_t best_j = -1;
+        for (int64_t k = (int64_t)rp[i], e = (int64_t)rp[i + 1]; k < e; ++k) {
+            const int32_t j = col[k];
+            if ((int64_t)j == i || state[j] < 4) continue;
+            const double a = fabs(val[k]);
+            if (best_j < 0 || a > best || (a == best && j < best_j)) { best = a; best_j = j; }
+        }
+        agg[i] = best_j >= 0 ? root_no[best_j] : 0; // (a member has a root neighbour: the rounds made it one)
+    }
+}
+
+__global__ __launch_bounds__(kMgT) void mg_iota_keys_kernel(const int32_t *__restrict__ agg, int64_t n, uint32_t *key, int32_t *idx) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) { key[i] = (uint32_t)agg[i]; idx[i] = (int32_t)i; }
+}
+// out[I] = the first position p in the ascending key[0, m) with key[p] >= I, for I in [0, count)
+template <typename K, typename O>
+__global__ __launch_bounds__(kMgT) void mg_lower_bound_kernel(const K *__restrict__ key, int64_t m, int64_t count, int shift, O *out) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t I = (int64_t)blockIdx.x * kMgT + threadIdx.x; I < count; I += stride) {
+        int64_t lo = 0, hi = m;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)(key[mid] >> shift) < I) lo = mid + 1; else hi = mid;
+        }
+        out[I] = (O)lo;
+    }
+}
+// every fine entry (r, c, v) -> key agg[r] << 32 | agg[c]; the values are copied beside it (the sort moves them)
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_entry_keys_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ col, int64_t n,
+                                                             const int32_t *__restrict__ agg, unsigned long long *key) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t r = (int64_t)blockIdx.x * kMgT + threadIdx.x; r < n; r += stride) {
+        const unsigned long long hi = (unsigned long long)(uint32_t)agg[r] << 32;
+        for (int64_t k = (int64_t)rp[r], e = (int64_t)rp[r + 1]; k < e; ++k) key[k] = hi | (uint32_t)agg[col[k]];
+    }
+}
+__global__ __launch_bounds__(kMgT) void mg_head_flag_kernel(const unsigned long long *__restrict__ key, int64_t m, int64_t *flag) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t k = (int64_t)blockIdx.x * kMgT + threadIdx.x; k < m; k += stride) flag[k] = (k == 0 || key[k] != key[k - 1]) ? 1 : 0;
+}
+// pos: the inclusive scan of the head flags (entry k belongs to run pos[k] - 1).  The head of run e records where the run starts and the run's (row, column).
+__global__ __launch_bounds__(kMgT) void mg_heads_kernel(const unsigned long long *__restrict__ key, const int64_t *__restrict__ pos, int64_t m,
+                                                        int64_t *start, int32_t *row_c, int32_t *col_c) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t k = (int64_t)blockIdx.x * kMgT + threadIdx.x; k < m; k += stride) {
+        if (k != 0 && key[k] == key[k - 1]) continue;
+        const int64_t e = pos[k] - 1;
+        start[e] = k;
+        row_c[e] = (int32_t)(key[k] >> 32);
+        col_c[e] = (int32_t)(key[k] & 0xffffffffull);
+    }
+}
+// a lane per coarse entry: the sum of its run in the sorted (= fine CRS) order, the first value starting it
+__global__ __launch_bounds__(kMgT) void mg_run_sum_kernel(const double *__restrict__ v, const int64_t *__restrict__ start, int64_t m_c,
+                                                          int64_t m, double *val_c) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t e = (int64_t)blockIdx.x * kMgT + threadIdx.x; e < m_c; e += stride) {
+        const int64_t s = start[e], t = e + 1 < m_c ? start[e + 1] : m;
+        double acc = v[s];
+        for (int64_t k = s + 1; k < t; ++k) acc = __dadd_rn(acc, v[k]);
+        val_c[e] = acc;
+    }
+}
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 16)); }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+#define MG_CHECK(call)                                                                                                 \
+    do {                                                                                                               \
+        hipError_t e_ = (call);                                                                                        \
+        if (e_ != hipSuccess) { ctx->err = std::string("bis_mg_create: " #call ": ") + hipGetErrorString(e_); return BIS_ERR_HIP; } \
+    } while (0)
+
+bis_status read_aux(bis_ctx *ctx, const unsigned *aux, unsigned *host) {
+    MG_CHECK(hipGetLastError());
+    MG_CHECK(hipMemcpyAsync(host, aux, sizeof(unsigned) * MG_AUX_COUNT, hipMemcpyDeviceToHost, ctx->stream));
+    MG_CHECK(hipStreamSynchronize(ctx->stream));
+    return BIS_OK;
+}
+
+// weights of level L and its diagonal check
+template <typename RP>
+bis_status level_weights(bis_ctx *ctx, bis_mg_level &L, double omega, unsigned *aux) {
+    MG_CHECK(hipMalloc(&L.w, sizeof(double) * (size_t)std::max<int64_t>(L.n, 2)));
+    MG_CHECK(hipMemsetAsync(aux, 0, sizeof(unsigned) * MG_AUX_COUNT, ctx->stream));
+    hipLaunchKernelGGL(mg_weights_kernel<RP>, dim3(mg_grid(L.n)), dim3(kMgT), 0, ctx->stream, (const RP *)L.A->row_ptr, L.A->col, L.A->val,
+                       L.n, omega, L.w, aux);
+    unsigned h[MG_AUX_COUNT] = {0};
+    if (bis_status st = read_aux(ctx, aux, h)) return st;
+    if (h[MG_AUX_BAD_DIAG]) {
+        ctx->err = "bis_mg_create: a row without a diagonal entry, or with a zero on the diagonal";
+        return BIS_ERR_ZERO_DIAG;
+    }
+    return BIS_OK;
+}
+
+// MIS aggregates of level L into agg; *n_coarse = the number of roots
+template <typename RP>
+bis_status mis_aggregates(bis_ctx *ctx, const bis_mg_level &L, int32_t *agg, int64_t *n_coarse, unsigned *aux) {
+    const int64_t n = L.n;
+    const RP *rp = (const RP *)L.A->row_ptr;
+    bool symmetric = true;
+    if (bis_status st = bis_mat_pattern_symmetric(ctx, L.A, &symmetric)) return st;
+    if (!symmetric) {
+        ctx->err = "bis_mg_create: MIS aggregates need a structurally symmetric pattern without repeated entries";
+        return BIS_ERR_UNSUPPORTED;
+    }
+    DevBuf state, flag, root_no, tmp;
+    MG_CHECK(state.alloc(sizeof(int) * (size_t)n));
+    MG_CHECK(flag.alloc(sizeof(int32_t) * (size_t)n));
+    MG_CHECK(root_no.alloc(sizeof(int32_t) * (size_t)n));
+    MG_CHECK(hipMemsetAsync(state.p, 0, sizeof(int) * (size_t)n, ctx->stream));
+    const dim3 grid(mg_grid(n));
+    for (int round = 0;; ++round) { // every round decides at least the undecided row with the largest key
+        const int tag = 4 + round;
+        MG_CHECK(hipMemsetAsync(aux, 0, sizeof(unsigned) * MG_AUX_COUNT, ctx->stream));
+        hipLaunchKernelGGL(mg_mis_select_kernel<RP>, grid, dim3(kMgT), 0, ctx->stream, rp, L.A->col, n, state.as<int>(), tag);
+        hipLaunchKernelGGL(mg_mis_join_kernel<RP>, grid, dim3(kMgT), 0, ctx->stream, rp, L.A->col, n, state.as<int>(), tag, aux);
+        unsigned h[MG_AUX_COUNT] = {0};
+        if (bis_status st = read_aux(ctx, aux, h)) return st;
+        if (h[MG_AUX_UNDECIDED] == 0) break;
+        if ((int64_t)round > n) { ctx->err = "bis_mg_create: the MIS rounds do not end (internal)"; return BIS_ERR_INVALID; }
+    }
+    hipLaunchKernelGGL(mg_root_flag_kernel, grid, dim3(kMgT), 0, ctx->stream, state.as<int>(), n, flag.as<int32_t>());
+    size_t bytes = 0;
+    MG_CHECK(rocprim::exclusive_scan(nullptr, bytes, flag.as<int32_t>(), root_no.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(),
+                                     ctx->stream));
+    MG_CHECK(tmp.alloc(bytes));
+    MG_CHECK(rocprim::exclusive_scan(tmp.p, bytes, flag.as<int32_t>(), root_no.as<int32_t>(), (int32_t)0, (size_t)n, rocprim::plus<int32_t>(),
+                                     ctx->stream));
+    hipLaunchKernelGGL(mg_mis_assign_kernel<RP>, grid, dim3(kMgT), 0, ctx->stream, rp, L.A->col, L.A->val, n, state.as<int>(),
+                       root_no.as<int32_t>(), agg);
+    int32_t last[2] = {0, 0};
+    MG_CHECK(hipGetLastError());
+    MG_CHECK(hipMemcpyAsync(&last[0], root_no.as<int32_t>() + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MG_CHECK(hipMemcpyAsync(&last[1], flag.as<int32_t>() + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MG_CHECK(hipStreamSynchronize(ctx->stream));
+    *n_coarse = (int64_t)last[0] + last[1];
+    return BIS_OK;
+}
+
+// agg_ptr / agg_idx of level L from its aggregates: a stable sort of (aggregate, row)
+bis_status members_lists(bis_ctx *ctx, bis_mg_level &L) {
+    const int64_t n = L.n, nc = L.n_coarse;
+    DevBuf key, key_out, idx, tmp;
+    MG_CHECK(key.alloc(4 * (size_t)n));
+    MG_CHECK(key_out.alloc(4 * (size_t)n));
+    MG_CHECK(idx.alloc(4 * (size_t)n));
+    MG_CHECK(hipMalloc(&L.agg_idx, 4 * (size_t)n));
+    MG_CHECK(hipMalloc(&L.agg_ptr, 4 * (size_t)(nc + 1)));
+    hipLaunchKernelGGL(mg_iota_keys_kernel, dim3(mg_grid(n)), dim3(kMgT), 0, ctx->stream, L.agg, n, key.as<uint32_t>(), idx.as<int32_t>());
+    size_t bytes = 0;
+    MG_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key.as<uint32_t>(), key_out.as<uint32_t>(), idx.as<int32_t>(), L.agg_idx, (size_t)n, 0, 32,
+                                       ctx->stream));
+    MG_CHECK(tmp.alloc(bytes));
+    MG_CHECK(rocprim::radix_sort_pairs(tmp.p, bytes, key.as<uint32_t>(), key_out.as<uint32_t>(), idx.as<int32_t>(), L.agg_idx, (size_t)n, 0, 32,
+                                       ctx->stream)); // stable: ascending rows inside an aggregate
+    hipLaunchKernelGGL((mg_lower_bound_kernel<uint32_t, int32_t>), dim3(mg_grid(nc + 1)), dim3(kMgT), 0, ctx->stream, key_out.as<uint32_t>(), n,
+                       nc + 1, 0, L.agg_ptr);
+    MG_CHECK(hipGetLastError());
+    MG_CHECK(hipStreamSynchronize(ctx->stream)); // (the temporaries go out of scope)
+    return BIS_OK;
+}
+
+// the Galerkin operator of level L for its aggregates
+template <typename RP>
+bis_status galerkin(bis_ctx *ctx, const bis_mg_level &L, bis_mat **out) {
+    const int64_t n = L.n, m = L.A->nnz, nc = L.n_coarse;
+    const RP *rp = (const RP *)L.A->row_ptr;
+    DevBuf key, key_out, val_out, tmp, start, row_c;
+    MG_CHECK(key.alloc(8 * (size_t)m));
+    MG_CHECK(key_out.alloc(8 * (size_t)m));
+    MG_CHECK(val_out.alloc(8 * (size_t)m));
+    hipLaunchKernelGGL(mg_entry_keys_kernel<RP>, dim3(mg_grid(n)), dim3(kMgT), 0, ctx->stream, rp, L.A->col, n, L.agg,
+                       key.as<unsigned long long>());
+    size_t bytes = 0;
+    MG_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key.as<unsigned long long>(), key_out.as<unsigned long long>(), (const double *)L.A->val,
+                                       val_out.as<double>(), (size_t)m, 0, 64, ctx->stream));
+    MG_CHECK(tmp.alloc(bytes));
+    MG_CHECK(rocprim::radix_sort_pairs(tmp.p, bytes, key.as<unsigned long long>(), key_out.as<unsigned long long>(), (const double *)L.A->val,
+                                       val_out.as<double>(), (size_t)m, 0, 64, ctx->stream)); // stable: a run keeps the fine CRS order
+    // the unsorted keys are done with: their buffer takes the head flags and, scanned in place, the runs' numbers + 1
+    int64_t *pos = key.as<int64_t>();
+    hipLaunchKernelGGL(mg_head_flag_kernel, dim3(mg_grid(m)), dim3(kMgT), 0, ctx->stream, key_out.as<unsigned long long>(), m, pos);
+    size_t bytes2 = 0;
+    MG_CHECK(rocprim::inclusive_scan(nullptr, bytes2, pos, pos, (size_t)m, rocprim::plus<int64_t>(), ctx->stream));
+    if (bytes2 > bytes) { hipFree(tmp.p); tmp.p = nullptr; MG_CHECK(tmp.alloc(bytes2)); }
+    MG_CHECK(rocprim::inclusive_scan(tmp.p, bytes2, pos, pos, (size_t)m, rocprim::plus<int64_t>(), ctx->stream));
+    int64_t last_pos = 0;
+    MG_CHECK(hipMemcpyAsync(&last_pos, pos + (m - 1), sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    MG_CHECK(hipStreamSynchronize(ctx->stream));
+    const int64_t m_c = last_pos; // (the runs up to and including the last entry's)
+    MG_CHECK(start.alloc(8 * (size_t)m_c));
+    MG_CHECK(row_c.alloc(4 * (size_t)m_c));
+    bis_mat *C = nullptr;
+    if (bis_status st = bis_mat_alloc(ctx, nc, nc, m_c, bis_want_rp64(m_c), &C)) return st;
+    hipLaunchKernelGGL(mg_heads_kernel, dim3(mg_grid(m)), dim3(kMgT), 0, ctx->stream, key_out.as<unsigned long long>(), pos, m,
+                       start.as<int64_t>(), row_c.as<int32_t>(), C->col);
+    hipLaunchKernelGGL(mg_run_sum_kernel, dim3(mg_grid(m_c)), dim3(kMgT), 0, ctx->stream, val_out.as<double>(), start.as<int64_t>(), m_c, m,
+                       C->val);
+    if (C->rp64)
+        hipLaunchKernelGGL((mg_lower_bound_kernel<int32_t, int64_t>), dim3(mg_grid(nc + 1)), dim3(kMgT), 0, ctx->stream, row_c.as<int32_t>(), m_c,
+                           nc + 1, 0, (int64_t *)C->row_ptr);
+    else
+        hipLaunchKernelGGL((mg_lower_bound_kernel<int32_t, int32_t>), dim3(mg_grid(nc + 1)), dim3(kMgT), 0, ctx->stream, row_c.as<int32_t>(), m_c,
+                           nc + 1, 0, (int32_t *)C->row_ptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        ctx->err = std::string("bis_mg_create: Galerkin product: ") + hipGetErrorString(e);
+        bis_mat_destroy(ctx, C);
+        return BIS_ERR_HIP;
+    }
+    *out = C;
+    return BIS_OK;
+}
+
+void free_level(bis_ctx *ctx, bis_mg_level &L) {
+    hipFree(L.w); hipFree(L.agg); hipFree(L.agg_ptr); hipFree(L.agg_idx); hipFree(L.x); hipFree(L.b); hipFree(L.y);
+    if (L.owned) bis_mat_destroy(ctx, L.owned);
+    L = bis_mg_level();
+}
+
+void mg_free(bis_ctx *ctx, bis_mg *mg) {
+    hipStreamSynchronize(ctx->stream);
+    for (bis_mg_level &L : mg->lv) free_level(ctx, L);
+    if (mg->operand) { mg->operand->mg = nullptr; bis_mat_destroy(ctx, mg->operand); }
+    hipFree(mg->b0);
+    delete mg;
+}
+
+bis_status mg_build(bis_ctx *ctx, const bis_mat *A, bis_mg *mg) {
+    const bis_mg_params &p = mg->p;
+    DevBuf auxb;
+    MG_CHECK(auxb.alloc(sizeof(unsigned) * MG_AUX_COUNT));
+    unsigned *aux = auxb.as<unsigned>();
+    mg->lv.reserve(kMgMaxLevels);
+    mg->lv.emplace_back();
+    mg->lv[0].A = A;
+    mg->lv[0].n = A->n_rows;
+    while (true) {
+        bis_mg_level &L = mg->lv.back();
+        if (L.n == 0) break;
+        if (bis_status st = L.A->rp64 ? level_weights<int64_t>(ctx, L, p.omega, aux) : level_weights<int32_t>(ctx, L, p.omega, aux)) return st;
+        if (L.n <= p.coarse_limit || (int)mg->lv.size() >= p.max_levels) break;
+        // the aggregates of this level
+        const int64_t *g = L.A->grid;
+        bool grid_ok = g[0] > 0 && g[1] > 0 && g[2] > 0 && g[3] > 0 && g[0] * g[1] * g[2] * g[3] == L.n;
+        if (p.coarsening == 1 && !grid_ok) {
+            ctx->err = "bis_mg_create: coarsening = grid, and a level has no grid hint that matches its size";
+            return BIS_ERR_INVALID;
+        }
+        if (p.coarsening == 2) grid_ok = false;
+        MG_CHECK(hipMalloc(&L.agg, 4 * (size_t)L.n));
+        int64_t nc = 0, cg[4] = {0, 0, 0, 0};
+        if (grid_ok) {
+            cg[0] = (g[0] + 1) / 2; cg[1] = (g[1] + 1) / 2; cg[2] = (g[2] + 1) / 2; cg[3] = g[3];
+            nc = cg[0] * cg[1] * cg[2] * cg[3];
+            hipLaunchKernelGGL(mg_grid_agg_kernel, dim3(mg_grid(L.n)), dim3(kMgT), 0, ctx->stream, L.n, g[0], g[1], g[3], cg[0], cg[1], L.agg);
+            MG_CHECK(hipGetLastError());
+        } else {
+            if (bis_status st = L.A->rp64 ? mis_aggregates<int64_t>(ctx, L, L.agg, &nc, aux) : mis_aggregates<int32_t>(ctx, L, L.agg, &nc, aux))
+                return st;
+        }
+        if (nc <= 0 || 5 * nc > 4 * L.n) { // n_{l+1} > 0.8 n_l: the step is dropped, this level is the coarsest
+            MG_CHECK(hipStreamSynchronize(ctx->stream));
+            hipFree(L.agg);
+            L.agg = nullptr;
+            break;
+        }
+        L.kind = grid_ok ? 1 : 2;
+        L.n_coarse = nc;
+        if (bis_status st = members_lists(ctx, L)) return st;
+        bis_mat *C = nullptr;
+        if (bis_status st = L.A->rp64 ? galerkin<int64_t>(ctx, L, &C) : galerkin<int32_t>(ctx, L, &C)) return st;
+        if (grid_ok) for (int k = 0; k < 4; ++k) C->grid[k] = cg[k];
+        if (bis_status st = bis_mat_finalize(ctx, C)) { bis_mat_destroy(ctx, C); return st; }
+        mg->lv.emplace_back(); // (reserved: L stays valid, but is not used below)
+        bis_mg_level &N = mg->lv.back();
+        N.A = N.owned = C;
+        N.n = nc;
+    }
+    // every level's SpMV form, and the cycle's scratch
+    for (size_t l = 0; l < mg->lv.size(); ++l) {
+        bis_mg_level &L = mg->lv[l];
+        if (L.n == 0) continue;
+        if (bis_status st = bis_mat_spmv_stream_info(ctx, L.A, nullptr, nullptr, nullptr, nullptr)) return st;
+        const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(L.n, 2);
+        MG_CHECK(hipMalloc(&L.y, bytes));
+        if (l > 0) { MG_CHECK(hipMalloc(&L.x, bytes)); MG_CHECK(hipMalloc(&L.b, bytes)); }
+    }
+    MG_CHECK(hipMalloc(&mg->b0, sizeof(double) * (size_t)std::max<int64_t>(A->n_rows, 2)));
+    if (bis_status st = bis_mat_alloc(ctx, A->n_rows, A->n_rows, 0, false, &mg->operand)) return st;
+    const size_t rpb = sizeof(int32_t) * (size_t)(A->n_rows + 1);
+    MG_CHECK(hipMemsetAsync(mg->operand->row_ptr, 0, rpb, ctx->stream));
+    if (bis_status st = bis_mat_finalize(ctx, mg->operand)) return st;
+    mg->operand->mg = mg;
+    MG_CHECK(hipStreamSynchronize(ctx->stream));
+    return BIS_OK;
+}
+
+// `sweeps` further sweeps x += w o (b - A x)
+bis_status smooth(bis_ctx *ctx, const bis_mg_level &L, double *x, const double *b, int sweeps) {
+    for (int s = 0; s < sweeps; ++s) {
+        if (bis_status st = bis_spmv_launch(ctx, L.A, x, L.y, nullptr, nullptr)) return st;
+        if (bis_status st = launch_relax(ctx, x, L.w, b, L.y, L.n)) return st;
+    }
+    return BIS_OK;
+}
+
+bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const double *b) {
+    const bis_mg_level &L = mg->lv[l];
+    if (bis_status st = launch_relax0(ctx, x, L.w, b, L.n)) return st;
+    if (l + 1 == mg->lv.size()) return smooth(ctx, L, x, b, mg->p.coarse_sweeps - 1);
+    if (bis_status st = smooth(ctx, L, x, b, mg->p.nu - 1)) return st;
+    const bis_mg_level &N = mg->lv[l + 1];
+    if (bis_status st = bis_spmv_launch(ctx, L.A, x, L.y, nullptr, nullptr)) return st;
+    hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_grid(N.n)), dim3(kMgT), 0, ctx->stream, L.agg_ptr, L.agg_idx, b, L.y, N.b, N.n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    if (bis_status st = cycle(ctx, mg, l + 1, N.x, N.b)) return st;
+    if (bis_status st = launch_prolong(ctx, x, L.agg, N.x, mg->p.coarse_scale, L.n)) return st;
+    return smooth(ctx, L, x, b, mg->p.nu);
+}
+
+} // namespace
+
+extern "C" {
+
+bis_status bis_mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, bis_mg **out) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, A && out, "bis_mg_create: bad arguments");
+    BIS_REQUIRE(ctx, A->n_rows == A->n_cols, "bis_mg_create: square matrix required");
+    BIS_REQUIRE(ctx, !A->view, "bis_mg_create: a row-range view has no diagonal block of its own");
+    bis_mg_params p = {10, 256, 0, 1, 4, 0.0, 1.0};
+    if (params) p = *params;
+    BIS_REQUIRE(ctx, p.max_levels >= 1 && p.max_levels <= kMgMaxLevels && p.coarse_limit >= 1 && p.coarsening >= 0 && p.coarsening <= 2 &&
+                         p.nu >= 1 && p.coarse_sweeps >= 1 && p.omega >= 0.0 && p.omega == p.omega && p.coarse_scale == p.coarse_scale,
+                "bis_mg_create: bad parameters (1 <= max_levels <= 16, coarse_limit >= 1, coarsening 0..2, nu >= 1, coarse_sweeps >= 1, omega >= 0)");
+    bis_mg *mg = new bis_mg;
+    mg->p = p;
+    const bis_status st = mg_build(ctx, A, mg);
+    if (st != BIS_OK) { mg_free(ctx, mg); return st; }
+    *out = mg;
+    return BIS_OK;
+}
+
+bis_status bis_mg_destroy(bis_ctx *ctx, bis_mg *mg) {
+    BIS_CTX_OK(ctx);
+    if (mg) mg_free(ctx, mg);
+    return BIS_OK;
+}
+
+bis_status bis_mg_apply(bis_ctx *ctx, const bis_mg *mg, double *out, const double *in) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, mg, "bis_mg_apply: bad arguments");
+    const int64_t n = mg->lv[0].n;
+    if (n == 0) return BIS_OK;
+    BIS_REQUIRE(ctx, out && in, "bis_mg_apply: null vector");
+    const double *b = in;
+    if (out == in) { // the sweeps read the right-hand side after the first one wrote x
+        BIS_HIP_CHECK(ctx, hipMemcpyAsync(mg->b0, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+        b = mg->b0;
+    }
+    return cycle(ctx, mg, 0, out, b);
+}
+
+const bis_mat *bis_mg_operand(const bis_mg *mg) { return mg ? mg->operand : nullptr; }
+
+bis_status bis_mg_info(const bis_mg *mg, int *levels, int64_t *rows, int64_t *nnz, int *kind) {
+    if (!mg) return BIS_ERR_INVALID;
+    if (levels) *levels = (int)mg->lv.size();
+    for (size_t l = 0; l < mg->lv.size(); ++l) {
+        if (rows) rows[l] = mg->lv[l].n;
+        if (nnz) nnz[l] = mg->lv[l].A->nnz;
+        if (kind) kind[l] = mg->lv[l].kind;
+    }
+    return BIS_OK;
+}
+
+const bis_mat *bis_mg_level_matrix(const bis_mg *mg, int level) {
+    return (mg && level >= 0 && (size_t)level < mg->lv.size()) ? mg->lv[(size_t)level].A : nullptr;
+}
+
+bis_status bis_mg_level_aggregates(bis_ctx *ctx, const bis_mg *mg, int level, int32_t *host) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, mg && host && level >= 0 && (size_t)level < mg->lv.size(), "bis_mg_level_aggregates: bad arguments");
+    const bis_mg_level &L = mg->lv[(size_t)level];
+    BIS_REQUIRE(ctx, L.kind != 0, "bis_mg_level_aggregates: the coarsest level has no aggregates");
+    BIS_HIP_CHECK(ctx, hipMemcpyAsync(host, L.agg, sizeof(int32_t) * (size_t)L.n, hipMemcpyDeviceToHost, ctx->stream));
+    BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return BIS_OK;
+}
+
+bis_status bis_mg_level_weights(bis_ctx *ctx, const bis_mg *mg, int level, double *host) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, mg && host && level >= 0 && (size_t)level < mg->lv.size(), "bis_mg_level_weights: bad arguments");
+    const bis_mg_level &L = mg->lv[(size_t)level];
+    if (L.n == 0) return BIS_OK;
+    BIS_HIP_CHECK(ctx, hipMemcpyAsync(host, L.w, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToHost, ctx->stream));
+    BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return BIS_OK;
+}
+
+} // extern "C"

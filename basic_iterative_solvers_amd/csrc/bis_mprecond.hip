@@ -88,6 +88,7 @@ bis_status bis_mapply_preconditioner(bis_ctx *ctx, int pc, int64_t n, int n_rhs,
                                      const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D, double *OUT,
                                      double *IN, double *TMP, double *WORK, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
+    if (pc == BIS_PC_MG) { ctx->err = "bis_mapply_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
     BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1 && pc >= BIS_PC_NONE && pc <= BIS_PC_FSAI, "bis_mapply_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, n_rhs >= 1 && n_rhs <= kMpMaxK, "bis_mapply_preconditioner: n_rhs must be between 1 and 8");
     if (pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {

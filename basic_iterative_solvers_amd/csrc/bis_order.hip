@@ -393,6 +393,34 @@ bis_status bfs_order_t(bis_ctx *ctx, const bis_mat *A, bool rcm, int32_t *perm_d
 
 } // namespace
 
+// the check bfs_order_t starts with, for other callers (bis_mg.hip): *symmetric = every off-diagonal entry has its mirror and
+// no row holds a column twice.  Blocking.
+bis_status bis_mat_pattern_symmetric(bis_ctx *ctx, const bis_mat *A, bool *symmetric) {
+    const int64_t n = A->n_rows;
+    *symmetric = true;
+    if (n == 0) return BIS_OK;
+    int *deg = nullptr, *status = nullptr;
+    auto cleanup = [&](bis_status rc) { hipFree(deg); hipFree(status); return rc; };
+#define SYM_CHECK(call)                                                                                                    \
+    do {                                                                                                                   \
+        hipError_t e_ = (call);                                                                                            \
+        if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return cleanup(BIS_ERR_HIP); } \
+    } while (0)
+    SYM_CHECK(hipMalloc(&deg, 4 * (size_t)n));
+    SYM_CHECK(hipMalloc(&status, sizeof(int) * 8));
+    SYM_CHECK(hipMemsetAsync(status, 0, sizeof(int) * 8, ctx->stream));
+    const dim3 grid((unsigned)((n + 3) / 4));
+    if (A->rp64) hipLaunchKernelGGL(symmetry_kernel<int64_t>, grid, dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, n, deg, status);
+    else hipLaunchKernelGGL(symmetry_kernel<int32_t>, grid, dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, n, deg, status);
+    int hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    SYM_CHECK(hipGetLastError());
+    SYM_CHECK(hipMemcpyAsync(hs, status, sizeof hs, hipMemcpyDeviceToHost, ctx->stream));
+    SYM_CHECK(hipStreamSynchronize(ctx->stream));
+    *symmetric = !(hs[0] | (hs[6] != 0) | (hs[7] != 0));
+    return cleanup(BIS_OK);
+#undef SYM_CHECK
+}
+
 extern "C" {
 
 bis_status bis_mat_permute(bis_ctx *ctx, const bis_mat *A, const int32_t *perm_dev, bis_mat **B) {

@@ -51,9 +51,9 @@
 using Interface = void *; // the SMAX seam of the reference (common.hpp:18-24) is the C ABI here
 #define SMAX_ARGS(...)
 
-enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8) and FSAI (9) are this build's additions
+enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8), FSAI (9) and MG (10) are this build's additions
     None, Jacobi, GaussSeidel, BackwardsGaussSeidel, SymmetricGaussSeidel, TwoStageGS,
-    SymmetricTwoStageGS, ILU0, ILU0Iter, FSAI
+    SymmetricTwoStageGS, ILU0, ILU0Iter, FSAI, MG
 };
 
 // -inner K: inner sweeps of the two-stage Gauss-Seidel types and of -p ilu0it, at run time; the default is the
@@ -62,6 +62,8 @@ inline int &precond_inner_iters() { static int k = PRECOND_INNER_ITERS; return k
 // -pprec 32|64: the values of the factors that -p fsai and -p ilu0it apply by SpMV are rounded to fp32 after the
 // factorisation (bis_mat_round_f32); 64, the default, leaves them as they are
 inline int &precond_value_bits() { static int b = 64; return b; }
+// -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis: the parameters of -p mg (bis_mg_params; these are its defaults)
+inline bis_mg_params &precond_mg_params() { static bis_mg_params p = {10, 256, 0, 1, 4, 0.0, 1.0}; return p; }
 enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB };
 
 inline std::string to_string(PrecondType t) {
@@ -70,6 +72,7 @@ inline std::string to_string(PrecondType t) {
                               "symmetric two-stage gauss-seidel", "incomplete LU(0)"};
     if (t == PrecondType::ILU0Iter) return "incomplete LU(0), iterative solves (" + std::to_string(precond_inner_iters()) + ")";
     if (t == PrecondType::FSAI) return "factorized sparse approximate inverse";
+    if (t == PrecondType::MG) return "aggregation multigrid";
     return n[static_cast<int>(t)];
 }
 inline std::string to_string(SolverType t) {

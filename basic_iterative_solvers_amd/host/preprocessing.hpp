@@ -2,7 +2,7 @@
 // allocate + initialise the solver's vectors, optional symmetric diagonal
 // scaling, split A into its strict triangles and diagonal (on the device for
 // generated matrices, on the host for file input), optional ILU(0) or FSAI
-// factors, initial residual and stopping criterion.
+// factors or the multigrid hierarchy, initial residual and stopping criterion.
 #pragma once
 
 #include "common.hpp"
@@ -74,6 +74,25 @@ inline void factor_LU(Solver *s) {
         s->U_strict->adopt(Gt);
         if (n_fallback != 0) std::cout << "fsai: " << n_fallback << " rows fell back to 1/sqrt(|a_ii|)" << std::endl;
         round_precond_factors(s);
+    }
+    if (s->preconditioner == PrecondType::MG) {
+        // -p mg: the hierarchy of A (after -scale and -perm); its operand takes the place of the strict lower triangle
+        const bis_status st = bis_mg_create(bis::ctx(), s->A->dev, &precond_mg_params(), &s->mg);
+        if (st == BIS_ERR_ZERO_DIAG || st == BIS_ERR_UNSUPPORTED || st == BIS_ERR_INVALID) { fprintf(stderr, "%s\n", bis_last_error(bis::ctx())); exit(EXIT_FAILURE); }
+        bis::check(st, "bis_mg_create");
+        s->L_strict->free_host();
+        s->L_strict->adopt(const_cast<bis_mat *>(bis_mg_operand(s->mg)));
+        int levels = 0, kind[16];
+        int64_t rows[16], nnz[16];
+        bis_mg_info(s->mg, &levels, rows, nnz, kind);
+        double total = 0.0;
+        for (int l = 0; l < levels; ++l) total += (double)nnz[l];
+        std::cout << "multigrid: " << levels << " levels, rows";
+        for (int l = 0; l < levels; ++l) std::cout << (l ? " / " : " ") << rows[l];
+        std::cout << ", operator complexity " << (nnz[0] > 0 ? total / (double)nnz[0] : 1.0) << ", aggregates";
+        for (int l = 0; l + 1 < levels; ++l) std::cout << (l ? " / " : " ") << (kind[l] == 1 ? "grid" : "mis");
+        if (levels < 2) std::cout << " none";
+        std::cout << std::endl;
     }
 }
 

@@ -40,6 +40,8 @@ class Solver {
     // -perm: perm[new] = old as int32 in device storage (nullptr: natural order).  The solve runs on
     // P A P^T; unpermute_x_star() returns x* in the caller's row order.
     double *perm_store = nullptr;
+    // -p mg: the hierarchy; its operand sits in L_strict->dev, where bis_apply_preconditioner and bis_cg_set_preconditioner look for it
+    bis_mg *mg = nullptr;
     void keep_permutation(const std::vector<int> &perm) {
         const long n = (long)perm.size();
         std::vector<double> raw((n + 1) / 2 + 1, 0.0);
@@ -91,6 +93,10 @@ class Solver {
         double *v[] = {x_star, x_0, b, tmp, work, residual, residual_0, A_D, A_D_inv, A_D_scale, L_D, U_D};
         for (auto p : v) dfree(p);
         dfree(perm_store);
+        if (mg) { // the operand belongs to the hierarchy
+            if (L_strict) L_strict->dev = nullptr;
+            bis_mg_destroy(bis::ctx(), mg);
+        }
         delete[] collected_residual_norms;
         delete[] time_per_iteration;
     }

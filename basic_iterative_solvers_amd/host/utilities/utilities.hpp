@@ -8,7 +8,8 @@
 // `-perm mc` applies the multi-colour reordering of utilities/permute.hpp; `-p ilu0it` is ILU(0) with iterative
 // triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st); `-p fsai` is the
 // factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs; `-pprec 32` rounds the factors those two
-// types apply by SpMV to fp32 (bis_mat_round_f32).
+// types apply by SpMV to fp32 (bis_mat_round_f32); `-p mg` is one V-cycle of the aggregation multigrid hierarchy of bis_mg_create
+// and `-mg key=value,...` sets its parameters.
 #pragma once
 
 #include <sys/stat.h>
@@ -51,7 +52,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 {"bgs", PrecondType::BackwardsGaussSeidel}, {"sgs", PrecondType::SymmetricGaussSeidel},
                 {"2st", PrecondType::TwoStageGS}, {"s2st", PrecondType::SymmetricTwoStageGS},
                 {"ilu0", PrecondType::ILU0}, {"ilu0it", PrecondType::ILU0Iter},
-                {"fsai", PrecondType::FSAI}};
+                {"fsai", PrecondType::FSAI}, {"mg", PrecondType::MG}};
             auto it = pcs.find(pt);
             if (it == pcs.end()) {
                 fprintf(stderr, "ERROR: assign_cli_inputs: Please choose an available preconditioner type: "
@@ -59,7 +60,8 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                                 "\n-p sgs (Symmetric Gauss-Seidel)\n-p 2st (2 Stage Gauss-Seidel)"
                                 "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)"
                                 "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)"
-                                "\n-p fsai (Factorized sparse approximate inverse on the pattern of tril(A))\n");
+                                "\n-p fsai (Factorized sparse approximate inverse on the pattern of tril(A))"
+                                "\n-p mg (Aggregation multigrid V-cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis)\n");
                 exit(EXIT_FAILURE);
             }
             a->preconditioner = it->second;
@@ -81,6 +83,28 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             }
             precond_value_bits() = a->pprec;
         }
+        else if (arg == "-mg" && i + 1 < argc) {
+            bis_mg_params &p = precond_mg_params();
+            std::stringstream ss(argv[++i]);
+            std::string item;
+            while (std::getline(ss, item, ',')) {
+                const size_t eq = item.find('=');
+                const std::string k = item.substr(0, eq), v = eq == std::string::npos ? "" : item.substr(eq + 1);
+                bool ok = !v.empty();
+                if (k == "nu") p.nu = atoi(v.c_str());
+                else if (k == "cs") p.coarse_sweeps = atoi(v.c_str());
+                else if (k == "limit") p.coarse_limit = atoll(v.c_str());
+                else if (k == "levels") p.max_levels = atoi(v.c_str());
+                else if (k == "scale") p.coarse_scale = atof(v.c_str());
+                else if (k == "omega") p.omega = atof(v.c_str());
+                else if (k == "coarsening" && (v == "auto" || v == "grid" || v == "mis")) p.coarsening = v == "auto" ? 0 : v == "grid" ? 1 : 2;
+                else ok = false;
+                if (!ok) {
+                    fprintf(stderr, "ERROR: -mg nu=K,cs=K,limit=N,levels=K,scale=S,omega=W,coarsening=auto|grid|mis: cannot read \"%s\"\n", item.c_str());
+                    exit(EXIT_FAILURE);
+                }
+            }
+        }
         else if (arg == "-unfused") a->unfused = true;
         else if (arg == "-hostscalars") a->host_scalars = true;
         else if (arg == "-trsv" && i + 1 < argc) {
@@ -100,6 +124,11 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else if (arg == "-cache" && i + 1 < argc) a->crs_cache = argv[++i];
         else if (arg == "-dev" && i + 1 < argc) a->device = atoi(argv[++i]);
         else std::cout << "ERROR: assign_cli_inputs: Arguement \"" << arg << "\" not recongnized." << std::endl;
+    }
+    if (a->preconditioner == PrecondType::MG && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
+        a->method != SolverType::BiCGSTAB) {
+        fprintf(stderr, "ERROR: -p mg needs a Krylov method: -cg, -gm or -bi\n");
+        exit(EXIT_FAILURE);
     }
     // the other types run exact sweeps on the fp64 arrays and would gain nothing from rounded values
     if (a->pprec == 32 && a->preconditioner != PrecondType::FSAI && a->preconditioner != PrecondType::ILU0Iter) {

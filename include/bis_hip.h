@@ -68,7 +68,9 @@ enum {
     /* not in the reference: ILU(0) whose two triangular solves are bis_itrsv with inner_iters steps each */
     BIS_PC_ILU0_ITER = 8,
     /* not in the reference: factorized sparse approximate inverse, M^-1 = Gt G with the factors of bis_mat_fsai */
-    BIS_PC_FSAI = 9
+    BIS_PC_FSAI = 9,
+    /* not in the reference: aggregation multigrid, one V-cycle of a bis_mg hierarchy (bis_mg_create) */
+    BIS_PC_MG = 10
 };
 
 typedef struct bis_ctx bis_ctx; /* device + stream + scratch (SMAX::Interface
@@ -190,6 +192,8 @@ BIS_API bis_status bis_mat_spmv_streamed_bytes(bis_ctx *ctx, const bis_mat *A,
  * verified against the dependencies, else the natural order is used). */
 BIS_API bis_status bis_mat_set_grid_hint(bis_mat *A, int64_t nx, int64_t ny,
                                          int64_t nz, int dof);
+/* the hint a matrix carries: hint[0..3] = nx, ny, nz, dof; all 0 without one */
+BIS_API bis_status bis_mat_grid_hint(const bis_mat *A, int64_t hint[4]);
 /* rebuild a matrix' row-block metadata after bis_set_option (tuning) */
 BIS_API bis_status bis_mat_retune(bis_ctx *ctx, bis_mat *A);
 /* Placement tuning (setup, optional): WHERE in HBM the streamed arrays of a matrix
@@ -383,6 +387,73 @@ BIS_API const char *bis_mat_ilu0_kernel(const bis_mat *L_strict);
 BIS_API bis_status bis_mat_fsai(bis_ctx *ctx, const bis_mat *A, bis_mat **G, bis_mat **Gt, int64_t *n_fallback_rows);
 BIS_API const char *bis_mat_fsai_kernel(const bis_mat *G);
 
+/* ---- aggregation multigrid (bis_mg.hip); no reference counterpart ------------------------------------------------------
+ * Unsmoothed aggregation, one V(nu,nu) cycle with Jacobi-type smoothing as the preconditioner: SpMVs and streaming passes
+ * only, no dependency between rows, any row order.
+ *
+ * Parameters (NULL = the defaults): max_levels 10 (1..16); coarse_limit 256 (>= 1): a level of at most this many rows is
+ * not coarsened; coarsening 0 = grid aggregates where the level has a grid hint whose product is its size, MIS aggregates
+ * otherwise, 1 = grid only (BIS_ERR_INVALID where a level has no such hint), 2 = MIS only; nu 1 (>= 1): sweeps before and
+ * after the coarse correction; coarse_sweeps 4 (>= 1): sweeps on the coarsest level; omega 0: l1-Jacobi,
+ * w_i = 1 / sum_j |a_ij| with the sum taken left to right in CRS order from 0, omega > 0: damped Jacobi,
+ * w_i = omega / a_ii (the first entry of row i on the diagonal); coarse_scale 1.0: factor on the coarse correction.
+ *
+ * Levels.  Level 0 is A itself: not copied, the caller keeps it alive and unchanged while the hierarchy lives.  Level l
+ * (n_l rows) is the coarsest if n_l <= coarse_limit, or if it is level max_levels - 1, or if its aggregates number more
+ * than 0.8 n_l (5 n_{l+1} > 4 n_l: the step is dropped, level l + 1 is not built).  kind[l]: 1 grid, 2 MIS, 0 coarsest.
+ *
+ * Grid aggregates of a level with hint (nx, ny, nz, dof), row = ((z ny + y) nx + x) dof + d:
+ * agg = (((z/2) cy + y/2) cx + x/2) dof + d, cx = (nx+1)/2, cy, cz alike; the coarse matrix gets the hint (cx, cy, cz, dof).
+ *
+ * MIS aggregates (any structurally symmetric pattern without repeated entries; otherwise BIS_ERR_UNSUPPORTED, as
+ * bis_mat_bfs_order).  The roots are the greedy maximal independent set of the off-diagonal pattern taken in descending
+ * order of the key (hash32(i), i), hash32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ * on 32-bit unsigned x.  Found in rounds (an undecided row whose key is the largest among its undecided neighbours becomes
+ * a root, its undecided neighbours members), which gives that set whatever the schedule; the host reads one counter per
+ * round.  A row without off-diagonal entries is a root.  A member joins the root among its neighbours with the largest
+ * |a_ij|, the lowest column among equals.  Aggregates are numbered by ascending root row.
+ *
+ * Galerkin operator for the piecewise-constant prolongation: entry (I, J) of level l + 1 is the sum of the fine entries
+ * (r, c, v) with agg[r] = I, agg[c] = J, taken in fine CRS order (ascending r, then the order inside row r), the first value
+ * starting the sum and every further one added to it in fp64.  Only pairs (I, J) with a fine entry exist; columns ascend
+ * inside a row; the row-pointer width follows the library's rule (option force_rp64 honoured).  The two mirror entries of a
+ * symmetric A are summed in different orders: the coarse matrices are symmetric to rounding only.
+ *
+ * BIS_ERR_INVALID: null arguments, A not square, a row-range view, bad parameters; BIS_ERR_ZERO_DIAG: a row of some level
+ * without a diagonal entry or with a zero there; n = 0: BIS_OK (one level without rows).  *out is written on success only.
+ * Blocking; everything runs on the device without floating-point atomics: two calls give the same bits.  Setup also
+ * resolves every level's SpMV form and allocates the cycle's scratch: bis_mg_apply allocates nothing and never blocks. */
+typedef struct bis_mg bis_mg;
+typedef struct {
+    int max_levels;
+    int64_t coarse_limit;
+    int coarsening;
+    int nu;
+    int coarse_sweeps;
+    double omega;
+    double coarse_scale;
+} bis_mg_params;
+BIS_API bis_status bis_mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, bis_mg **out);
+BIS_API bis_status bis_mg_destroy(bis_ctx *ctx, bis_mg *mg);
+/* out = M^-1 in: one V-cycle, stream-ordered; out may alias in (the right-hand side is then copied first).  On level l with
+ * right-hand side b, every product, subtraction and addition rounded separately (no fused multiply-add), y = A x by bis_spmv:
+ *   x = w o b;  then nu - 1 sweeps  y = A x, x_i = x_i + w_i (b_i - y_i);
+ *   y = A x;  r_c[I] = sum over the rows i of aggregate I in ascending order of (b_i - y_i), the first difference starting the
+ *   sum;  e_c = the cycle of level l + 1 on r_c;  x_i = x_i + coarse_scale e_c[agg[i]];  then nu sweeps as above.
+ * The coarsest level: x = w o b, then coarse_sweeps - 1 sweeps. */
+BIS_API bis_status bis_mg_apply(bis_ctx *ctx, const bis_mg *mg, double *out, const double *in);
+/* The hierarchy as the preconditioner of type BIS_PC_MG: an n x n matrix without entries that mg owns (bis_mat_destroy on it
+ * does nothing) and that leads back to mg; every entry point but the preconditioner dispatch sees the zero matrix. */
+BIS_API const bis_mat *bis_mg_operand(const bis_mg *mg);
+/* *levels, and per level (arrays of 16) rows, non-zeros and the aggregate kind; any pointer may be NULL. */
+BIS_API bis_status bis_mg_info(const bis_mg *mg, int *levels, int64_t *rows, int64_t *nnz, int *kind);
+/* Level l's matrix (level 0: A), owned by mg: for bis_mat_download, bis_mat_grid_hint, bis_mat_spmv_stream_info.  NULL
+ * outside the hierarchy. */
+BIS_API const bis_mat *bis_mg_level_matrix(const bis_mg *mg, int level);
+/* agg[0, n_l) of a level that is not the coarsest, and w[0, n_l) of any level, to host arrays.  Blocking. */
+BIS_API bis_status bis_mg_level_aggregates(bis_ctx *ctx, const bis_mg *mg, int level, int32_t *host);
+BIS_API bis_status bis_mg_level_weights(bis_ctx *ctx, const bis_mg *mg, int level, double *host);
+
 /* ---- the operator surface (kernels.hpp) ------------------------------------ */
 /* spmv / native_spmv, kernels.hpp:22-52: y = A x. */
 BIS_API bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x,
@@ -543,7 +614,10 @@ BIS_API const char *bis_itrsv_kernel(const bis_mat *T_strict);
  * distinct from each other and from output and input (BIS_ERR_INVALID); output may alias input.
  * BIS_PC_FSAI (9): tmp = bis_spmv(L_strict, input), then output = bis_spmv(U_strict, tmp), with G in the L_strict and Gt
  * in the U_strict argument (bis_mat_fsai).  The diagonal arguments and work are not read; tmp is required and must be
- * distinct from input and output (BIS_ERR_INVALID); output may alias input. */
+ * distinct from input and output (BIS_ERR_INVALID); output may alias input.
+ * BIS_PC_MG (10): output = bis_mg_apply(input) of the hierarchy whose operand (bis_mg_operand) is in the L_strict argument;
+ * the operand must have n rows (BIS_ERR_INVALID), no other argument is read, output may alias input; outer_iters != 1:
+ * BIS_ERR_UNSUPPORTED. */
 BIS_API bis_status bis_apply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
@@ -593,7 +667,8 @@ BIS_API bis_status bis_mitrsv(bis_ctx *ctx, const bis_mat *T_strict, const doubl
  * with bis_sptrsm's proviso; ILU0_ITER: with bis_mitrsv's).  BIS_PC_TWO_STAGE_GS, BIS_PC_SYMMETRIC_TWO_STAGE_GS and outer_iters != 1:
  * BIS_ERR_UNSUPPORTED.  TMP, WORK: n x n_rhs blocks, needed by SGS / ILU0 / ILU0_ITER / FSAI (TMP) and ILU0_ITER (WORK).
  * FSAI: two bis_spmm, TMP distinct from IN and OUT; column j equals the single-vector apply wherever bis_spmm's column j
- * equals bis_spmv's (every matrix that does not run the wave-per-row SpMV). */
+ * equals bis_spmv's (every matrix that does not run the wave-per-row SpMV).  BIS_PC_MG has no multi-vector form:
+ * BIS_ERR_UNSUPPORTED here and in bis_mcg_set_preconditioner, bis_mbicgstab_set_preconditioner, bis_mgmres_set_preconditioner. */
 BIS_API bis_status bis_mapply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, int n_rhs, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
@@ -677,7 +752,8 @@ BIS_API bis_status bis_cg_destroy(bis_ctx *ctx, bis_cg *cg);
  * then updates r and (r,r) only; the sweep(s) and a stream-ordered (r,z) follow;
  * everything stays on the device as before.  Call before bis_cg_init.
  * BIS_PC_FSAI needs the two factors (G, Gt of bis_mat_fsai, of this rank's diagonal block on a distributed handle) and
- * nothing else: no diagonals, no work vector. */
+ * nothing else: no diagonals, no work vector.  BIS_PC_MG needs the hierarchy's operand (bis_mg_operand, of the solver's
+ * size) in L_strict and nothing else; on a distributed handle, or with outer_iters != 1: BIS_ERR_UNSUPPORTED. */
 BIS_API bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                              const bis_mat *L_strict, const bis_mat *U_strict,
                                              const double *A_D, const double *A_D_inv,

@@ -1,0 +1,197 @@
+#!/usr/bin/env python3
+"""Time the aggregation multigrid preconditioner (bis_mg_create, "mg") against the single-level ones -- per input in ONE
+process on ONE allocation of the matrix, the preconditioners' operands and the vectors, the legs alternating round by
+round, five rounds.
+   python tools/mg_ab.py [INPUT ...] [--parts a,b,c] [--rounds 5] [--max-iters 2000] [--json FILE]
+INPUT is a generator string: hpcg:256, anderson:256, fem:80,80,81 and unstr:80,80,80 are the defaults; each runs in a child
+process of its own under a time limit (a GPU step that fails or runs out of time ends the script: nothing more is started on
+the device).  Reported per input:
+  (a) setup: ms of bis_mg_create cut at 1, 2, ... levels (max_levels = k; the time of level k's coarsening is the difference
+      of two neighbours), the rows, non-zeros, aggregate kind and SpMV form of every level, the operator complexity;
+  (b) one apply (10 per timed call) against the sum of its own SpMVs timed alone -- per level 2 nu of them, coarse_sweeps - 1
+      on the coarsest: the difference is what the vector passes cost;
+  (c) iterations and ms of the fused CG to 1e-10 r0 (b = A 1, x0 = 0) with mg at coarse_scale 1.0 and 1.5 against none, sgs,
+      ilu0it (inner 3) and fsai; a status read every 8 iterations, as the CLI does.
+--json writes the records (meant for profiles/)."""
+import json, os, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEFAULT = ["hpcg:256", "anderson:256", "fem:80,80,81", "unstr:80,80,80"]
+STEP_LIMIT = 540  # seconds per input
+TOL = 1e-10
+CHUNK = 8
+APPLIES = 10
+
+
+def generate(ctx, spec):
+    kind, dims = spec.split(":")
+    nums = [int(v) for v in dims.split(",") if "=" not in v]
+    return dict(hpcg=ctx.gen_hpcg, anderson=ctx.gen_anderson, fem=ctx.gen_fem, unstr=ctx.gen_unstr)[kind](*nums)
+
+
+def timed(ctx, legs, rounds):
+    """{name: [ms per call, one entry per round]}, the legs alternating inside every round (one warm-up call each first)."""
+    for _, f in legs:
+        f()
+    ctx.sync()
+    times = {name: [] for name, _ in legs}
+    for _ in range(rounds):
+        for name, f in legs:
+            ctx.sync()
+            t0 = time.perf_counter()
+            f()
+            ctx.sync()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    return times
+
+
+def summary(times, per=1):
+    import numpy as np
+    return dict(median_ms={q: float(np.median(v)) / per for q, v in times.items()}, min_ms={q: float(np.min(v)) / per for q, v in times.items()},
+                rounds=times)
+
+
+def run_input(spec, parts, rounds, max_iters):
+    import numpy as np
+    from basic_iterative_solvers_amd import Context
+    ctx = Context(0)
+    A = generate(ctx, spec)
+    n = A.n_rows
+    rec = dict(input=spec, rows=n, nnz=A.nnz, rounds_per_leg=rounds)
+    mg = ctx.mg(A)
+    mg15 = ctx.mg(A, coarse_scale=1.5)
+    levels = [mg.level_matrix(l) for l in range(mg.levels)]
+    rec["hierarchy"] = dict(levels=mg.levels, rows=mg.rows, nnz=mg.nnz, kinds=mg.kinds, operator_complexity=sum(mg.nnz) / max(mg.nnz[0], 1),
+                            spmv_forms=[[M.spmv_stream_info()[3], M.spmv_kernel()] for M in levels])
+    print(f"{spec}: {mg.levels} levels, rows {mg.rows}, operator complexity {rec['hierarchy']['operator_complexity']:.3f}, kinds {mg.kinds}", flush=True)
+    ones = ctx.upload(np.ones(n))
+    b, x = ctx.alloc(n), ctx.alloc(n)
+    ctx.spmv(A, ones, b)
+
+    if "a" in parts:
+        def setup_leg(k):
+            def f():
+                ctx.mg(A, max_levels=k).free()
+            return f
+
+        rec["setup"] = summary(timed(ctx, [(f"levels<={k}", setup_leg(k)) for k in range(1, mg.levels + 1)], rounds))
+        m = rec["setup"]["median_ms"]
+        print(f"{spec} (a) setup, ms by max_levels: " + ", ".join(f"{k}: {m[f'levels<={k}']:.2f}" for k in range(1, mg.levels + 1)), flush=True)
+
+    if "b" in parts:
+        out = ctx.alloc(n)
+        xs = [ctx.upload(np.ones(M.n_rows)) for M in levels]
+        ys = [ctx.alloc(M.n_rows) for M in levels]
+        count = [2 for _ in levels]  # nu = 1: the restriction's and the post-sweep's SpMV
+        count[-1] = 3  # the coarsest level: coarse_sweeps - 1
+
+        def apply_leg():
+            for _ in range(APPLIES):
+                mg.apply(out, b)
+
+        def spmv_leg():
+            for _ in range(APPLIES):
+                for M, xv, yv, c in zip(levels, xs, ys, count):
+                    for _ in range(c):
+                        ctx.spmv(M, xv, yv)
+
+        rec["apply"] = summary(timed(ctx, [("apply", apply_leg), ("spmvs_alone", spmv_leg)], rounds), per=APPLIES)
+        rec["apply"]["spmvs_per_level"] = count
+        m = rec["apply"]["median_ms"]
+        print(f"{spec} (b) one apply {m['apply']:.3f} ms, its {sum(count)} SpMVs alone {m['spmvs_alone']:.3f} ms", flush=True)
+        for v in [out] + xs + ys:
+            v.free()
+
+    if "c" in parts:
+        Ls, Us, D, Dinv = ctx.split_strict(A)
+        iLs, iLD, iUs, iUD = ctx.ilu0(A)
+        iUinv = ctx.alloc(n)
+        ctx.elemwise_div_vectors(iUinv, iLD, iUD)
+        pcs = [("mg", "mg", 0, dict(Ls=mg.operand)), ("mg_scale1.5", "mg", 0, dict(Ls=mg15.operand)), ("none", None, 0, {}),
+               ("sgs", "sgs", 0, dict(Ls=Ls, Us=Us, A_D=D, A_D_inv=Dinv, L_D=D, U_D=D)),
+               ("ilu0it", "ilu0it", 3, dict(Ls=iLs, Us=iUs, A_D=iLD, A_D_inv=iUinv, L_D=iLD, U_D=iUD))]
+        try:
+            G, Gt, _ = ctx.fsai(A)
+            pcs.append(("fsai", "fsai", 0, dict(Ls=G, Us=Gt)))
+        except Exception as e:  # (rows longer than FSAI's limit)
+            rec["fsai_refused"] = str(e)
+        handles, legs, got = [], [], {}
+
+        def solve_leg(s, key):
+            def f():
+                ctx.init_vector(x, 0.0)
+                s.init(TOL)
+                done = 0
+                while done < max_iters:
+                    s.iterate(CHUNK)
+                    done += CHUNK
+                    it, conv, hist = s.status()
+                    if conv or it < done:
+                        break
+                got[key] = dict(iters=it, converged=conv, last_over_r0=float(hist[-1] / hist[0]) if len(hist) else 0.0)
+            return f
+
+        for key, pc, inner, kw in pcs:
+            s = ctx.cg(A, b, x)
+            if pc:
+                s.set_preconditioner(pc, inner=inner, **kw)
+            handles.append(s)
+            legs.append((key, solve_leg(s, key)))
+        r = summary(timed(ctx, legs, rounds))
+        r["result"] = got
+        rec["solve_cg"] = r
+        print(f"{spec} (c) -cg to {TOL:g} r0: " + ", ".join(
+            f"{k} {got[k]['iters']} it {'conv' if got[k]['converged'] else 'NOT conv'} {r['median_ms'][k]:.1f} ms" for k, *_ in pcs), flush=True)
+        for s in handles:
+            s.free()
+
+    info = ctx.device_info()
+    mg.free()
+    mg15.free()
+    ctx.close()
+    return dict(device=info, records=[rec])
+
+
+def main():
+    argv = sys.argv[1:]
+
+    def opt(name, default):
+        return argv[argv.index(name) + 1] if name in argv else default
+
+    json_out = opt("--json", None)
+    parts = opt("--parts", "a,b,c")
+    rounds = int(opt("--rounds", 5))
+    max_iters = int(opt("--max-iters", 2000))
+    taken = {argv[argv.index(q) + 1] for q in ("--json", "--parts", "--rounds", "--max-iters") if q in argv}
+    child = "--child" in argv
+    specs = [a for a in argv if not a.startswith("--") and a not in taken] or DEFAULT
+    if child:  # one input, in this process
+        out = run_input(specs[0], parts.split(","), rounds, max_iters)
+        if json_out:
+            with open(json_out, "w") as f:
+                json.dump(out, f, indent=1)
+        return 0
+    # one child per input, each GPU step under its own time limit; a failing step ends the script
+    merged = dict(device=None, records=[])
+    for i, spec in enumerate(specs):
+        part = f"{json_out}.{i}.part" if json_out else None
+        cmd = ["timeout", "-k", "10", str(STEP_LIMIT), sys.executable, os.path.abspath(__file__), "--child", spec,
+               "--parts", parts, "--rounds", str(rounds), "--max-iters", str(max_iters)]
+        rc = subprocess.call(cmd + (["--json", part] if part else []))
+        if rc != 0:
+            print(f"{spec}: step ended with status {rc}; stopping, nothing more is started on the device", flush=True)
+            return rc
+        if part:
+            with open(part) as f:
+                got = json.load(f)
+            os.remove(part)
+            merged["device"] = got["device"]
+            merged["records"] += got["records"]
+            with open(json_out, "w") as f:  # (kept up to date input by input)
+                json.dump(merged, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
