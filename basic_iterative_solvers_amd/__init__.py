@@ -252,11 +252,19 @@ class Context:
         self.check(self.lib.bis_mat_fsai(self.h, A.h, C.byref(hg), C.byref(hgt), C.byref(nf)))
         return Mat(self, hg), Mat(self, hgt), nf.value
 
-    def mg(self, A, **params):
+    def mg(self, A, cycle=None, cycle_levels=0, **params):
         """The aggregation multigrid hierarchy of A (bis_mg_create): an MG object.  Parameters: max_levels, coarse_limit,
-        coarsening (0 / "auto", 1 / "grid", 2 / "mis"), nu, coarse_sweeps, omega, coarse_scale.  Preconditioner "mg" takes
-        Ls=MG.operand."""
-        return MG(self, A, **params)
+        coarsening (0 / "auto", 1 / "grid", 2 / "mis"), nu, coarse_sweeps, omega, coarse_scale.  `cycle` (0 / "v", 1 / "w",
+        2 / "k", 3 / "kgcr") and `cycle_levels` go to MG.set_cycle after creation; without `cycle` the hierarchy stays V.
+        Preconditioner "mg" takes Ls=MG.operand."""
+        m = MG(self, A, **params)
+        if cycle is not None:
+            try:
+                m.set_cycle(cycle, cycle_levels)
+            except Exception:
+                m.free()
+                raise
+        return m
 
     # ---- kernels (kernels.hpp names) ---------------------------------------
     def spmv(self, A, x, y):
@@ -574,9 +582,11 @@ class MGParams(C.Structure):
 
 
 class MG:
-    """bis_mg: an aggregation multigrid hierarchy of A; one V-cycle is the preconditioner "mg" (pass `.operand` as Ls)."""
+    """bis_mg: an aggregation multigrid hierarchy of A; one cycle of it (V unless set_cycle chose W or K) is the
+    preconditioner "mg" (pass `.operand` as Ls)."""
 
     COARSENING = dict(auto=0, grid=1, mis=2)
+    CYCLE = dict(v=0, w=1, k=2, kgcr=3)
 
     def __init__(self, ctx, A, max_levels=10, coarse_limit=256, coarsening=0, nu=1, coarse_sweeps=4, omega=0.0, coarse_scale=1.0):
         self.ctx, self._keep = ctx, A
@@ -610,8 +620,24 @@ class MG:
         self.ctx.check(self.ctx.lib.bis_mg_level_weights(self.ctx.h, self.h, C.c_int(int(l)), out.ctypes))
         return out
 
+    def set_cycle(self, cycle, levels=0):
+        """The cycle of this hierarchy (bis_mg_set_cycle; blocking): 0 / "v", 1 / "w", 2 / "k" (conjugate K-cycle, for SPD
+        A under CG), 3 / "kgcr" (GCR K-cycle, any A) on the first `levels` transitions (0: all but the last)."""
+        if isinstance(cycle, str):
+            if cycle not in self.CYCLE:
+                raise BisError(f"MG.set_cycle: cycle {cycle!r} is none of {sorted(self.CYCLE)}")
+            cycle = self.CYCLE[cycle]
+        self.ctx.check(self.ctx.lib.bis_mg_set_cycle(self.ctx.h, self.h, C.c_int(int(cycle)), C.c_int(int(levels))))
+
+    @property
+    def cycle(self):
+        """(cycle, cycle_levels) as set (bis_mg_cycle)."""
+        c, k = C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.lib.bis_mg_cycle(self.h, C.byref(c), C.byref(k)))
+        return c.value, k.value
+
     def apply(self, out, inp):
-        """out = M^-1 inp: one V-cycle (bis_mg_apply); out may alias inp."""
+        """out = M^-1 inp: one cycle (bis_mg_apply); out may alias inp."""
         self.ctx.check(self.ctx.lib.bis_mg_apply(self.ctx.h, self.h, C.c_void_p(out.ptr), C.c_void_p(inp.ptr)))
 
     def free(self):

@@ -11,11 +11,19 @@
 // Apply (bis_mg_apply, stream-ordered, allocates nothing): per level bis_spmv and three streaming kernels -- relax
 // (x += w o (b - y), and its from-zero form x = w o b), restrict (r_c[I] = sum over the members of b_i - y_i, a lane per
 // aggregate) and prolong (x_i += scale e_c[agg[i]]).  Products, subtractions and additions are rounded separately.
+//
+// Cycles (bis_mg_set_cycle, blocking, allocates the extra scratch): V is the above.  A W or K transition replaces the one
+// coarse solve e_c = cycle(l + 1, r_c) by two of them: W adds the cycle of the residual r_c - A e_1; K (Notay's K-cycle) takes
+// two steps of a Krylov method preconditioned by the cycle of level l + 1 -- conjugate directions (for CG) or GCR.  Three more
+// streaming kernels: r = a - s b with s on the device, the multi-dot pass (2 or 3 sums over 3 or 4 operands in one read, the last
+// workgroup to arrive sums the partials in index order and computes the step's coefficients into the transition's own device
+// scalars) and the combine x = c1 x + c2 d.  The launch sequence is fixed, nothing is read back.
 #include "bis_internal.hpp"
 
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
+#include <cfloat>
 
 struct bis_mg_level {
     const bis_mat *A = nullptr; // level 0: the caller's matrix; otherwise `owned`
@@ -28,6 +36,8 @@ struct bis_mg_level {
     int32_t *agg_ptr = nullptr; // [n_coarse + 1]
     int32_t *agg_idx = nullptr; // [n] members by aggregate, ascending rows inside one
     double *x = nullptr, *b = nullptr, *y = nullptr; // cycle scratch; level 0 owns y only (x, b are the caller's vectors)
+    // the coarse level of a W or K transition only (bis_mg_set_cycle): kr = r_2 or r~, kd = e_2 or d, kv = v (K; w lives in y)
+    double *kr = nullptr, *kd = nullptr, *kv = nullptr;
 };
 
 struct bis_mg {
@@ -35,6 +45,11 @@ struct bis_mg {
     std::vector<bis_mg_level> lv;
     bis_mat *operand = nullptr;
     double *b0 = nullptr; // level 0: the copy of the right-hand side when out aliases in
+    int cycle = BIS_MG_CYCLE_V, cycle_levels = 0;
+    // W and K transitions (allocated by the first bis_mg_set_cycle that leaves V)
+    double *ksc = nullptr;       // device scalars: [0, 4) = {1, 1, 0, 1}: W's constants; transition t: [kMgScBase + kMgScPer t, ...), MG_SC_*
+    double *kpartials = nullptr; // [3 kMaxReduceBlocks] the multi-dot pass' per-workgroup sums
+    unsigned *kcounters = nullptr; // [4 + kArriveSubs] its arrival counters (every launch re-arms them)
 };
 
 namespace {
@@ -42,6 +57,9 @@ namespace {
 constexpr int kMgT = 256;
 constexpr int kMgMaxBlocks = 16384; // elementwise passes: the wide grid of bis_blas1.hip's kernels
 constexpr int kMgMaxLevels = 16;
+// a transition's device scalars: c1, c2 and the "e_c = 0" flag are adjacent (the combine kernel reads the three)
+enum { MG_SC_C1 = 0, MG_SC_C2, MG_SC_ZERO, MG_SC_S1, MG_SC_RHO1, MG_SC_COUNT };
+constexpr int kMgScBase = 8, kMgScPer = 8;
 
 typedef double mg_v2d __attribute__((ext_vector_type(2)));
 typedef int mg_v2i __attribute__((ext_vector_type(2)));
@@ -143,6 +161,155 @@ __global__ __launch_bounds__(kMgT) void mg_prolong_kernel(double *x, const int32
     }
 }
 
+// ---- the W and K transitions' kernels ----------------------------------------------------------------------------------
+// r = a - s b, s read from device memory when the kernel runs (the product rounded, then the difference): K's
+// r~ = r_c - s1 v, and W's r_2 = r_c - y with s = 1 (1 y is y: the plain difference)
+template <bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_axmy_kernel(double *r, const double *a, const double *b, const double *s_dev, int64_t n) {
+    const double s = *s_dev;
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *r2 = reinterpret_cast<mg_v2d *>(r);
+        const mg_v2d *a2 = reinterpret_cast<const mg_v2d *>(a), *b2 = reinterpret_cast<const mg_v2d *>(b);
+        for (; i < n2; i += stride) {
+            const mg_v2d av = __builtin_nontemporal_load(a2 + i), bv = __builtin_nontemporal_load(b2 + i);
+            mg_v2d o;
+            o.x = __dsub_rn(av.x, __dmul_rn(s, bv.x));
+            o.y = __dsub_rn(av.y, __dmul_rn(s, bv.y));
+            r2[i] = o;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) r[n - 1] = __dsub_rn(a[n - 1], __dmul_rn(s, b[n - 1]));
+    } else {
+        for (; i < n; i += stride) r[i] = __dsub_rn(__builtin_nontemporal_load(a + i), __dmul_rn(s, __builtin_nontemporal_load(b + i)));
+    }
+}
+
+// x_i = (c1 x_i) + (c2 d_i), coef = {c1, c2, zero}; zero != 0: x = 0 whatever x and d hold (the guarded K step).  W's
+// e_1 + e_2 is this with {1, 1, 0}: both products are exact, the sum is the plain one.
+__device__ __forceinline__ double mg_combine1(double x, double d, double c1, double c2) { return __dadd_rn(__dmul_rn(c1, x), __dmul_rn(c2, d)); }
+
+template <bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_combine_kernel(double *x, const double *d, const double *coef, int64_t n) {
+    const double c1 = coef[MG_SC_C1], c2 = coef[MG_SC_C2];
+    const bool zero = coef[MG_SC_ZERO] != 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *x2 = reinterpret_cast<mg_v2d *>(x);
+        const mg_v2d *d2 = reinterpret_cast<const mg_v2d *>(d);
+        for (; i < n2; i += stride) {
+            mg_v2d o;
+            o.x = 0.0;
+            o.y = 0.0;
+            if (!zero) {
+                const mg_v2d xv = __builtin_nontemporal_load(x2 + i), dv = __builtin_nontemporal_load(d2 + i);
+                o.x = mg_combine1(xv.x, dv.x, c1, c2);
+                o.y = mg_combine1(xv.y, dv.y, c1, c2);
+            }
+            x2[i] = o;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = zero ? 0.0 : mg_combine1(x[n - 1], d[n - 1], c1, c2);
+    } else {
+        for (; i < n; i += stride)
+            x[i] = zero ? 0.0 : mg_combine1(__builtin_nontemporal_load(x + i), __builtin_nontemporal_load(d + i), c1, c2);
+    }
+}
+
+// The K step's dot products in one pass.  With t = GCR ? q : p:
+//   NS = 2, operands (p, q, -, r) = (c, v, -, r_c):   (t, v), (t, r_c)             -> rho1, alpha1 -> s1
+//   NS = 3, operands (p, q, u, r) = (d, w, v, r~):    (t, v), (t, w), (t, r~)      -> gamma, beta, alpha2 -> c1, c2
+// A lane sums its products by fused multiply-add in index order, the workgroup's lanes are summed by block_sum, and the
+// last workgroup to arrive sums the workgroups' partials in index order: the bits depend on (n, the data) only.  No
+// workgroup waits for another.  Thread 0 of that workgroup then does the step's scalar algebra (every operation rounded).
+template <int NS>
+__device__ __forceinline__ void mg_kdots_acc(double (&acc)[3], double p, double q, double u, double r, bool gcr) {
+    const double t = gcr ? q : p;
+    if (NS == 2) {
+        acc[0] = fma(t, q, acc[0]);
+        acc[1] = fma(t, r, acc[1]);
+    } else {
+        acc[0] = fma(t, u, acc[0]);
+        acc[1] = fma(t, q, acc[1]);
+        acc[2] = fma(t, r, acc[2]);
+    }
+}
+
+template <int NS, bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_kdots_kernel(const double *p, const double *q, const double *u, const double *r, int64_t n, int gcr_,
+                                                        double *partials, unsigned *counters, double *sc) {
+    __shared__ double lds[kMgT / 64];
+    __shared__ bool last;
+    const bool gcr = gcr_ != 0;
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    double acc[3] = {0.0, 0.0, 0.0};
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        const mg_v2d *p2 = reinterpret_cast<const mg_v2d *>(p), *q2 = reinterpret_cast<const mg_v2d *>(q),
+                     *u2 = reinterpret_cast<const mg_v2d *>(u), *r2 = reinterpret_cast<const mg_v2d *>(r);
+        for (; i < n2; i += stride) {
+            const mg_v2d pv = __builtin_nontemporal_load(p2 + i), qv = __builtin_nontemporal_load(q2 + i),
+                         rv = __builtin_nontemporal_load(r2 + i);
+            mg_v2d uv = qv;
+            if (NS == 3) uv = __builtin_nontemporal_load(u2 + i);
+            mg_kdots_acc<NS>(acc, pv.x, qv.x, uv.x, rv.x, gcr);
+            mg_kdots_acc<NS>(acc, pv.y, qv.y, uv.y, rv.y, gcr);
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) mg_kdots_acc<NS>(acc, p[n - 1], q[n - 1], NS == 3 ? u[n - 1] : 0.0, r[n - 1], gcr);
+    } else {
+        for (; i < n; i += stride)
+            mg_kdots_acc<NS>(acc, __builtin_nontemporal_load(p + i), __builtin_nontemporal_load(q + i),
+                             NS == 3 ? __builtin_nontemporal_load(u + i) : 0.0, __builtin_nontemporal_load(r + i), gcr);
+    }
+    double s[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        if (k) __syncthreads();
+        s[k] = block_sum<kMgT>(acc[k], lds);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) publish(partials + (size_t)k * kMaxReduceBlocks + blockIdx.x, s[k]);
+        last = arrive_last2(counters, counters + 4, blockIdx.x, gridDim.x);
+    }
+    __syncthreads();
+    if (!last) return;
+    double tot[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        double a = 0.0;
+        for (int b = threadIdx.x; b < (int)gridDim.x; b += kMgT) a += fetch(partials + (size_t)k * kMaxReduceBlocks + b);
+        __syncthreads();
+        tot[k] = block_sum<kMgT>(a, lds);
+    }
+    if (threadIdx.x != 0) return;
+    if (NS == 2) {
+        const double rho1 = tot[0], alpha1 = tot[1];
+        const bool bad = rho1 == 0.0 || !(fabs(rho1) <= DBL_MAX); // zero or not finite: e_c = 0
+        sc[MG_SC_RHO1] = rho1;
+        sc[MG_SC_ZERO] = bad ? 1.0 : 0.0;
+        sc[MG_SC_S1] = bad ? 0.0 : __ddiv_rn(alpha1, rho1);
+        sc[MG_SC_C1] = 0.0;
+        sc[MG_SC_C2] = 0.0;
+    } else {
+        const double gamma = tot[0], beta = tot[1], alpha2 = tot[2], rho1 = sc[MG_SC_RHO1], s1 = sc[MG_SC_S1];
+        double c1 = 0.0, c2 = 0.0;
+        if (sc[MG_SC_ZERO] == 0.0) {
+            const double rho2 = __dsub_rn(beta, __ddiv_rn(__dmul_rn(gamma, gamma), rho1));
+            c1 = s1;
+            if (rho2 > 0.0) { // (false for NaN)
+                c2 = __ddiv_rn(alpha2, rho2);
+                c1 = __dsub_rn(s1, __ddiv_rn(__dmul_rn(gamma, c2), rho1));
+            }
+        }
+        sc[MG_SC_C1] = c1;
+        sc[MG_SC_C2] = c2;
+    }
+}
+
 bis_status launch_relax0(bis_ctx *ctx, double *x, const double *w, const double *b, int64_t n) {
     const bool vec = aligned16(x) && aligned16(w) && aligned16(b) && n >= 2;
     const int grid = mg_grid(vec ? n >> 1 : n);
@@ -164,6 +331,37 @@ bis_status launch_prolong(bis_ctx *ctx, double *x, const int32_t *agg, const dou
     const int grid = mg_grid(vec ? n >> 1 : n);
     if (vec) hipLaunchKernelGGL((mg_prolong_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, agg, ec, scale, n);
     else hipLaunchKernelGGL((mg_prolong_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, agg, ec, scale, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+
+bis_status launch_axmy(bis_ctx *ctx, double *r, const double *a, const double *b, const double *s_dev, int64_t n) {
+    const bool vec = aligned16(r) && aligned16(a) && aligned16(b) && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+    if (vec) hipLaunchKernelGGL((mg_axmy_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, r, a, b, s_dev, n);
+    else hipLaunchKernelGGL((mg_axmy_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, r, a, b, s_dev, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+bis_status launch_combine(bis_ctx *ctx, double *x, const double *d, const double *coef, int64_t n) {
+    const bool vec = aligned16(x) && aligned16(d) && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+    if (vec) hipLaunchKernelGGL((mg_combine_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, d, coef, n);
+    else hipLaunchKernelGGL((mg_combine_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, d, coef, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+// u == nullptr: the first step's two sums over (p, q, r); otherwise the second step's three over (p, q, u, r)
+bis_status launch_kdots(bis_ctx *ctx, const bis_mg *mg, const double *p, const double *q, const double *u, const double *r, int64_t n, bool gcr,
+                        double *sc) {
+    const bool vec = aligned16(p) && aligned16(q) && aligned16(u) && aligned16(r) && n >= 2;
+    const int64_t items = vec ? n >> 1 : n;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((items + kMgT - 1) / kMgT, kMaxReduceBlocks));
+#define MG_KDOTS(NS, V) hipLaunchKernelGGL((mg_kdots_kernel<NS, V>), dim3(grid), dim3(kMgT), 0, ctx->stream, p, q, u, r, n, gcr ? 1 : 0, \
+                                           mg->kpartials, mg->kcounters, sc)
+    if (u) { if (vec) MG_KDOTS(3, true); else MG_KDOTS(3, false); }
+    else { if (vec) MG_KDOTS(2, true); else MG_KDOTS(2, false); }
+#undef MG_KDOTS
     BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
 }
@@ -494,6 +692,7 @@ bis_status galerkin(bis_ctx *ctx, const bis_mg_level &L, bis_mat **out) {
 
 void free_level(bis_ctx *ctx, bis_mg_level &L) {
     hipFree(L.w); hipFree(L.agg); hipFree(L.agg_ptr); hipFree(L.agg_idx); hipFree(L.x); hipFree(L.b); hipFree(L.y);
+    hipFree(L.kr); hipFree(L.kd); hipFree(L.kv);
     if (L.owned) bis_mat_destroy(ctx, L.owned);
     L = bis_mg_level();
 }
@@ -503,6 +702,7 @@ void mg_free(bis_ctx *ctx, bis_mg *mg) {
     for (bis_mg_level &L : mg->lv) free_level(ctx, L);
     if (mg->operand) { mg->operand->mg = nullptr; bis_mat_destroy(ctx, mg->operand); }
     hipFree(mg->b0);
+    hipFree(mg->ksc); hipFree(mg->kpartials); hipFree(mg->kcounters);
     delete mg;
 }
 
@@ -585,6 +785,36 @@ bis_status smooth(bis_ctx *ctx, const bis_mg_level &L, double *x, const double *
     return BIS_OK;
 }
 
+// the cycle of transition t (level t -> t + 1): the one onto the coarsest level is always the plain one
+int transition_cycle(int cycle, int cycle_levels, size_t levels, size_t t) {
+    return (t + 2 < levels && (cycle_levels == 0 || t < (size_t)cycle_levels)) ? cycle : BIS_MG_CYCLE_V;
+}
+
+bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const double *b);
+
+// e_c = N.x for the restricted residual N.b of transition t = l: the plain call, or the W / K step around two of them
+bis_status coarse_solve(bis_ctx *ctx, const bis_mg *mg, size_t l) {
+    const bis_mg_level &N = mg->lv[l + 1];
+    const int kind = transition_cycle(mg->cycle, mg->cycle_levels, mg->lv.size(), l);
+    if (bis_status st = cycle(ctx, mg, l + 1, N.x, N.b)) return st; // e_1, or c
+    if (kind == BIS_MG_CYCLE_V) return BIS_OK;
+    if (kind == BIS_MG_CYCLE_W) {
+        if (bis_status st = bis_spmv_launch(ctx, N.A, N.x, N.y, nullptr, nullptr)) return st;
+        if (bis_status st = launch_axmy(ctx, N.kr, N.b, N.y, mg->ksc + 3, N.n)) return st; // r_2 = r_c - y
+        if (bis_status st = cycle(ctx, mg, l + 1, N.kd, N.kr)) return st;                  // e_2
+        return launch_combine(ctx, N.x, N.kd, mg->ksc, N.n);                               // e_c = e_1 + e_2
+    }
+    const bool gcr = kind == BIS_MG_CYCLE_K_GCR;
+    double *sc = mg->ksc + kMgScBase + kMgScPer * l;
+    if (bis_status st = bis_spmv_launch(ctx, N.A, N.x, N.kv, nullptr, nullptr)) return st;           // v = A c
+    if (bis_status st = launch_kdots(ctx, mg, N.x, N.kv, nullptr, N.b, N.n, gcr, sc)) return st;     // rho1, alpha1 -> s1
+    if (bis_status st = launch_axmy(ctx, N.kr, N.b, N.kv, sc + MG_SC_S1, N.n)) return st;            // r~ = r_c - s1 v
+    if (bis_status st = cycle(ctx, mg, l + 1, N.kd, N.kr)) return st;                                // d
+    if (bis_status st = bis_spmv_launch(ctx, N.A, N.kd, N.y, nullptr, nullptr)) return st;           // w = A d
+    if (bis_status st = launch_kdots(ctx, mg, N.kd, N.y, N.kv, N.kr, N.n, gcr, sc)) return st;       // gamma, beta, alpha2 -> c1, c2
+    return launch_combine(ctx, N.x, N.kd, sc, N.n);                                                  // e_c = c1 c + c2 d
+}
+
 bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const double *b) {
     const bis_mg_level &L = mg->lv[l];
     if (bis_status st = launch_relax0(ctx, x, L.w, b, L.n)) return st;
@@ -594,7 +824,7 @@ bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const doub
     if (bis_status st = bis_spmv_launch(ctx, L.A, x, L.y, nullptr, nullptr)) return st;
     hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_grid(N.n)), dim3(kMgT), 0, ctx->stream, L.agg_ptr, L.agg_idx, b, L.y, N.b, N.n);
     BIS_HIP_CHECK(ctx, hipGetLastError());
-    if (bis_status st = cycle(ctx, mg, l + 1, N.x, N.b)) return st;
+    if (bis_status st = coarse_solve(ctx, mg, l)) return st;
     if (bis_status st = launch_prolong(ctx, x, L.agg, N.x, mg->p.coarse_scale, L.n)) return st;
     return smooth(ctx, L, x, b, mg->p.nu);
 }
@@ -639,6 +869,57 @@ bis_status bis_mg_apply(bis_ctx *ctx, const bis_mg *mg, double *out, const doubl
         b = mg->b0;
     }
     return cycle(ctx, mg, 0, out, b);
+}
+
+bis_status bis_mg_set_cycle(bis_ctx *ctx, bis_mg *mg, int cycle, int cycle_levels) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, mg, "bis_mg_set_cycle: bad arguments");
+    BIS_REQUIRE(ctx, cycle >= BIS_MG_CYCLE_V && cycle <= BIS_MG_CYCLE_K_GCR && cycle_levels >= 0,
+                "bis_mg_set_cycle: cycle 0..3 (V, W, K, K-GCR), cycle_levels >= 0");
+#define MG_SET_CHECK(call)                                                                                             \
+    do {                                                                                                               \
+        hipError_t e_ = (call);                                                                                        \
+        if (e_ != hipSuccess) { ctx->err = std::string("bis_mg_set_cycle: " #call ": ") + hipGetErrorString(e_); return BIS_ERR_HIP; } \
+    } while (0)
+    MG_SET_CHECK(hipStreamSynchronize(ctx->stream)); // applies in flight read the scratch that may go
+    mg->cycle = BIS_MG_CYCLE_V;                      // (what holds if an allocation below fails)
+    mg->cycle_levels = 0;
+    if (cycle != BIS_MG_CYCLE_V && !mg->ksc) {
+        MG_SET_CHECK(hipMalloc(&mg->kpartials, sizeof(double) * 3 * kMaxReduceBlocks));
+        MG_SET_CHECK(hipMalloc(&mg->kcounters, sizeof(unsigned) * (4 + kArriveSubs)));
+        MG_SET_CHECK(hipMemsetAsync(mg->kcounters, 0, sizeof(unsigned) * (4 + kArriveSubs), ctx->stream));
+        double *sc = nullptr;
+        const size_t count = kMgScBase + kMgScPer * kMgMaxLevels;
+        MG_SET_CHECK(hipMalloc(&sc, sizeof(double) * count));
+        std::vector<double> init(count, 0.0);
+        init[0] = init[1] = init[3] = 1.0; // W: {c1, c2, zero} = {1, 1, 0}, and the factor 1 of r_2 = r_c - 1 y
+        const hipError_t e = hipMemcpy(sc, init.data(), sizeof(double) * count, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(sc); MG_SET_CHECK(e); }
+        mg->ksc = sc;
+    }
+    for (size_t t = 0; t + 1 < mg->lv.size(); ++t) {
+        bis_mg_level &N = mg->lv[t + 1];
+        const int kind = transition_cycle(cycle, cycle_levels, mg->lv.size(), t);
+        const bool two = kind != BIS_MG_CYCLE_V, kv = kind == BIS_MG_CYCLE_K || kind == BIS_MG_CYCLE_K_GCR;
+        const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(N.n, 2);
+        if (!two) { hipFree(N.kr); hipFree(N.kd); N.kr = N.kd = nullptr; }
+        if (!kv) { hipFree(N.kv); N.kv = nullptr; }
+        if (two && !N.kr) MG_SET_CHECK(hipMalloc(&N.kr, bytes));
+        if (two && !N.kd) MG_SET_CHECK(hipMalloc(&N.kd, bytes));
+        if (kv && !N.kv) MG_SET_CHECK(hipMalloc(&N.kv, bytes));
+    }
+    MG_SET_CHECK(hipStreamSynchronize(ctx->stream));
+#undef MG_SET_CHECK
+    mg->cycle = cycle;
+    mg->cycle_levels = cycle_levels;
+    return BIS_OK;
+}
+
+bis_status bis_mg_cycle(const bis_mg *mg, int *cycle, int *cycle_levels) {
+    if (!mg) return BIS_ERR_INVALID;
+    if (cycle) *cycle = mg->cycle;
+    if (cycle_levels) *cycle_levels = mg->cycle_levels;
+    return BIS_OK;
 }
 
 const bis_mat *bis_mg_operand(const bis_mg *mg) { return mg ? mg->operand : nullptr; }

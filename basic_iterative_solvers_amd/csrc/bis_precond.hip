@@ -31,7 +31,7 @@ bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_m
                                     int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1, "bis_apply_preconditioner: bad arguments");
-    if (pc == BIS_PC_MG) { // (not in the reference) the V-cycle of the hierarchy whose operand is in L_strict (bis_mg_operand); nothing else is read
+    if (pc == BIS_PC_MG) { // (not in the reference) the cycle of the hierarchy whose operand is in L_strict (bis_mg_operand); nothing else is read
         BIS_REQUIRE(ctx, L_strict && L_strict->mg && L_strict->n_rows == n, "bis_apply_preconditioner: MG needs the operand of a hierarchy of size n in L_strict");
         if (outer_iters != 1) { ctx->err = "bis_apply_preconditioner: MG with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
         return bis_mg_apply(ctx, L_strict->mg, output, input);

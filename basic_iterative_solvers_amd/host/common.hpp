@@ -64,6 +64,9 @@ inline int &precond_inner_iters() { static int k = PRECOND_INNER_ITERS; return k
 inline int &precond_value_bits() { static int b = 64; return b; }
 // -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis: the parameters of -p mg (bis_mg_params; these are its defaults)
 inline bis_mg_params &precond_mg_params() { static bis_mg_params p = {10, 256, 0, 1, 4, 0.0, 1.0}; return p; }
+// -mg cycle=v|w|k|kgcr,klev=N: the cycle of -p mg and the number of transitions it covers (bis_mg_set_cycle; 0: all but the last)
+struct MGCycle { int cycle = BIS_MG_CYCLE_V, levels = 0; };
+inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
 enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB };
 
 inline std::string to_string(PrecondType t) {

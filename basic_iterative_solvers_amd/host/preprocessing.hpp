@@ -93,6 +93,16 @@ inline void factor_LU(Solver *s) {
         for (int l = 0; l + 1 < levels; ++l) std::cout << (l ? " / " : " ") << (kind[l] == 1 ? "grid" : "mis");
         if (levels < 2) std::cout << " none";
         std::cout << std::endl;
+        const MGCycle &cyc = precond_mg_cycle();
+        if (cyc.cycle != BIS_MG_CYCLE_V) { // (a command line without cycle= prints and computes what it always did)
+            bis::check(bis_mg_set_cycle(bis::ctx(), s->mg, cyc.cycle, cyc.levels), "bis_mg_set_cycle");
+            static const char *names[] = {"V", "W", "K (conjugate)", "K (GCR)"};
+            const int covered = std::max(0, cyc.levels == 0 ? levels - 2 : std::min(cyc.levels, levels - 2));
+            std::cout << "multigrid cycle: " << names[cyc.cycle] << ", transitions ";
+            if (covered > 0) std::cout << "0.." << covered - 1;
+            else std::cout << "none (the hierarchy has fewer than three levels: the V-cycle)";
+            std::cout << std::endl;
+        }
     }
 }
 

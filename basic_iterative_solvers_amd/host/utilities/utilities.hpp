@@ -9,7 +9,7 @@
 // triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st); `-p fsai` is the
 // factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs; `-pprec 32` rounds the factors those two
 // types apply by SpMV to fp32 (bis_mat_round_f32); `-p mg` is one V-cycle of the aggregation multigrid hierarchy of bis_mg_create
-// and `-mg key=value,...` sets its parameters.
+// (or, with `-mg cycle=w|k|kgcr`, one W- or K-cycle) and `-mg key=value,...` sets its parameters.
 #pragma once
 
 #include <sys/stat.h>
@@ -61,7 +61,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                                 "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)"
                                 "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)"
                                 "\n-p fsai (Factorized sparse approximate inverse on the pattern of tril(A))"
-                                "\n-p mg (Aggregation multigrid V-cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis)\n");
+                                "\n-p mg (Aggregation multigrid cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=0)\n");
                 exit(EXIT_FAILURE);
             }
             a->preconditioner = it->second;
@@ -98,9 +98,12 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 else if (k == "scale") p.coarse_scale = atof(v.c_str());
                 else if (k == "omega") p.omega = atof(v.c_str());
                 else if (k == "coarsening" && (v == "auto" || v == "grid" || v == "mis")) p.coarsening = v == "auto" ? 0 : v == "grid" ? 1 : 2;
+                else if (k == "cycle" && (v == "v" || v == "w" || v == "k" || v == "kgcr"))
+                    precond_mg_cycle().cycle = v == "v" ? BIS_MG_CYCLE_V : v == "w" ? BIS_MG_CYCLE_W : v == "k" ? BIS_MG_CYCLE_K : BIS_MG_CYCLE_K_GCR;
+                else if (k == "klev" && v.find_first_not_of("0123456789") == std::string::npos) precond_mg_cycle().levels = atoi(v.c_str());
                 else ok = false;
                 if (!ok) {
-                    fprintf(stderr, "ERROR: -mg nu=K,cs=K,limit=N,levels=K,scale=S,omega=W,coarsening=auto|grid|mis: cannot read \"%s\"\n", item.c_str());
+                    fprintf(stderr, "ERROR: -mg nu=K,cs=K,limit=N,levels=K,scale=S,omega=W,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=N: cannot read \"%s\"\n", item.c_str());
                     exit(EXIT_FAILURE);
                 }
             }
@@ -128,6 +131,13 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     if (a->preconditioner == PrecondType::MG && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
         a->method != SolverType::BiCGSTAB) {
         fprintf(stderr, "ERROR: -p mg needs a Krylov method: -cg, -gm or -bi\n");
+        exit(EXIT_FAILURE);
+    }
+    // a K-cycle changes with its right-hand side: left-preconditioned GMRES builds its basis for ONE operator M^-1 A, and there is no flexible GMRES here
+    if (a->preconditioner == PrecondType::MG && a->method == SolverType::GMRES &&
+        (precond_mg_cycle().cycle == BIS_MG_CYCLE_K || precond_mg_cycle().cycle == BIS_MG_CYCLE_K_GCR)) {
+        fprintf(stderr, "ERROR: -mg cycle=k|kgcr is not a fixed preconditioner, which -gm (left-preconditioned GMRES, not flexible) assumes: "
+                        "use -cg or -bi, or cycle=v|w\n");
         exit(EXIT_FAILURE);
     }
     // the other types run exact sweeps on the fp64 arrays and would gain nothing from rounded values

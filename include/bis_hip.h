@@ -69,7 +69,8 @@ enum {
     BIS_PC_ILU0_ITER = 8,
     /* not in the reference: factorized sparse approximate inverse, M^-1 = Gt G with the factors of bis_mat_fsai */
     BIS_PC_FSAI = 9,
-    /* not in the reference: aggregation multigrid, one V-cycle of a bis_mg hierarchy (bis_mg_create) */
+    /* not in the reference: aggregation multigrid, one cycle of a bis_mg hierarchy (bis_mg_create; the V-cycle unless
+     * bis_mg_set_cycle chose another) */
     BIS_PC_MG = 10
 };
 
@@ -388,8 +389,8 @@ BIS_API bis_status bis_mat_fsai(bis_ctx *ctx, const bis_mat *A, bis_mat **G, bis
 BIS_API const char *bis_mat_fsai_kernel(const bis_mat *G);
 
 /* ---- aggregation multigrid (bis_mg.hip); no reference counterpart ------------------------------------------------------
- * Unsmoothed aggregation, one V(nu,nu) cycle with Jacobi-type smoothing as the preconditioner: SpMVs and streaming passes
- * only, no dependency between rows, any row order.
+ * Unsmoothed aggregation, one V(nu,nu) cycle with Jacobi-type smoothing as the preconditioner (or a W- or K-cycle of the same
+ * hierarchy: bis_mg_set_cycle): SpMVs and streaming passes only, no dependency between rows, any row order.
  *
  * Parameters (NULL = the defaults): max_levels 10 (1..16); coarse_limit 256 (>= 1): a level of at most this many rows is
  * not coarsened; coarsening 0 = grid aggregates where the level has a grid hint whose product is its size, MIS aggregates
@@ -435,13 +436,38 @@ typedef struct {
 } bis_mg_params;
 BIS_API bis_status bis_mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, bis_mg **out);
 BIS_API bis_status bis_mg_destroy(bis_ctx *ctx, bis_mg *mg);
-/* out = M^-1 in: one V-cycle, stream-ordered; out may alias in (the right-hand side is then copied first).  On level l with
+/* out = M^-1 in: one cycle (the V-cycle below unless bis_mg_set_cycle chose another), stream-ordered; out may alias in (the
+ * right-hand side is then copied first).  On level l with
  * right-hand side b, every product, subtraction and addition rounded separately (no fused multiply-add), y = A x by bis_spmv:
  *   x = w o b;  then nu - 1 sweeps  y = A x, x_i = x_i + w_i (b_i - y_i);
  *   y = A x;  r_c[I] = sum over the rows i of aggregate I in ascending order of (b_i - y_i), the first difference starting the
  *   sum;  e_c = the cycle of level l + 1 on r_c;  x_i = x_i + coarse_scale e_c[agg[i]];  then nu sweeps as above.
  * The coarsest level: x = w o b, then coarse_sweeps - 1 sweeps. */
 BIS_API bis_status bis_mg_apply(bis_ctx *ctx, const bis_mg *mg, double *out, const double *in);
+/* The cycle of an existing hierarchy (a fresh one is V).  With L levels there are L - 1 transitions, transition t from level t
+ * to level N = t + 1.  Transition t uses `cycle` iff t < L - 2 (the one onto the coarsest level is always the plain one) and
+ * (cycle_levels == 0 or t < cycle_levels); every other transition is the V step.  At most two levels: V's bits under any
+ * setting.  The hierarchy, the operators and the smoother stay; only "e_c = the cycle of level N on r_c" above is replaced,
+ * every product, quotient, difference and sum below rounded separately, A_N x by bis_spmv:
+ *   W:  e_1 = cycle(N, r_c);  y = A_N e_1;  r_2 = r_c - y;  e_2 = cycle(N, r_2);  e_c = e_1 + e_2.  Linear and fixed, like V.
+ *   K (Notay's K-cycle: two steps of a Krylov method preconditioned by the cycle of level N; BIS_MG_CYCLE_K takes conjugate
+ *   directions, for SPD A under CG; BIS_MG_CYCLE_K_GCR minimises the residual, for any A):
+ *     c = cycle(N, r_c);  v = A_N c;  t = c (K) or v (K_GCR);  rho1 = (t, v), alpha1 = (t, r_c);
+ *     rho1 zero or not finite: e_c = 0, exactly, whatever the rest computes;  s1 = alpha1 / rho1;  r~ = r_c - s1 v;
+ *     d = cycle(N, r~);  w = A_N d;  t2 = d (K) or w (K_GCR);  gamma = (t2, v), beta = (t2, w), alpha2 = (t2, r~);
+ *     rho2 = beta - (gamma gamma) / rho1;  not rho2 > 0 (NaN included): c1 = s1, c2 = 0;  otherwise c2 = alpha2 / rho2,
+ *     c1 = s1 - (gamma c2) / rho1;  e_c,i = (c1 c_i) + (c2 d_i).
+ *   The dot products are sums of fused multiply-adds in a fixed order that depends on the length only (per-workgroup partial
+ *   sums, summed in index order by the workgroup that arrives last); the coefficients stay in device scalars that every
+ *   transition owns.  There is no early exit: the launch sequence is fixed, nothing is read back, two applies give the same
+ *   bits.  A K-cycle is not a fixed linear operator: a method that assumes one (left-preconditioned GMRES) is not for it.
+ * bis_mg_set_cycle blocks and allocates the extra scratch (two vectors on the coarse level of a W transition, three of a K
+ * transition), so bis_mg_apply still allocates nothing and never blocks; setting V again restores V's bits.
+ * BIS_ERR_INVALID: null arguments, cycle outside 0..3, cycle_levels < 0 (nothing changes).  bis_mg_cycle reports what is
+ * set; either pointer may be NULL. */
+enum { BIS_MG_CYCLE_V = 0, BIS_MG_CYCLE_W = 1, BIS_MG_CYCLE_K = 2, BIS_MG_CYCLE_K_GCR = 3 };
+BIS_API bis_status bis_mg_set_cycle(bis_ctx *ctx, bis_mg *mg, int cycle, int cycle_levels);
+BIS_API bis_status bis_mg_cycle(const bis_mg *mg, int *cycle, int *cycle_levels);
 /* The hierarchy as the preconditioner of type BIS_PC_MG: an n x n matrix without entries that mg owns (bis_mat_destroy on it
  * does nothing) and that leads back to mg; every entry point but the preconditioner dispatch sees the zero matrix. */
 BIS_API const bis_mat *bis_mg_operand(const bis_mg *mg);

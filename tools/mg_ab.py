@@ -11,7 +11,11 @@ the device).  Reported per input:
   (b) one apply (10 per timed call) against the sum of its own SpMVs timed alone -- per level 2 nu of them, coarse_sweeps - 1
       on the coarsest: the difference is what the vector passes cost;
   (c) iterations and ms of the fused CG to 1e-10 r0 (b = A 1, x0 = 0) with mg at coarse_scale 1.0 and 1.5 against none, sgs,
-      ilu0it (inner 3) and fsai; a status read every 8 iterations, as the CLI does.
+      ilu0it (inner 3) and fsai; a status read every 8 iterations, as the CLI does;
+  (d) the cycles (bis_mg_set_cycle) on the same hierarchy, the same CG handle and the same vectors: V, and W, K, K-GCR on the
+      first 1, 2, 3 and on all transitions (a count that covers all of them is run once, as "all") -- iterations and ms of
+      the fused CG to 1e-10 r0, and one apply against the sum of its own SpMVs timed alone (the K-GCR legs are there for the
+      apply's cost: its cycle is not symmetric, CG is not the method for it).  The cycle is set before the clock starts.
 --json writes the records (meant for profiles/)."""
 import json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,13 +35,19 @@ def generate(ctx, spec):
 
 
 def timed(ctx, legs, rounds):
-    """{name: [ms per call, one entry per round]}, the legs alternating inside every round (one warm-up call each first)."""
-    for _, f in legs:
+    """{name: [ms per call, one entry per round]}, the legs alternating inside every round (one warm-up call each first).  A leg
+    is (name, f) or (name, f, prepare): prepare() runs before the clock starts."""
+    legs = [(leg[0], leg[1], leg[2] if len(leg) > 2 else None) for leg in legs]
+    for _, f, prepare in legs:
+        if prepare:
+            prepare()
         f()
     ctx.sync()
-    times = {name: [] for name, _ in legs}
+    times = {name: [] for name, _, _ in legs}
     for _ in range(rounds):
-        for name, f in legs:
+        for name, f, prepare in legs:
+            if prepare:
+                prepare()
             ctx.sync()
             t0 = time.perf_counter()
             f()
@@ -50,6 +60,21 @@ def summary(times, per=1):
     import numpy as np
     return dict(median_ms={q: float(np.median(v)) / per for q, v in times.items()}, min_ms={q: float(np.min(v)) / per for q, v in times.items()},
                 rounds=times)
+
+
+CYCLES = [(1, "W"), (2, "K"), (3, "K-GCR")]
+
+
+def cycle_spmvs(n_levels, cycle, klev, nu=1, coarse_sweeps=4):
+    """SpMVs per level of one apply: a level is visited twice as often as the one above it below a W or K transition, every
+    visit costs 2 nu (coarse_sweeps - 1 on the coarsest level), and a W / K transition adds 1 / 2 on its coarse level."""
+    visits, extra = [1] * n_levels, [0] * n_levels
+    for t in range(n_levels - 1):
+        on = cycle != 0 and t < n_levels - 2 and (klev == 0 or t < klev)
+        visits[t + 1] = visits[t] * (2 if on else 1)
+        if on:
+            extra[t + 1] = visits[t] * (1 if cycle == 1 else 2)
+    return [visits[l] * (2 * nu if l < n_levels - 1 else coarse_sweeps - 1) + extra[l] for l in range(n_levels)]
 
 
 def run_input(spec, parts, rounds, max_iters):
@@ -146,6 +171,71 @@ def run_input(spec, parts, rounds, max_iters):
         for s in handles:
             s.free()
 
+    if "d" in parts:
+        settings = [("V", 0, 0)]
+        for cyc, cname in CYCLES:
+            for klev in (1, 2, 3):
+                if klev < mg.levels - 2:
+                    settings.append((f"{cname} klev={klev}", cyc, klev))
+            if mg.levels > 2:
+                settings.append((f"{cname} all", cyc, 0))
+        out = ctx.alloc(n)
+        xs = [ctx.upload(np.ones(M.n_rows)) for M in levels]
+        ys = [ctx.alloc(M.n_rows) for M in levels]
+        s = ctx.cg(A, b, x)
+        s.set_preconditioner("mg", Ls=mg.operand)
+        got, counts = {}, {}
+
+        def setter(cyc, klev):
+            return lambda: mg.set_cycle(cyc, klev)
+
+        def solve_leg(key):
+            def f():
+                ctx.init_vector(x, 0.0)
+                s.init(TOL)
+                done = 0
+                while done < max_iters:
+                    s.iterate(CHUNK)
+                    done += CHUNK
+                    it, conv, hist = s.status()
+                    if conv or it < done:
+                        break
+                got[key] = dict(iters=it, converged=conv, last_over_r0=float(hist[-1] / hist[0]) if len(hist) else 0.0)
+            return f
+
+        def apply_leg():
+            for _ in range(APPLIES):
+                mg.apply(out, b)
+
+        def spmv_leg(count):
+            def f():
+                for _ in range(APPLIES):
+                    for M, xv, yv, c in zip(levels, xs, ys, count):
+                        for _ in range(c):
+                            ctx.spmv(M, xv, yv)
+            return f
+
+        solve_legs, apply_legs = [], []
+        for key, cyc, klev in settings:
+            counts[key] = cycle_spmvs(mg.levels, cyc, klev)
+            solve_legs.append((key, solve_leg(key), setter(cyc, klev)))
+            apply_legs.append((key, apply_leg, setter(cyc, klev)))
+            apply_legs.append((key + " spmvs_alone", spmv_leg(counts[key])))
+        r = summary(timed(ctx, solve_legs, rounds))
+        r["result"] = got
+        rec["cycles_solve_cg"] = r
+        a = summary(timed(ctx, apply_legs, rounds), per=APPLIES)
+        a["spmvs_per_level"] = counts
+        rec["cycles_apply"] = a
+        mg.set_cycle(0)
+        for key, _, _ in settings:
+            print(f"{spec} (d) {key}: -cg {got[key]['iters']} it {'conv' if got[key]['converged'] else 'NOT conv'} "
+                  f"{r['median_ms'][key]:.1f} ms; one apply {a['median_ms'][key]:.3f} ms, its {sum(counts[key])} SpMVs alone "
+                  f"{a['median_ms'][key + ' spmvs_alone']:.3f} ms", flush=True)
+        s.free()
+        for v in [out] + xs + ys:
+            v.free()
+
     info = ctx.device_info()
     mg.free()
     mg15.free()
@@ -160,7 +250,7 @@ def main():
         return argv[argv.index(name) + 1] if name in argv else default
 
     json_out = opt("--json", None)
-    parts = opt("--parts", "a,b,c")
+    parts = opt("--parts", "a,b,c,d")
     rounds = int(opt("--rounds", 5))
     max_iters = int(opt("--max-iters", 2000))
     taken = {argv[argv.index(q) + 1] for q in ("--json", "--parts", "--rounds", "--max-iters") if q in argv}
