@@ -585,7 +585,8 @@ bis_status bis_axpy_dot_dev(bis_ctx *ctx, double *w, const double *u, const doub
                             double *result_dev) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, n >= 0 && result_dev && scale_dev && (n == 0 || (w && u)), "bis_axpy_dot_dev: bad arguments");
-    BIS_REQUIRE(ctx, w != u && w != v, "bis_axpy_dot_dev: w must not alias u or v (pass v = NULL for (w, w))");
+    // (n == 0 with null operands is valid like everywhere else: null w "equals" a null u or v without aliasing anything)
+    BIS_REQUIRE(ctx, !w || (w != u && w != v), "bis_axpy_dot_dev: w must not alias u or v (pass v = NULL for (w, w))");
     // bit-identical to the separate launches only if both of them would take the same form (16-byte vector or scalar
     // index map); with mixed alignment (odd n: every other basis vector) they would not: run them separately then
     const bool vec_axpy = aligned16(w) && aligned16(u) && n >= 2, vec_dot = aligned16(w) && (!v || aligned16(v)) && n >= 2;

@@ -53,6 +53,10 @@ inline int ew_grid(int64_t n_items) {
 
 // Jacobi: r = b - t (kernels.hpp:124 with scale 1: fma(-1, t, b)), partials of (r, r) with the index map and the two
 // accumulators of dot_partial_kernel, and x_next = (b - (t - D x)) / D as normalize_x_kernel computes it.
+// The kernel-by-kernel schedule takes that norm of a residual VECTOR, a 16-byte aligned allocation of its own (as r_0 in
+// bis_stat_init is): its dot runs in the double2 form whatever the alignment of b, D and x.  r is never stored here, so
+// the pair index map holds for every n and every operand; VEC only says whether the operands may be LOADED 16 bytes at a
+// time (all of them 16-byte aligned) or element by element.
 template <bool VEC>
 __global__ __launch_bounds__(kT) void jacobi_step_kernel(int64_t n, const int *__restrict__ flags, const double *__restrict__ t,
                                                          const double *__restrict__ D, const double *__restrict__ b,
@@ -67,32 +71,34 @@ __global__ __launch_bounds__(kT) void jacobi_step_kernel(int64_t n, const int *_
         const double adjusted = fma(-dv, xv, tv);
         return (bv - adjusted) / dv;
     };
-    if (VEC) {
-        const int64_t n2 = n >> 1;
-        const double2 *t2 = reinterpret_cast<const double2 *>(t), *D2 = reinterpret_cast<const double2 *>(D);
-        const double2 *b2 = reinterpret_cast<const double2 *>(b), *x2 = reinterpret_cast<const double2 *>(x);
-        double2 *o2 = reinterpret_cast<double2 *>(x_next);
-        for (; i < n2; i += stride) {
-            const double2 tv = t2[i], bv = b2[i], dv = D2[i], xv = x2[i];
-            const double r0 = fma(-1.0, tv.x, bv.x), r1 = fma(-1.0, tv.y, bv.y);
-            acc0 = fma(r0, r0, acc0);
-            acc1 = fma(r1, r1, acc1);
-            double2 o;
-            o.x = next(tv.x, dv.x, xv.x, bv.x);
-            o.y = next(tv.y, dv.y, xv.y, bv.y);
+    const int64_t n2 = n >> 1;
+    const double2 *t2 = reinterpret_cast<const double2 *>(t), *D2 = reinterpret_cast<const double2 *>(D);
+    const double2 *b2 = reinterpret_cast<const double2 *>(b), *x2 = reinterpret_cast<const double2 *>(x);
+    double2 *o2 = reinterpret_cast<double2 *>(x_next);
+    for (; i < n2; i += stride) {
+        double2 tv, bv, dv, xv;
+        if (VEC) {
+            tv = t2[i]; bv = b2[i]; dv = D2[i]; xv = x2[i];
+        } else {
+            tv = make_double2(t[2 * i], t[2 * i + 1]); bv = make_double2(b[2 * i], b[2 * i + 1]);
+            dv = make_double2(D[2 * i], D[2 * i + 1]); xv = make_double2(x[2 * i], x[2 * i + 1]);
+        }
+        const double r0 = fma(-1.0, tv.x, bv.x), r1 = fma(-1.0, tv.y, bv.y);
+        acc0 = fma(r0, r0, acc0);
+        acc1 = fma(r1, r1, acc1);
+        double2 o;
+        o.x = next(tv.x, dv.x, xv.x, bv.x);
+        o.y = next(tv.y, dv.y, xv.y, bv.y);
+        if (VEC) {
             o2[i] = o;
+        } else {
+            x_next[2 * i] = o.x; x_next[2 * i + 1] = o.y;
         }
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const double rr = fma(-1.0, t[n - 1], b[n - 1]);
-            acc0 = fma(rr, rr, acc0);
-            x_next[n - 1] = next(t[n - 1], D[n - 1], x[n - 1], b[n - 1]);
-        }
-    } else {
-        for (; i < n; i += stride) {
-            const double rr = fma(-1.0, t[i], b[i]);
-            acc0 = fma(rr, rr, acc0);
-            x_next[i] = next(t[i], D[i], x[i], b[i]);
-        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double rr = fma(-1.0, t[n - 1], b[n - 1]);
+        acc0 = fma(rr, rr, acc0);
+        x_next[n - 1] = next(t[n - 1], D[n - 1], x[n - 1], b[n - 1]);
     }
     const double s = block_sum<kT>(acc0 + acc1, lds);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
@@ -207,7 +213,7 @@ bis_status bis_stat_iterate(bis_ctx *ctx, bis_stat *s, int n_iters) {
             // the sample of this iteration (||b - A x_{k+1}||) and, in the same pass, the step the NEXT iteration starts with
             double *nn = (k & 1) ? s->xb : s->x; // x_{k+2} overwrites x_k
             const bool vec = n >= 2 && (((uintptr_t)s->t | (uintptr_t)s->D | (uintptr_t)s->b | (uintptr_t)nxt | (uintptr_t)nn) & 15) == 0;
-            const int grid = vec ? ew_grid(n >> 1) : ew_grid(n);
+            const int grid = ew_grid(n >> 1); // the grid bis_dot_dev gives an aligned r of n entries (n == 1: one workgroup either way)
             if (vec) hipLaunchKernelGGL((jacobi_step_kernel<true>), dim3(grid), dim3(kT), 0, ctx->stream, n, s->flags, s->t, s->D, s->b, nxt, nn, ctx->partials);
             else hipLaunchKernelGGL((jacobi_step_kernel<false>), dim3(grid), dim3(kT), 0, ctx->stream, n, s->flags, s->t, s->D, s->b, nxt, nn, ctx->partials);
             hipLaunchKernelGGL(stat_book_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->partials, grid, s->sc, s->flags, s->hist, s->hist_cap);

@@ -739,7 +739,8 @@ BIS_API bis_status bis_kernel_swap_operands(bis_ctx *ctx, const char *name);
  * per iteration.  Jacobi makes ONE SpMV per iteration -- the product A x_k that
  * samples iteration k's residual is the one iteration k+1 starts from -- and
  * fuses residual, norm partials and the step into one pass; the sampled norms are
- * bit-identical to bis_compute_residual + bis_euclidean_vec_norm.  GS / SGS run
+ * bit-identical to bis_compute_residual + bis_euclidean_vec_norm of a 16-byte
+ * aligned residual vector, whatever the alignment of b, D and x.  GS / SGS run
  * the reference's operations unchanged, stream-ordered.  After the stop test has
  * fired the remaining enqueued launches are no-ops (SpMVs and sweeps included).
  * x: x_0 on entry; read the result with bis_stat_solution (Jacobi alternates
