@@ -403,6 +403,9 @@ class Context:
     def mgmres(self, A, B, X, k, restart=10):
         return MGMRES(self, A, B, X, k, restart)
 
+    def fgmres(self, A, b, x, restart=10):
+        return FGMRES(self, A, b, x, restart)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -807,6 +810,56 @@ class MGMRES:
     def free(self):
         if self.h:
             self.ctx.lib.bis_mgmres_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class FGMRES:
+    """Restarted flexible GMRES(restart) on one right-hand side as a device schedule (bis_fgmres_*): the preconditioner stands
+    on the right and may change from step to step (an MG K-cycle), the history is the true residual's.  x changes only at a
+    restart or a stop: `solution` gives the explicit iterate."""
+
+    def __init__(self, ctx, A, b, x, restart=10):
+        self.ctx, self.restart = ctx, int(restart)
+        self.h = C.c_void_p()
+        self._keep = (A, b, x)
+        ctx.check(ctx.lib.bis_fgmres_create(ctx.h, A.h, C.c_void_p(b.ptr), C.c_void_p(x.ptr), C.c_int(self.restart),
+                                            C.byref(self.h)))
+
+    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
+        """MGMRES.set_preconditioner's keywords, every type; an MG object stands for "mg" with its operand as Ls."""
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        if isinstance(pc, MG):
+            pc, Ls = "mg", pc.operand
+        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
+        self.ctx.check(self.ctx.lib.bis_fgmres_set_preconditioner(
+            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
+
+    def init(self, tol):
+        r0 = C.c_double()
+        self.ctx.check(self.ctx.lib.bis_fgmres_init(self.ctx.h, self.h, C.c_double(tol), C.byref(r0)))
+        return r0.value
+
+    def iterate(self, n):
+        self.ctx.check(self.ctx.lib.bis_fgmres_iterate(self.ctx.h, self.h, C.c_int(int(n))))
+
+    def status(self, hist_cap=4096):
+        """(iterations, converged, history): the history has iterations + 1 + restarts entries (n_hist of bis_fgmres_status)."""
+        iters, conv, n_hist = C.c_int(), C.c_int(), C.c_int()
+        hist = np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_fgmres_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv), C.byref(n_hist),
+                                                      hist.ctypes, C.c_int(hist_cap)))
+        return iters.value, bool(conv.value), hist[:min(n_hist.value, hist_cap)].copy()
+
+    def solution(self, out):
+        """The explicit iterate into the n-vector `out` (bis_fgmres_solution); the solve does not change."""
+        self.ctx.check(self.ctx.lib.bis_fgmres_solution(self.ctx.h, self.h, C.c_void_p(out.ptr)))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_fgmres_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 

@@ -23,9 +23,10 @@ inline void print_residuals(double *norms, double *time_per_iteration, int count
 inline void summary_output(Args *, Solver *solver) {
     print_residuals(solver->collected_residual_norms, solver->time_per_iteration,
                     solver->collected_residual_norms_count, solver->residual_check_len);
-    if (solver->method == SolverType::GMRES) solver->iter_count += solver->gmres_restart_count;
+    const bool restarted = solver->method == SolverType::GMRES || solver->method == SolverType::FGMRES;
+    if (restarted) solver->iter_count += solver->gmres_restart_count;
     std::cout << "\nSolver: " << to_string(solver->method);
-    if (solver->method == SolverType::GMRES) std::cout << "(" << solver->gmres_restart_len << ")";
+    if (restarted) std::cout << "(" << solver->gmres_restart_len << ")";
     if (solver->preconditioner != PrecondType::None)
         std::cout << " with preconditioner: " << to_string(solver->preconditioner);
     if (solver->convergence_flag)

@@ -9,7 +9,8 @@
 // triangular solves (bis_itrsv) and `-inner K` their step count (also the inner sweeps of 2st / s2st); `-p fsai` is the
 // factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs; `-pprec 32` rounds the factors those two
 // types apply by SpMV to fp32 (bis_mat_round_f32); `-p mg` is one V-cycle of the aggregation multigrid hierarchy of bis_mg_create
-// (or, with `-mg cycle=w|k|kgcr`, one W- or K-cycle) and `-mg key=value,...` sets its parameters.
+// (or, with `-mg cycle=w|k|kgcr`, one W- or K-cycle) and `-mg key=value,...` sets its parameters; the method `-fgm` is flexible
+// GMRES(m) on the device schedule bis_fgmres_* (methods/fgmres.hpp), which takes every -p type, the K-cycles included.
 #pragma once
 
 #include <sys/stat.h>
@@ -31,11 +32,13 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     else if (st == "-cg") a->method = SolverType::ConjugateGradient;
     else if (st == "-gm") a->method = SolverType::GMRES;
     else if (st == "-bi") a->method = SolverType::BiCGSTAB;
+    else if (st == "-fgm") a->method = SolverType::FGMRES;
     else {
         printf("ERROR: parse_cli: Please choose an available solver:"
                "\n-j (Jacobi)\n-gs (Gauss-Seidel)\n-sgs (Symmetric Gauss-Seidel)"
                "\n-gm ([Preconditioned] GMRES)\n-cg ([Preconditioned] Conjugate Gradient)"
-               "\n-bi ([Preconditioned] BiCGSTAB)\n");
+               "\n-bi ([Preconditioned] BiCGSTAB)"
+               "\n-fgm ([Preconditioned] flexible GMRES, right-preconditioned)\n");
         exit(EXIT_FAILURE);
     }
     for (int i = 3; i < argc; ++i) {
@@ -129,7 +132,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else std::cout << "ERROR: assign_cli_inputs: Arguement \"" << arg << "\" not recongnized." << std::endl;
     }
     if (a->preconditioner == PrecondType::MG && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
-        a->method != SolverType::BiCGSTAB) {
+        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES) {
         fprintf(stderr, "ERROR: -p mg needs a Krylov method: -cg, -gm or -bi\n");
         exit(EXIT_FAILURE);
     }
@@ -138,6 +141,10 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         (precond_mg_cycle().cycle == BIS_MG_CYCLE_K || precond_mg_cycle().cycle == BIS_MG_CYCLE_K_GCR)) {
         fprintf(stderr, "ERROR: -mg cycle=k|kgcr is not a fixed preconditioner, which -gm (left-preconditioned GMRES, not flexible) assumes: "
                         "use -cg or -bi, or cycle=v|w\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->method == SolverType::FGMRES && (a->unfused || a->host_scalars)) {
+        fprintf(stderr, "ERROR: -fgm is a device schedule (bis_fgmres_*) and has no call-by-call form: -unfused and -hostscalars do not apply\n");
         exit(EXIT_FAILURE);
     }
     // the other types run exact sweeps on the fp64 arrays and would gain nothing from rounded values

@@ -460,7 +460,8 @@ BIS_API bis_status bis_mg_apply(bis_ctx *ctx, const bis_mg *mg, double *out, con
  *   The dot products are sums of fused multiply-adds in a fixed order that depends on the length only (per-workgroup partial
  *   sums, summed in index order by the workgroup that arrives last); the coefficients stay in device scalars that every
  *   transition owns.  There is no early exit: the launch sequence is fixed, nothing is read back, two applies give the same
- *   bits.  A K-cycle is not a fixed linear operator: a method that assumes one (left-preconditioned GMRES) is not for it.
+ *   bits.  A K-cycle is not a fixed linear operator: a method that assumes one (left-preconditioned GMRES) is not for it;
+ *   flexible GMRES (bis_fgmres_*) is.
  * bis_mg_set_cycle blocks and allocates the extra scratch (two vectors on the coarse level of a W transition, three of a K
  * transition), so bis_mg_apply still allocates nothing and never blocks; setting V again restores V's bits.
  * BIS_ERR_INVALID: null arguments, cycle outside 0..3, cycle_levels < 0 (nothing changes).  bis_mg_cycle reports what is
@@ -943,6 +944,83 @@ BIS_API bis_status bis_mgmres_solution(bis_ctx *ctx, bis_mgmres *m, double *X_ou
 BIS_API bis_status bis_mgmres_status(bis_ctx *ctx, bis_mgmres *m, int j, int *iters, int *converged, int *n_hist,
                                      double *hist_host, int hist_cap);
 BIS_API bis_status bis_mgmres_destroy(bis_ctx *ctx, bis_mgmres *m);
+
+/* ---- restarted flexible GMRES(m) on one right-hand side, a device schedule (no reference counterpart) -------
+ * Saad's FGMRES: the preconditioner stands on the RIGHT and the preconditioned basis
+ * Z_n = M_n^-1 V_n is kept, so M_n may be a different operator at every step -- a
+ * K-cycle of bis_mg_* (BIS_MG_CYCLE_K, BIS_MG_CYCLE_K_GCR), any inner iteration --
+ * where bis_mgmres_* and the host's -gm assume one fixed M.  The residual that is
+ * minimised, estimated and recorded is the TRUE residual || b - A x ||, the quantity
+ * bis_cg_* records and the stopping test is written for.
+ * init: R = b - A x; history entry 0 is ||R||; threshold = tol ||R||; beta = ||R||;
+ * V_0 = R (1 / beta).  At position n of a cycle (n = iterations mod restart_len):
+ * Z_n = M^-1 V_n by bis_apply_preconditioner, straight into block n of Z (V_n
+ * survives: with outer_iters > 1 the apply writes its input, and is handed a copy);
+ * W = A Z_n by bis_spmv; modified Gram-Schmidt against V_0 .. V_n in the reference's
+ * order (h_i = (W, V_i), W -= h_i V_i; one fma per element, fma-accumulated dots);
+ * h_{n+1} = ||W||, V_{n+1} = W (1 / h_{n+1}); the new Hessenberg column is rotated by
+ * the stored Givens rotations, the new one is c = a / den, s = b / den with
+ * den = sqrt(a^2 + b^2); g_{n+1} = -s g_n, g_n = c g_n; the history entry is
+ * |g_{n+1}|, here the estimate of the true residual norm; the stop test is
+ * bis_mgmres_*'s (< threshold, non-finite, NaN).  At the end of a cycle, or at a
+ * stop: y by back substitution, x_i += sum_c y_c Z_c[i] (the sum from 0 over
+ * ascending c by fma, then added to x_i).  Restart: R = b - A x, beta = ||R|| with
+ * NO preconditioner apply; beta is written as ONE MORE history entry and tested
+ * against the threshold, V_0 = R (1 / beta).  So the history has iters + 1 +
+ * restarts entries: bis_fgmres_status returns that count as n_hist.
+ * Without a preconditioner FGMRES is GMRES: the histories of bis_fgmres_* and of
+ * bis_mgmres_* with n_rhs = 1 agree at the history gate (their reductions add in
+ * different orders).  With one, history entry k of the two differs: there the
+ * preconditioned, here the true residual.
+ * One iteration at position n issues one apply, one SpMV, n + 2 fused Gram-Schmidt /
+ * reduction passes and one scale, all single-vector kernels on 16-byte accesses
+ * (56 + 32 n bytes per row besides the SpMV and the apply); the reductions go by
+ * per-workgroup partial sums that the workgroup arriving last adds in index order
+ * (no floating-point atomics: two runs give the same bits); coefficients, rotations,
+ * g, y, the history and the flags live on the device and nothing is read back inside
+ * bis_fgmres_iterate.  x changes only at a restart or a stop; in between
+ * bis_fgmres_solution gives x + Z y.  After the stop no later call changes x, the
+ * history or the status: every launch of the schedule returns at once (launches of
+ * the preconditioner queued behind the stop may still run; their results are
+ * discarded).  b = 0 with x0 = 0 (beta = 0) stops at iteration 1, not converged; a
+ * lucky breakdown (h_{n+1} = 0) gives the estimate 0 and converges in that iteration.
+ * Memory: V is restart_len + 1 blocks, Z restart_len blocks, one more block W:
+ * (2 restart_len + 2) n doubles with a preconditioner, (restart_len + 2) n without
+ * (BIS_PC_NONE, or no set_preconditioner call: Z_n IS V_n, no Z storage and no copy;
+ * n counts rounded up to even, so that every block starts on 16 bytes), plus the
+ * preconditioner's scratch (SGS, ILU0, FSAI: one block; the two-stage types and
+ * ILU0_ITER: two; MG: the hierarchy's own) and restart_len^2 + 6 restart_len + 5
+ * doubles of state.
+ * Arguments, error codes and the order of calls are bis_mgmres_*'s with n_rhs = 1:
+ * A square, 1 <= restart_len <= 64; b and x n-vectors on 16-byte boundaries
+ * (bis_vec_alloc's are), x holds the start vector and is updated in place;
+ * set_preconditioner before init (BIS_ERR_INVALID after); a missing operand
+ * BIS_ERR_INVALID; n = 0: BIS_OK, nothing is launched.  The one difference:
+ * set_preconditioner takes EVERY type and every outer_iters / inner_iters that
+ * bis_apply_preconditioner takes -- the two-stage types, outer_iters > 1, and
+ * BIS_PC_MG (the hierarchy's operand in L_strict) with any cycle -- and refuses what
+ * that call refuses with its status: an MG operand of another size
+ * BIS_ERR_INVALID, MG with outer_iters != 1 BIS_ERR_UNSUPPORTED. */
+typedef struct bis_fgmres bis_fgmres;
+BIS_API bis_status bis_fgmres_create(bis_ctx *ctx, const bis_mat *A, const double *b, double *x, int restart_len,
+                                     bis_fgmres **out);
+BIS_API bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, int precond_type,
+                                                 const bis_mat *L_strict, const bis_mat *U_strict,
+                                                 const double *A_D, const double *A_D_inv,
+                                                 const double *L_D, const double *U_D,
+                                                 int outer_iters, int inner_iters);
+/* r0_norm_host (may be NULL) receives ||b - A x0||_2 (blocking) */
+BIS_API bis_status bis_fgmres_init(bis_ctx *ctx, bis_fgmres *s, double tol, double *r0_norm_host);
+/* non-blocking; the cycle position persists across calls (no call boundary restarts a cycle) */
+BIS_API bis_status bis_fgmres_iterate(bis_ctx *ctx, bis_fgmres *s, int n_iters);
+/* blocking: the explicit iterate into x_out (n entries on a 16-byte boundary, not x itself): x once the solve has
+ * stopped, x + Z y at the current step while it is live.  The handle's state does not change. */
+BIS_API bis_status bis_fgmres_solution(bis_ctx *ctx, bis_fgmres *s, double *x_out);
+/* blocking: iterations, converged flag, the number of history entries (iters + 1 + restarts) and the first
+ * min(n_hist, hist_cap) of them */
+BIS_API bis_status bis_fgmres_status(bis_ctx *ctx, bis_fgmres *s, int *iters, int *converged, int *n_hist,
+                                     double *hist_host, int hist_cap);
+BIS_API bis_status bis_fgmres_destroy(bis_ctx *ctx, bis_fgmres *s);
 
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
