@@ -406,6 +406,9 @@ class Context:
     def fgmres(self, A, b, x, restart=10):
         return FGMRES(self, A, b, x, restart)
 
+    def minres(self, A, b, x):
+        return MINRES(self, A, b, x)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -860,6 +863,51 @@ class FGMRES:
     def free(self):
         if self.h:
             self.ctx.lib.bis_fgmres_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class MINRES:
+    """Preconditioned MINRES on one right-hand side as a device schedule (bis_minres_*): symmetric A, definite or not, and
+    one fixed symmetric positive definite preconditioner (not checked).  The history is phibar: the residual norm in the
+    M^-1 norm, the 2-norm without a preconditioner; it never increases.  x is the iterate of the last history entry."""
+
+    def __init__(self, ctx, A, b, x):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self._keep = (A, b, x)
+        ctx.check(ctx.lib.bis_minres_create(ctx.h, A.h, C.c_void_p(b.ptr), C.c_void_p(x.ptr), C.byref(self.h)))
+
+    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
+        """CG.set_preconditioner's keywords, every type; an MG object stands for "mg" with its operand as Ls."""
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        if isinstance(pc, MG):
+            pc, Ls = "mg", pc.operand
+        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
+        self.ctx.check(self.ctx.lib.bis_minres_set_preconditioner(
+            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
+
+    def init(self, tol):
+        r0 = C.c_double()
+        self.ctx.check(self.ctx.lib.bis_minres_init(self.ctx.h, self.h, C.c_double(tol), C.byref(r0)))
+        return r0.value
+
+    def iterate(self, n):
+        self.ctx.check(self.ctx.lib.bis_minres_iterate(self.ctx.h, self.h, C.c_int(int(n))))
+
+    def status(self, hist_cap=4096):
+        """(iterations, converged, history[0 .. iterations])"""
+        iters, conv = C.c_int(), C.c_int()
+        hist = np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_minres_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv),
+                                                      hist.ctypes, C.c_int(hist_cap)))
+        return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_minres_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
 
 

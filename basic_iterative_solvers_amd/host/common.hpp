@@ -67,7 +67,7 @@ inline bis_mg_params &precond_mg_params() { static bis_mg_params p = {10, 256, 0
 // -mg cycle=v|w|k|kgcr,klev=N: the cycle of -p mg and the number of transitions it covers (bis_mg_set_cycle; 0: all but the last)
 struct MGCycle { int cycle = BIS_MG_CYCLE_V, levels = 0; };
 inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
-enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES }; // FGMRES: this build's addition (-fgm)
+enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES }; // FGMRES, MINRES: this build's additions (-fgm, -mr)
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
@@ -80,7 +80,7 @@ inline std::string to_string(PrecondType t) {
 }
 inline std::string to_string(SolverType t) {
     static const char *n[] = {"jacobi", "gauss-seidel", "symmetric-gauss-seidel", "gmres",
-                              "conjugate-gradient", "bicgstab", "fgmres"};
+                              "conjugate-gradient", "bicgstab", "fgmres", "minres"};
     return n[static_cast<int>(t)];
 }
 

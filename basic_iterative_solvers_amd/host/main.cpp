@@ -1,6 +1,6 @@
 // main.cpp -- CLI driver of the MI355X build; same command line and the same
 // stdout (residual table, summary, timer tree) as the reference's main.cpp.
-//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-bi>
+//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-bi>
 //        [-p j|gs|bgs|sgs|2st|s2st|ilu0|ilu0it|fsai|mg] [-mg KEY=VALUE,... (nu, cs, limit, levels, scale, omega, coarsening, cycle=v|w|k|kgcr, klev)] [-inner K] [-pprec 32|64] [-scale 0|1] [-rl N] [-unfused] [-dev K]
 #include <chrono>
 
@@ -11,6 +11,7 @@
 #include "methods/gauss_seidel.hpp"
 #include "methods/gmres.hpp"
 #include "methods/jacobi.hpp"
+#include "methods/minres.hpp"
 #include "postprocessing.hpp"
 #include "preprocessing.hpp"
 #include "solver_harness.hpp"
@@ -28,6 +29,7 @@ static void run(Args *cli_args, Timers *timers) {
     case SolverType::GMRES: solver = new GMRESSolver(cli_args); break;
     case SolverType::BiCGSTAB: solver = new BiCGSTABSolver(cli_args); break;
     case SolverType::FGMRES: solver = new FGMRESSolver(cli_args); break;
+    case SolverType::MINRES: solver = new MINRESSolver(cli_args); break;
     }
     auto A = std::make_unique<MatrixCRS>();
     if (!make_generated_matrix(cli_args->matrix_file_name, A.get())) {

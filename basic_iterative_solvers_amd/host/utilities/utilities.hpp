@@ -10,7 +10,8 @@
 // factorized sparse approximate inverse of bis_mat_fsai, applied as two SpMVs; `-pprec 32` rounds the factors those two
 // types apply by SpMV to fp32 (bis_mat_round_f32); `-p mg` is one V-cycle of the aggregation multigrid hierarchy of bis_mg_create
 // (or, with `-mg cycle=w|k|kgcr`, one W- or K-cycle) and `-mg key=value,...` sets its parameters; the method `-fgm` is flexible
-// GMRES(m) on the device schedule bis_fgmres_* (methods/fgmres.hpp), which takes every -p type, the K-cycles included.
+// GMRES(m) on the device schedule bis_fgmres_* (methods/fgmres.hpp), which takes every -p type, the K-cycles included; the method
+// `-mr` is MINRES for symmetric, possibly indefinite matrices on the device schedule bis_minres_* (methods/minres.hpp).
 #pragma once
 
 #include <sys/stat.h>
@@ -33,12 +34,14 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     else if (st == "-gm") a->method = SolverType::GMRES;
     else if (st == "-bi") a->method = SolverType::BiCGSTAB;
     else if (st == "-fgm") a->method = SolverType::FGMRES;
+    else if (st == "-mr") a->method = SolverType::MINRES;
     else {
         printf("ERROR: parse_cli: Please choose an available solver:"
                "\n-j (Jacobi)\n-gs (Gauss-Seidel)\n-sgs (Symmetric Gauss-Seidel)"
                "\n-gm ([Preconditioned] GMRES)\n-cg ([Preconditioned] Conjugate Gradient)"
                "\n-bi ([Preconditioned] BiCGSTAB)"
-               "\n-fgm ([Preconditioned] flexible GMRES, right-preconditioned)\n");
+               "\n-fgm ([Preconditioned] flexible GMRES, right-preconditioned)"
+               "\n-mr ([Preconditioned] MINRES, symmetric indefinite matrices)\n");
         exit(EXIT_FAILURE);
     }
     for (int i = 3; i < argc; ++i) {
@@ -132,7 +135,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else std::cout << "ERROR: assign_cli_inputs: Arguement \"" << arg << "\" not recongnized." << std::endl;
     }
     if (a->preconditioner == PrecondType::MG && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
-        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES) {
+        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES) {
         fprintf(stderr, "ERROR: -p mg needs a Krylov method: -cg, -gm or -bi\n");
         exit(EXIT_FAILURE);
     }
@@ -141,6 +144,16 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         (precond_mg_cycle().cycle == BIS_MG_CYCLE_K || precond_mg_cycle().cycle == BIS_MG_CYCLE_K_GCR)) {
         fprintf(stderr, "ERROR: -mg cycle=k|kgcr is not a fixed preconditioner, which -gm (left-preconditioned GMRES, not flexible) assumes: "
                         "use -cg or -bi, or cycle=v|w\n");
+        exit(EXIT_FAILURE);
+    }
+    // MINRES assumes one fixed symmetric positive definite M, as -gm assumes one fixed M
+    if (a->preconditioner == PrecondType::MG && a->method == SolverType::MINRES &&
+        (precond_mg_cycle().cycle == BIS_MG_CYCLE_K || precond_mg_cycle().cycle == BIS_MG_CYCLE_K_GCR)) {
+        fprintf(stderr, "ERROR: -mg cycle=k|kgcr is not a fixed preconditioner, which -mr (MINRES) assumes: use -fgm, or cycle=v|w\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->method == SolverType::MINRES && (a->unfused || a->host_scalars)) {
+        fprintf(stderr, "ERROR: -mr is a device schedule (bis_minres_*) and has no call-by-call form: -unfused and -hostscalars do not apply\n");
         exit(EXIT_FAILURE);
     }
     if (a->method == SolverType::FGMRES && (a->unfused || a->host_scalars)) {

@@ -1022,6 +1022,87 @@ BIS_API bis_status bis_fgmres_status(bis_ctx *ctx, bis_fgmres *s, int *iters, in
                                      double *hist_host, int hist_cap);
 BIS_API bis_status bis_fgmres_destroy(bis_ctx *ctx, bis_fgmres *s);
 
+/* ---- MINRES on the device (no reference counterpart) ---------------------------
+ * Preconditioned MINRES (Paige-Saunders) for a SYMMETRIC A, definite or not, and one
+ * fixed symmetric positive definite M: the method for shift-and-invert systems
+ * (H - sigma I) x = b with sigma inside the spectrum, where CG is not defined.  One
+ * SpMV, one apply and two reductions per iteration, seven n-vectors at any iteration
+ * count; the residual norm never increases; on SPD matrices it does what CG does.
+ * Without a preconditioner z = M^-1 r is r itself.
+ * init: r1 = b - A x0; y = M^-1 r1; beta1 = sqrt((r1, y)); r2 = r1; w = w2 = 0;
+ * oldb = 0, beta = beta1, dbar = 0, epsln = 0, phibar = beta1, cs = -1, sn = 0.
+ * History entry 0 is beta1, the value bis_minres_init returns; threshold = tol beta1.
+ * Iteration k = 1, 2, ...:
+ *     v = y (1/beta);  y = A v;  if k >= 2: y = y - (beta/oldb) r1
+ *     alpha = (v, y);  y = y - (alpha/beta) r2;  r1 <- r2;  r2 <- y;  y = M^-1 r2
+ *     oldb = beta;  beta = sqrt((r2, y))
+ *     oldeps = epsln;  delta = cs dbar + sn alpha;  gbar = sn dbar - cs alpha;
+ *     epsln = sn beta;  dbar = -cs beta
+ *     gamma = sqrt(gbar^2 + beta^2);  cs = gbar/gamma;  sn = beta/gamma;
+ *     phi = cs phibar;  phibar = sn phibar
+ *     w1 <- w2;  w2 <- w;  w = (v - oldeps w1 - delta w2) (1/gamma);  x = x + phi w
+ *     history[k] = phibar;  stop if phibar < threshold (converged) or phibar is not
+ *     finite (not converged)
+ * phibar_k is ||r_k|| in the M^-1 norm; without a preconditioner it is ||b - A x_k||_2.
+ * Rounding: every "vector - scalar * vector" above and x + phi w is one fma per
+ * element (the product is not rounded); the factors beta/oldb, alpha/beta, 1/gamma and
+ * 1/beta are formed first, one division each, and the scalings by 1/gamma and 1/beta
+ * are multiplications of their own.  The fused dots are bis_dot's: its grid, index map,
+ * two fma chains per lane and its order of the block and partial sums, which the
+ * workgroup that arrives last adds (no floating-point atomics, no waiting): two runs
+ * give the same bits.  The scalar lines round every operation separately.  So the
+ * history and x are, bit for bit, those of the same iteration made of bis_spmv,
+ * bis_dot, bis_subtract_vectors / bis_sum_vectors, bis_scale and
+ * bis_apply_preconditioner with the scalar lines in IEEE double on the host.
+ * Edge cases: beta = 0 with gamma != 0 is a lucky breakdown, phibar = 0, converged in
+ * that iteration; (r2, y) < 0 (M not positive definite) makes beta NaN and the solve
+ * stops, not converged, with that NaN in the history; b = 0 with x0 = 0 stops at
+ * iteration 1, not converged, as bis_fgmres_* does.
+ * Schedule per iteration: the SpMV; pass B (the r1 term with the partial sums of (v, y)
+ * fused); pass C (the r2 term; without a preconditioner the sums of (y, y) fused; with
+ * Jacobi, outer_iters = 1 and A_D on a 16-byte boundary (bis_vec_alloc's are; any
+ * other A_D takes the general path, same bits) the division by D and (r2, y)
+ * fused; every other type: bis_apply_preconditioner, then the dot as one more
+ * pass), whose last workgroup does
+ * the scalar lines, the history, the count and the stop test in one lane; pass D (w,
+ * x and the next v in one pass).  r1 <- r2 <- y and w1 <- w2 <- w rotate buffers by
+ * the iteration number, they are never copies.  Beside the SpMV and the apply that is
+ * 120 bytes per row and iteration (B 32, C 24, D 64; the fused CG moves 92), 136 with
+ * Jacobi or with the dot pass of the other types.  Memory: 7 n doubles (n rounded up
+ * to even) and the history, plus the preconditioner's scratch (SGS, ILU0, FSAI: one
+ * n-vector; the two-stage types and ILU0_ITER: two; MG: the hierarchy's own).
+ * Scalars, history and the stop flag stay on the device; bis_minres_iterate reads
+ * nothing back.  After the stop every launch returns at once except pass D of the
+ * stopping iteration, so x is the iterate the last history entry belongs to, and no
+ * later call changes x, the history or the status (launches of the preconditioner
+ * queued behind the stop may still run; nothing reads their results).
+ * bis_minres_set_preconditioner takes the arguments of bis_fgmres_set_preconditioner:
+ * every type, outer_iters and inner_iters that bis_apply_preconditioner takes for one
+ * vector, BIS_PC_MG (the hierarchy's operand in L_strict) included.  The library does
+ * NOT check that M is symmetric positive definite.  GS and BGS alone, an ILU(0) of a
+ * nonsymmetric factorisation, the two-stage types with few inner steps and the MG
+ * K-cycles (BIS_MG_CYCLE_K, BIS_MG_CYCLE_K_GCR) are not such operators: MINRES with
+ * them is undefined (use bis_fgmres_*).  Call it before bis_minres_init.
+ * Errors: null arguments, a non-square A, b or x off a 16-byte boundary,
+ * set_preconditioner after init, a missing operand, an MG operand of another size:
+ * BIS_ERR_INVALID; MG with outer_iters != 1: BIS_ERR_UNSUPPORTED; n = 0: BIS_OK,
+ * nothing is launched; *out is written on success only. */
+typedef struct bis_minres bis_minres;
+BIS_API bis_status bis_minres_create(bis_ctx *ctx, const bis_mat *A, const double *b, double *x, bis_minres **out);
+BIS_API bis_status bis_minres_set_preconditioner(bis_ctx *ctx, bis_minres *s, int precond_type,
+                                                 const bis_mat *L_strict, const bis_mat *U_strict,
+                                                 const double *A_D, const double *A_D_inv,
+                                                 const double *L_D, const double *U_D,
+                                                 int outer_iters, int inner_iters);
+/* blocking; r0_norm_host (may be NULL) receives beta1 */
+BIS_API bis_status bis_minres_init(bis_ctx *ctx, bis_minres *s, double tol, double *r0_norm_host);
+/* non-blocking: enqueues n_iters iterations */
+BIS_API bis_status bis_minres_iterate(bis_ctx *ctx, bis_minres *s, int n_iters);
+/* blocking: iterations, converged flag, history entries 0 .. iterations (at most hist_cap of them; may be NULL) */
+BIS_API bis_status bis_minres_status(bis_ctx *ctx, bis_minres *s, int *iters, int *converged, double *hist_host,
+                                     int hist_cap);
+BIS_API bis_status bis_minres_destroy(bis_ctx *ctx, bis_minres *s);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
