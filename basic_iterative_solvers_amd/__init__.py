@@ -16,7 +16,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "lib", "libbis_hip.so")
 
-PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8, "fsai": 9, "mg": 10})
+PC = dict(none=0, j=1, gs=2, bgs=3, sgs=4, **{"2st": 5, "s2st": 6, "ilu0": 7, "ilu0it": 8, "fsai": 9, "mg": 10, "bj": 11})
 
 _lib = None
 
@@ -45,6 +45,7 @@ def load_library():
         _lib.bis_mat_fsai_kernel.restype = C.c_char_p
         _lib.bis_mg_operand.restype = C.c_void_p
         _lib.bis_mg_level_matrix.restype = C.c_void_p
+        _lib.bis_bj_operand.restype = C.c_void_p
     return _lib
 
 
@@ -265,6 +266,12 @@ class Context:
                 m.free()
                 raise
         return m
+
+    def bjacobi(self, A, block_size=None, block_ptr=None, symmetrize=False):
+        """The block-Jacobi handle of A (bis_bj_create): a BJ object.  Uniform blocks of `block_size` (1..32) consecutive rows,
+        or the blocks of `block_ptr` (n_blocks + 1 ascending row indices from 0 to n); `symmetrize` makes every inverse block
+        equal its transpose bit for bit (for CG and MINRES).  Preconditioner "bj" takes Ls=BJ.operand."""
+        return BJ(self, A, block_size, block_ptr, symmetrize)
 
     # ---- kernels (kernels.hpp names) ---------------------------------------
     def spmv(self, A, x, y):
@@ -652,6 +659,66 @@ class MG:
             self.h = C.c_void_p()
 
 
+class BJParams(C.Structure):
+    """bis_bj_params."""
+    _fields_ = [("block_size", C.c_int), ("block_ptr", C.POINTER(C.c_int32)), ("n_blocks", C.c_int64), ("symmetrize", C.c_int)]
+
+
+class BJ:
+    """bis_bj: the inverted dense diagonal blocks of A; their block-diagonal product is the preconditioner "bj" (pass
+    `.operand` as Ls, or the object itself as the type).  A is not kept by the library."""
+
+    def __init__(self, ctx, A, block_size=None, block_ptr=None, symmetrize=False):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        if block_ptr is not None:
+            bp = np.ascontiguousarray(block_ptr, dtype=np.int32)
+            p = BJParams(0 if block_size is None else int(block_size), bp.ctypes.data_as(C.POINTER(C.c_int32)), len(bp) - 1,
+                         int(bool(symmetrize)))
+        else:
+            if block_size is None:
+                raise BisError("Context.bjacobi: give block_size or block_ptr")
+            p = BJParams(int(block_size), None, 0, int(bool(symmetrize)))
+        ctx.check(ctx.lib.bis_bj_create(ctx.h, A.h, C.byref(p), C.byref(self.h)))
+        self.n_blocks, self.max_block, self.value_count = self.info()
+        self.operand = Mat(ctx, C.c_void_p(ctx.lib.bis_bj_operand(self.h)))
+
+    def info(self):
+        """(n_blocks, rows of the largest block, stored values = the sum of the squared block sizes) (bis_bj_info)."""
+        nb, mb, vc = C.c_int64(), C.c_int(), C.c_int64()
+        self.ctx.lib.bis_bj_info(self.h, C.byref(nb), C.byref(mb), C.byref(vc))
+        return nb.value, mb.value, vc.value
+
+    def blocks(self):
+        """(values, offsets): inverse block b row-major at values[offsets[b]:offsets[b + 1]] (bis_bj_blocks)."""
+        vals = np.zeros(self.value_count, dtype=np.float64)
+        offs = np.zeros(self.n_blocks + 1, dtype=np.int64)
+        self.ctx.check(self.ctx.lib.bis_bj_blocks(self.ctx.h, self.h, vals.ctypes, offs.ctypes))
+        return vals, offs
+
+    def apply(self, out, inp):
+        """out = M^-1 inp (bis_bj_apply); out may alias inp."""
+        self.ctx.check(self.ctx.lib.bis_bj_apply(self.ctx.h, self.h, C.c_void_p(out.ptr), C.c_void_p(inp.ptr)))
+
+    def mapply(self, out, inp, k):
+        """The same on k interleaved columns (bis_bj_mapply); out may alias inp."""
+        self.ctx.check(self.ctx.lib.bis_bj_mapply(self.ctx.h, self.h, C.c_void_p(out.ptr), C.c_void_p(inp.ptr), C.c_int(int(k))))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.bis_bj_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+def _handle_pc(pc, Ls):
+    """set_preconditioner's first argument may be an MG or a BJ object: its type with its operand as Ls."""
+    if isinstance(pc, MG):
+        return "mg", pc.operand
+    if isinstance(pc, BJ):
+        return "bj", pc.operand
+    return pc, Ls
+
+
 class CG:
     def __init__(self, ctx, A, b, x, A_D=None):
         self.ctx = ctx
@@ -662,6 +729,7 @@ class CG:
     def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
         def p(v):
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        pc, Ls = _handle_pc(pc, Ls)
         self._keep = (Ls, Us, A_D, A_D_inv, L_D, U_D)
         self.ctx.check(self.ctx.lib.bis_cg_set_preconditioner(
             self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
@@ -702,6 +770,7 @@ class MCG:
     def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
         def p(v):
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        pc, Ls = _handle_pc(pc, Ls)
         self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
         self.ctx.check(self.ctx.lib.bis_mcg_set_preconditioner(
             self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
@@ -742,6 +811,7 @@ class MBiCGSTAB:
     def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
         def p(v):
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        pc, Ls = _handle_pc(pc, Ls)
         self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
         self.ctx.check(self.ctx.lib.bis_mbicgstab_set_preconditioner(
             self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
@@ -784,6 +854,7 @@ class MGMRES:
     def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
         def p(v):
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        pc, Ls = _handle_pc(pc, Ls)
         self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
         self.ctx.check(self.ctx.lib.bis_mgmres_set_preconditioner(
             self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
@@ -832,8 +903,7 @@ class FGMRES:
         """MGMRES.set_preconditioner's keywords, every type; an MG object stands for "mg" with its operand as Ls."""
         def p(v):
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        if isinstance(pc, MG):
-            pc, Ls = "mg", pc.operand
+        pc, Ls = _handle_pc(pc, Ls)
         self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
         self.ctx.check(self.ctx.lib.bis_fgmres_set_preconditioner(
             self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
@@ -881,8 +951,7 @@ class MINRES:
         """CG.set_preconditioner's keywords, every type; an MG object stands for "mg" with its operand as Ls."""
         def p(v):
             return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        if isinstance(pc, MG):
-            pc, Ls = "mg", pc.operand
+        pc, Ls = _handle_pc(pc, Ls)
         self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
         self.ctx.check(self.ctx.lib.bis_minres_set_preconditioner(
             self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),

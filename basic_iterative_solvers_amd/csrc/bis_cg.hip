@@ -290,7 +290,7 @@ bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                      const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D,
                                      int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, cg && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_MG && outer_iters >= 1 && inner_iters >= 0,
+    BIS_REQUIRE(ctx, cg && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_BLOCK_JACOBI && outer_iters >= 1 && inner_iters >= 0,
                 "bis_cg_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !cg->initialised && cg->enqueued == 0, "bis_cg_set_preconditioner: call it before bis_cg_init / bis_cg_iterate");
     BIS_REQUIRE(ctx, precond_type != BIS_PC_FSAI || (L_strict && U_strict && L_strict->n_rows == cg->n && U_strict->n_rows == cg->n),
@@ -303,12 +303,20 @@ bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
             return BIS_ERR_UNSUPPORTED;
         }
     }
+    if (precond_type == BIS_PC_BLOCK_JACOBI) {
+        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == cg->n,
+                    "bis_cg_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
+        if (cg->dist || outer_iters != 1) {
+            ctx->err = "bis_cg_set_preconditioner: block Jacobi on a distributed handle, or with outer_iters != 1, is not built";
+            return BIS_ERR_UNSUPPORTED;
+        }
+    }
     if (cg->z == cg->r) { // z aliased r (no preconditioner at creation): it needs its own storage now
         cg->z = nullptr;
         bis_status st = bis_vec_alloc(ctx, cg->n, &cg->z);
         if (st != BIS_OK) { cg->z = cg->r; return st; }
     }
-    if (!cg->pc_work && precond_type != BIS_PC_FSAI && precond_type != BIS_PC_MG) { bis_status st = bis_vec_alloc(ctx, cg->n, &cg->pc_work); if (st != BIS_OK) return st; }
+    if (!cg->pc_work && precond_type != BIS_PC_FSAI && precond_type != BIS_PC_MG && precond_type != BIS_PC_BLOCK_JACOBI) { bis_status st = bis_vec_alloc(ctx, cg->n, &cg->pc_work); if (st != BIS_OK) return st; }
     cg->pc = precond_type;
     cg->pcL = L_strict; cg->pcU = U_strict;
     cg->pcAD = A_D; cg->pcADinv = A_D_inv; cg->pcLD = L_D; cg->pcUD = U_D;

@@ -359,7 +359,7 @@ bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, int precon
                                          const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, s && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_MG && outer_iters >= 1 && inner_iters >= 0,
+    BIS_REQUIRE(ctx, s && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_BLOCK_JACOBI && outer_iters >= 1 && inner_iters >= 0,
                 "bis_fgmres_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !s->initialised && s->enqueued == 0,
                 "bis_fgmres_set_preconditioner: call it before bis_fgmres_init / bis_fgmres_iterate");
@@ -368,6 +368,11 @@ bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, int precon
         BIS_REQUIRE(ctx, L_strict && L_strict->mg && L_strict->n_rows == s->n,
                     "bis_fgmres_set_preconditioner: MG needs the operand of a hierarchy of the solver's size in L_strict");
         if (outer_iters != 1) { ctx->err = "bis_fgmres_set_preconditioner: MG with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
+    }
+    if (pc == BIS_PC_BLOCK_JACOBI) {
+        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == s->n,
+                    "bis_fgmres_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
+        if (outer_iters != 1) { ctx->err = "bis_fgmres_set_preconditioner: block Jacobi with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
     }
     // the operands the type reads (bis_apply_preconditioner would refuse them only inside bis_fgmres_iterate)
     const bool two = pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
@@ -378,7 +383,7 @@ bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, int precon
     const bool need_AD = pc == BIS_PC_JACOBI || pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL ||
                          pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
     const bool need_ADinv = two || pc == BIS_PC_ILU0_ITER;
-    if (pc != BIS_PC_MG) {
+    if (pc != BIS_PC_MG && pc != BIS_PC_BLOCK_JACOBI) {
         BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_fgmres_set_preconditioner: the type needs a triangle that is null");
         BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == s->n) && (!upper || U_strict->n_rows == s->n),
                     "bis_fgmres_set_preconditioner: a triangle of another size");

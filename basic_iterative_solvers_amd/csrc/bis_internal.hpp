@@ -230,6 +230,7 @@ struct bis_mat {
     const char *fsai_kernel = "";           // the instance of fsai_rows_kernel that computed this FSAI factor G (bis_mat_fsai_kernel)
     struct bis_mg *mg = nullptr;            // the hierarchy this matrix is the preconditioner operand of (bis_mg_operand): an n x n matrix without
                                             // entries that the hierarchy owns; bis_mat_destroy leaves it alone
+    struct bis_bj *bj = nullptr;            // ... or the block-Jacobi handle (bis_bj_operand), in the same way
 };
 
 #define BIS_HIP_CHECK(ctx, call)                                               \

@@ -645,6 +645,7 @@ bis_status bis_mat_destroy(bis_ctx *ctx, bis_mat *A) {
     BIS_CTX_OK(ctx);
     if (!A) return BIS_OK;
     if (A->mg) return BIS_OK; // the operand of a multigrid hierarchy (bis_mg_operand) goes with bis_mg_destroy
+    if (A->bj) return BIS_OK; // ... and the operand of a block-Jacobi handle (bis_bj_operand) with bis_bj_destroy
     hipStreamSynchronize(ctx->stream);
     bis_trsv_drop(A, /*chains=*/true);
     if (!A->view) {

@@ -401,7 +401,7 @@ bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precon
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (precond_type == BIS_PC_MG) { ctx->err = "bis_mgmres_set_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
-    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_FSAI && outer_iters >= 1 && inner_iters >= 0,
+    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && (precond_type <= BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI) && outer_iters >= 1 && inner_iters >= 0,
                 "bis_mgmres_set_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0,
                 "bis_mgmres_set_preconditioner: call it before bis_mgmres_init / bis_mgmres_iterate");
@@ -419,10 +419,13 @@ bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precon
     const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
                        precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
     const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
+    if (precond_type == BIS_PC_BLOCK_JACOBI) // the handle's operand (bis_bj_operand) and nothing else: no diagonal, no TMP, no WORK
+        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == m->n,
+                    "bis_mgmres_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
     BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mgmres_set_preconditioner: the type needs a triangle that is null");
     BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n),
                 "bis_mgmres_set_preconditioner: a triangle of another size");
-    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
+    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
                                    (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
                 "bis_mgmres_set_preconditioner: the type needs a diagonal that is null");
     // every allocation first: a failure leaves the handle as it was

@@ -89,8 +89,14 @@ bis_status bis_mapply_preconditioner(bis_ctx *ctx, int pc, int64_t n, int n_rhs,
                                      double *IN, double *TMP, double *WORK, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (pc == BIS_PC_MG) { ctx->err = "bis_mapply_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
-    BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1 && pc >= BIS_PC_NONE && pc <= BIS_PC_FSAI, "bis_mapply_preconditioner: bad arguments");
+    BIS_REQUIRE(ctx, n >= 0 && outer_iters >= 1 && pc >= BIS_PC_NONE && (pc <= BIS_PC_FSAI || pc == BIS_PC_BLOCK_JACOBI),
+                "bis_mapply_preconditioner: bad arguments");
     BIS_REQUIRE(ctx, n_rhs >= 1 && n_rhs <= kMpMaxK, "bis_mapply_preconditioner: n_rhs must be between 1 and 8");
+    if (pc == BIS_PC_BLOCK_JACOBI) { // the handle whose operand is in L_strict (bis_bj_operand); nothing else is read
+        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == n, "bis_mapply_preconditioner: block Jacobi needs the operand of a handle of size n in L_strict");
+        if (outer_iters != 1) { ctx->err = "bis_mapply_preconditioner: outer_iters must be 1 on interleaved blocks"; return BIS_ERR_UNSUPPORTED; }
+        return bis_bj_mapply(ctx, L_strict->bj, OUT, IN, n_rhs);
+    }
     if (pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {
         ctx->err = "bis_mapply_preconditioner: the two-stage Gauss-Seidel types have no multi-vector form";
         return BIS_ERR_UNSUPPORTED;

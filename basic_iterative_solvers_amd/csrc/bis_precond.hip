@@ -36,6 +36,11 @@ bis_status bis_apply_preconditioner(bis_ctx *ctx, int pc, int64_t n, const bis_m
         if (outer_iters != 1) { ctx->err = "bis_apply_preconditioner: MG with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
         return bis_mg_apply(ctx, L_strict->mg, output, input);
     }
+    if (pc == BIS_PC_BLOCK_JACOBI) { // (not in the reference) the inverse blocks of the handle whose operand is in L_strict (bis_bj_operand); nothing else is read
+        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == n, "bis_apply_preconditioner: block Jacobi needs the operand of a handle of size n in L_strict");
+        if (outer_iters != 1) { ctx->err = "bis_apply_preconditioner: block Jacobi with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
+        return bis_bj_apply(ctx, L_strict->bj, output, input);
+    }
     if (pc == BIS_PC_ILU0_ITER)
         BIS_REQUIRE(ctx, L_strict && U_strict && inner_iters >= 0 && (n == 0 || (tmp && work && tmp != work && tmp != output &&
                          tmp != input && work != output && work != input)),

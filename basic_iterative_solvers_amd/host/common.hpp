@@ -51,9 +51,9 @@
 using Interface = void *; // the SMAX seam of the reference (common.hpp:18-24) is the C ABI here
 #define SMAX_ARGS(...)
 
-enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8), FSAI (9) and MG (10) are this build's additions
+enum class PrecondType { // ordinals == BIS_PC_* == reference common.hpp:38-47; ILU0Iter (8), FSAI (9), MG (10) and BlockJacobi (11) are this build's additions
     None, Jacobi, GaussSeidel, BackwardsGaussSeidel, SymmetricGaussSeidel, TwoStageGS,
-    SymmetricTwoStageGS, ILU0, ILU0Iter, FSAI, MG
+    SymmetricTwoStageGS, ILU0, ILU0Iter, FSAI, MG, BlockJacobi
 };
 
 // -inner K: inner sweeps of the two-stage Gauss-Seidel types and of -p ilu0it, at run time; the default is the
@@ -67,6 +67,8 @@ inline bis_mg_params &precond_mg_params() { static bis_mg_params p = {10, 256, 0
 // -mg cycle=v|w|k|kgcr,klev=N: the cycle of -p mg and the number of transitions it covers (bis_mg_set_cycle; 0: all but the last)
 struct MGCycle { int cycle = BIS_MG_CYCLE_V, levels = 0; };
 inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
+// -bs N: rows per block of -p bj (bis_bj_params.block_size); 0: not given, the dof of the matrix' grid hint where that is above 1
+inline int &precond_block_size() { static int b = 0; return b; }
 enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES }; // FGMRES, MINRES: this build's additions (-fgm, -mr)
 
 inline std::string to_string(PrecondType t) {
@@ -76,6 +78,7 @@ inline std::string to_string(PrecondType t) {
     if (t == PrecondType::ILU0Iter) return "incomplete LU(0), iterative solves (" + std::to_string(precond_inner_iters()) + ")";
     if (t == PrecondType::FSAI) return "factorized sparse approximate inverse";
     if (t == PrecondType::MG) return "aggregation multigrid";
+    if (t == PrecondType::BlockJacobi) return "block jacobi";
     return n[static_cast<int>(t)];
 }
 inline std::string to_string(SolverType t) {

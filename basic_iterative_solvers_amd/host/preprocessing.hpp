@@ -2,7 +2,7 @@
 // allocate + initialise the solver's vectors, optional symmetric diagonal
 // scaling, split A into its strict triangles and diagonal (on the device for
 // generated matrices, on the host for file input), optional ILU(0) or FSAI
-// factors or the multigrid hierarchy, initial residual and stopping criterion.
+// factors, the multigrid hierarchy or the block-Jacobi handle, initial residual and stopping criterion.
 #pragma once
 
 #include "common.hpp"
@@ -34,6 +34,34 @@ inline void round_precond_factors(Solver *s) {
         worst = change > worst ? change : worst;
     }
     std::cout << "preconditioner values rounded to fp32: max relative change " << worst << std::endl;
+}
+
+// -p bj: the inverted diagonal blocks of A (after -scale and -perm); the handle's operand takes the place of the strict lower triangle
+inline void factor_block_jacobi(Solver *s) {
+    int bs = precond_block_size();
+    if (bs == 0) {
+        int64_t g[4] = {0, 0, 0, 0};
+        bis::check(bis_mat_grid_hint(s->A->dev, g), "bis_mat_grid_hint");
+        if (g[0] > 0 && g[3] > 1 && g[3] <= 32) bs = (int)g[3];
+    }
+    if (bs == 0) {
+        fprintf(stderr, "ERROR: -p bj: the matrix carries no grid hint with more than one unknown per node to take the block size from: give -bs N (1 <= N <= 32)\n");
+        exit(EXIT_FAILURE);
+    }
+    // CG and MINRES assume a symmetric M: the inverse blocks are symmetrised there (bit for bit), elsewhere they stay as computed
+    const bool sym = s->method == SolverType::ConjugateGradient || s->method == SolverType::MINRES;
+    const bis_bj_params p = {bs, nullptr, 0, sym ? 1 : 0};
+    const bis_status st = bis_bj_create(bis::ctx(), s->A->dev, &p, &s->bj);
+    if (st == BIS_ERR_ZERO_DIAG || st == BIS_ERR_INVALID) { fprintf(stderr, "%s\n", bis_last_error(bis::ctx())); exit(EXIT_FAILURE); }
+    bis::check(st, "bis_bj_create");
+    s->L_strict->free_host();
+    s->L_strict->adopt(const_cast<bis_mat *>(bis_bj_operand(s->bj)));
+    int64_t n_blocks = 0, values = 0;
+    int max_block = 0;
+    bis_bj_info(s->bj, &n_blocks, &max_block, &values);
+    const int64_t last = n_blocks > 0 ? (int64_t)s->N - (n_blocks - 1) * bs : 0;
+    std::cout << "block Jacobi: " << n_blocks << " blocks of " << bs << " rows (last " << last << "), " << values << " stored values"
+              << (s->perm_store ? ", consecutive rows of the permuted matrix" : "") << std::endl;
 }
 
 inline void factor_LU(Solver *s) {
@@ -104,6 +132,7 @@ inline void factor_LU(Solver *s) {
             std::cout << std::endl;
         }
     }
+    if (s->preconditioner == PrecondType::BlockJacobi) factor_block_jacobi(s);
 }
 
 inline void preprocessing(Args *cli_args, Solver *solver, Timers *timers, std::unique_ptr<MatrixCRS> &A) {

@@ -42,6 +42,8 @@ class Solver {
     double *perm_store = nullptr;
     // -p mg: the hierarchy; its operand sits in L_strict->dev, where bis_apply_preconditioner and bis_cg_set_preconditioner look for it
     bis_mg *mg = nullptr;
+    // -p bj: the block-Jacobi handle, its operand in L_strict->dev in the same way
+    bis_bj *bj = nullptr;
     void keep_permutation(const std::vector<int> &perm) {
         const long n = (long)perm.size();
         std::vector<double> raw((n + 1) / 2 + 1, 0.0);
@@ -96,6 +98,10 @@ class Solver {
         if (mg) { // the operand belongs to the hierarchy
             if (L_strict) L_strict->dev = nullptr;
             bis_mg_destroy(bis::ctx(), mg);
+        }
+        if (bj) { // ... or to the block-Jacobi handle
+            if (L_strict) L_strict->dev = nullptr;
+            bis_bj_destroy(bis::ctx(), bj);
         }
         delete[] collected_residual_norms;
         delete[] time_per_iteration;

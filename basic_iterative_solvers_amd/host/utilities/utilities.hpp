@@ -11,7 +11,8 @@
 // types apply by SpMV to fp32 (bis_mat_round_f32); `-p mg` is one V-cycle of the aggregation multigrid hierarchy of bis_mg_create
 // (or, with `-mg cycle=w|k|kgcr`, one W- or K-cycle) and `-mg key=value,...` sets its parameters; the method `-fgm` is flexible
 // GMRES(m) on the device schedule bis_fgmres_* (methods/fgmres.hpp), which takes every -p type, the K-cycles included; the method
-// `-mr` is MINRES for symmetric, possibly indefinite matrices on the device schedule bis_minres_* (methods/minres.hpp).
+// `-mr` is MINRES for symmetric, possibly indefinite matrices on the device schedule bis_minres_* (methods/minres.hpp);
+// `-p bj` is block Jacobi (bis_bj_create) on blocks of `-bs N` consecutive rows (default: the dof of the grid hint).
 #pragma once
 
 #include <sys/stat.h>
@@ -58,7 +59,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 {"bgs", PrecondType::BackwardsGaussSeidel}, {"sgs", PrecondType::SymmetricGaussSeidel},
                 {"2st", PrecondType::TwoStageGS}, {"s2st", PrecondType::SymmetricTwoStageGS},
                 {"ilu0", PrecondType::ILU0}, {"ilu0it", PrecondType::ILU0Iter},
-                {"fsai", PrecondType::FSAI}, {"mg", PrecondType::MG}};
+                {"fsai", PrecondType::FSAI}, {"mg", PrecondType::MG}, {"bj", PrecondType::BlockJacobi}};
             auto it = pcs.find(pt);
             if (it == pcs.end()) {
                 fprintf(stderr, "ERROR: assign_cli_inputs: Please choose an available preconditioner type: "
@@ -67,7 +68,8 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                                 "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)"
                                 "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)"
                                 "\n-p fsai (Factorized sparse approximate inverse on the pattern of tril(A))"
-                                "\n-p mg (Aggregation multigrid cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=0)\n");
+                                "\n-p mg (Aggregation multigrid cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=0)"
+                                "\n-p bj (Block Jacobi on blocks of -bs N consecutive rows, N = 1..32; default: the dof of the grid hint)\n");
                 exit(EXIT_FAILURE);
             }
             a->preconditioner = it->second;
@@ -88,6 +90,15 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 exit(EXIT_FAILURE);
             }
             precond_value_bits() = a->pprec;
+        }
+        else if (arg == "-bs" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const int bs = v.find_first_not_of("0123456789") == std::string::npos && v.size() <= 3 ? atoi(v.c_str()) : 0;
+            if (bs < 1 || bs > 32) {
+                fprintf(stderr, "ERROR: -bs N: the rows per block of -p bj, 1 <= N <= 32\n");
+                exit(EXIT_FAILURE);
+            }
+            precond_block_size() = bs;
         }
         else if (arg == "-mg" && i + 1 < argc) {
             bis_mg_params &p = precond_mg_params();
@@ -137,6 +148,11 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     if (a->preconditioner == PrecondType::MG && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
         a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES) {
         fprintf(stderr, "ERROR: -p mg needs a Krylov method: -cg, -gm or -bi\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->preconditioner == PrecondType::BlockJacobi && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
+        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES) {
+        fprintf(stderr, "ERROR: -p bj needs a Krylov method: -cg, -gm, -fgm, -mr or -bi\n");
         exit(EXIT_FAILURE);
     }
     // a K-cycle changes with its right-hand side: left-preconditioned GMRES builds its basis for ONE operator M^-1 A, and there is no flexible GMRES here

@@ -71,7 +71,9 @@ enum {
     BIS_PC_FSAI = 9,
     /* not in the reference: aggregation multigrid, one cycle of a bis_mg hierarchy (bis_mg_create; the V-cycle unless
      * bis_mg_set_cycle chose another) */
-    BIS_PC_MG = 10
+    BIS_PC_MG = 10,
+    /* not in the reference: block Jacobi, the inverted dense diagonal blocks of a bis_bj handle (bis_bj_create) */
+    BIS_PC_BLOCK_JACOBI = 11
 };
 
 typedef struct bis_ctx bis_ctx; /* device + stream + scratch (SMAX::Interface
@@ -481,6 +483,59 @@ BIS_API const bis_mat *bis_mg_level_matrix(const bis_mg *mg, int level);
 BIS_API bis_status bis_mg_level_aggregates(bis_ctx *ctx, const bis_mg *mg, int level, int32_t *host);
 BIS_API bis_status bis_mg_level_weights(bis_ctx *ctx, const bis_mg *mg, int level, double *host);
 
+/* ---- block Jacobi (bis_bjacobi.hip); no reference counterpart -------------------------------------------------------------
+ * M^-1 = diag(B_0^-1, B_1^-1, ...): the dense diagonal blocks of A over blocks of consecutive rows, inverted once on the
+ * device and applied as a block-diagonal product.  No dependency between rows, any row order, 1..8 right-hand sides; SPD for
+ * SPD A (with symmetrize, symmetric bit for bit).  Blocks of nx rows on a grid: line Jacobi.
+ *
+ * Blocks.  block_ptr == NULL: uniform blocks of block_size (1..32) consecutive rows, the last one shorter if n is not a
+ * multiple.  Otherwise block b covers rows [block_ptr[b], block_ptr[b + 1]), block_ptr (host, n_blocks + 1 entries) starting
+ * at 0, ascending strictly, ending at n, every block of 1..32 rows; block_size is then ignored.
+ *
+ * Extraction.  Block b covers rows and columns [s, e).  It starts as zeros; every entry of rows s .. e - 1 whose column lies
+ * in [s, e) is added to its place in the row's storage order (repeated entries sum left to right); entries outside the range
+ * are not read.
+ *
+ * Inversion.  Gauss-Jordan with partial pivoting on [B | I], every operation rounded on its own (no fused multiply-add).
+ * Step k = 0 .. m - 1: the pivot row is the first row i >= k with the largest |a_ik| (p = k, then i ascending, p = i where
+ * |a_ik| > |a_pk|); rows k and p are swapped; r = 1 / a_kk; row k becomes row k * r (all 2 m columns, a_kk included); every
+ * other row i becomes a_ij - (f * a_kj) over all 2 m columns with f = a_ik taken before the update, the product rounded,
+ * then the difference.  The right half is R = B^-1.  A pivot that is 0 or not finite: BIS_ERR_ZERO_DIAG.
+ * symmetrize = 1: every R_ij becomes (R_ij + R_ji) * 0.5, so R equals its transpose bit for bit.
+ *
+ * Apply.  out_i = sum_j R_ij * in_j over the block's columns in ascending order: the first product starts the sum, every
+ * further product is rounded and then added, every addition rounded (no fused multiply-add).  Column j of
+ * bis_bj_mapply (1..8 interleaved columns, bis_spmm's layout) has the bits of bis_bj_apply on column j.  Both are
+ * stream-ordered, allocate nothing and allow out == in (OUT == IN).  Streamed bytes: 8 sum_b m_b^2 + 16 n n_rhs; a handle
+ * with a block_ptr also reads 12 bytes of index per block.
+ *
+ * BIS_ERR_INVALID: null arguments (params included), A not square, a row-range view, block_size outside 1..32, a block_ptr
+ * that does not start at 0, does not ascend strictly, does not end at n or has a block of more than 32 rows, n_rhs outside
+ * 1..8.  *out is written on success only, and a failing bis_bj_create leaves nothing allocated.  n = 0: BIS_OK, nothing is
+ * launched.  bis_bj_create blocks; everything runs on the device without floating-point atomics: two creates and two
+ * applies give the same bits.  A is not kept: the handle may outlive it. */
+typedef struct bis_bj bis_bj;
+typedef struct {
+    int block_size;           /* 1..32: uniform blocks of consecutive rows, the last one shorter if n is not a multiple;
+                                 ignored when block_ptr is given */
+    const int32_t *block_ptr; /* host, n_blocks + 1 entries, block_ptr[0] = 0, strictly ascending, last = n,
+                                 every block 1..32 rows; NULL: uniform */
+    int64_t n_blocks;
+    int symmetrize;           /* 1: every inverse block R becomes (R + R^T) * 0.5 elementwise (bit-symmetric) */
+} bis_bj_params;
+BIS_API bis_status bis_bj_create(bis_ctx *ctx, const bis_mat *A, const bis_bj_params *params, bis_bj **out);
+BIS_API bis_status bis_bj_destroy(bis_ctx *ctx, bis_bj *bj);
+BIS_API bis_status bis_bj_apply(bis_ctx *ctx, const bis_bj *bj, double *out, const double *in);
+BIS_API bis_status bis_bj_mapply(bis_ctx *ctx, const bis_bj *bj, double *OUT, const double *IN, int n_rhs);
+/* The handle as the preconditioner of type BIS_PC_BLOCK_JACOBI: an n x n matrix without entries that bj owns (bis_mat_destroy
+ * on it does nothing) and that leads back to bj; every entry point but the preconditioner dispatch sees the zero matrix. */
+BIS_API const bis_mat *bis_bj_operand(const bis_bj *bj);
+/* Number of blocks, rows of the largest block, sum of m_b^2; any pointer may be NULL.  BIS_ERR_INVALID: null handle. */
+BIS_API bis_status bis_bj_info(const bis_bj *bj, int64_t *n_blocks, int *max_block, int64_t *value_count);
+/* The inverse blocks to the host: block b row-major at host_values[host_offsets[b]], host_offsets (n_blocks + 1 entries)
+ * the running sum of m_b^2; either pointer may be NULL.  Blocking. */
+BIS_API bis_status bis_bj_blocks(bis_ctx *ctx, const bis_bj *bj, double *host_values, int64_t *host_offsets);
+
 /* ---- the operator surface (kernels.hpp) ------------------------------------ */
 /* spmv / native_spmv, kernels.hpp:22-52: y = A x. */
 BIS_API bis_status bis_spmv(bis_ctx *ctx, const bis_mat *A, const double *x,
@@ -644,7 +699,10 @@ BIS_API const char *bis_itrsv_kernel(const bis_mat *T_strict);
  * distinct from input and output (BIS_ERR_INVALID); output may alias input.
  * BIS_PC_MG (10): output = bis_mg_apply(input) of the hierarchy whose operand (bis_mg_operand) is in the L_strict argument;
  * the operand must have n rows (BIS_ERR_INVALID), no other argument is read, output may alias input; outer_iters != 1:
- * BIS_ERR_UNSUPPORTED. */
+ * BIS_ERR_UNSUPPORTED.
+ * BIS_PC_BLOCK_JACOBI (11): output = bis_bj_apply(input) of the handle whose operand (bis_bj_operand) is in the L_strict
+ * argument, under the rules of BIS_PC_MG: n rows or BIS_ERR_INVALID, nothing else read, output may alias input,
+ * outer_iters != 1: BIS_ERR_UNSUPPORTED. */
 BIS_API bis_status bis_apply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
@@ -695,7 +753,9 @@ BIS_API bis_status bis_mitrsv(bis_ctx *ctx, const bis_mat *T_strict, const doubl
  * BIS_ERR_UNSUPPORTED.  TMP, WORK: n x n_rhs blocks, needed by SGS / ILU0 / ILU0_ITER / FSAI (TMP) and ILU0_ITER (WORK).
  * FSAI: two bis_spmm, TMP distinct from IN and OUT; column j equals the single-vector apply wherever bis_spmm's column j
  * equals bis_spmv's (every matrix that does not run the wave-per-row SpMV).  BIS_PC_MG has no multi-vector form:
- * BIS_ERR_UNSUPPORTED here and in bis_mcg_set_preconditioner, bis_mbicgstab_set_preconditioner, bis_mgmres_set_preconditioner. */
+ * BIS_ERR_UNSUPPORTED here and in bis_mcg_set_preconditioner, bis_mbicgstab_set_preconditioner, bis_mgmres_set_preconditioner.
+ * BIS_PC_BLOCK_JACOBI has one: OUT = bis_bj_mapply(IN) of the handle whose operand is in L_strict (n rows, or BIS_ERR_INVALID);
+ * nothing else is read, OUT may alias IN, and the three lock-step set_preconditioner calls take it and allocate no TMP or WORK. */
 BIS_API bis_status bis_mapply_preconditioner(
     bis_ctx *ctx, int precond_type, int64_t n, int n_rhs, const bis_mat *L_strict,
     const bis_mat *U_strict, const double *A_D, const double *A_D_inv,
@@ -781,7 +841,9 @@ BIS_API bis_status bis_cg_destroy(bis_ctx *ctx, bis_cg *cg);
  * everything stays on the device as before.  Call before bis_cg_init.
  * BIS_PC_FSAI needs the two factors (G, Gt of bis_mat_fsai, of this rank's diagonal block on a distributed handle) and
  * nothing else: no diagonals, no work vector.  BIS_PC_MG needs the hierarchy's operand (bis_mg_operand, of the solver's
- * size) in L_strict and nothing else; on a distributed handle, or with outer_iters != 1: BIS_ERR_UNSUPPORTED. */
+ * size) in L_strict and nothing else; on a distributed handle, or with outer_iters != 1: BIS_ERR_UNSUPPORTED.
+ * BIS_PC_BLOCK_JACOBI: the same with the operand of a bis_bj handle (bis_bj_operand); no work vector is allocated, and a
+ * distributed handle refuses it (blocks may straddle ranks). */
 BIS_API bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                              const bis_mat *L_strict, const bis_mat *U_strict,
                                              const double *A_D, const double *A_D_inv,
@@ -1000,7 +1062,8 @@ BIS_API bis_status bis_mgmres_destroy(bis_ctx *ctx, bis_mgmres *m);
  * bis_apply_preconditioner takes -- the two-stage types, outer_iters > 1, and
  * BIS_PC_MG (the hierarchy's operand in L_strict) with any cycle -- and refuses what
  * that call refuses with its status: an MG operand of another size
- * BIS_ERR_INVALID, MG with outer_iters != 1 BIS_ERR_UNSUPPORTED. */
+ * BIS_ERR_INVALID, MG with outer_iters != 1 BIS_ERR_UNSUPPORTED.
+ * BIS_PC_BLOCK_JACOBI (the operand of a bis_bj handle in L_strict): as BIS_PC_MG. */
 typedef struct bis_fgmres bis_fgmres;
 BIS_API bis_status bis_fgmres_create(bis_ctx *ctx, const bis_mat *A, const double *b, double *x, int restart_len,
                                      bis_fgmres **out);
@@ -1078,7 +1141,8 @@ BIS_API bis_status bis_fgmres_destroy(bis_ctx *ctx, bis_fgmres *s);
  * queued behind the stop may still run; nothing reads their results).
  * bis_minres_set_preconditioner takes the arguments of bis_fgmres_set_preconditioner:
  * every type, outer_iters and inner_iters that bis_apply_preconditioner takes for one
- * vector, BIS_PC_MG (the hierarchy's operand in L_strict) included.  The library does
+ * vector, BIS_PC_MG (the hierarchy's operand in L_strict) and BIS_PC_BLOCK_JACOBI (the
+ * handle's operand there; create it with symmetrize = 1) included.  The library does
  * NOT check that M is symmetric positive definite.  GS and BGS alone, an ILU(0) of a
  * nonsymmetric factorisation, the two-stage types with few inner steps and the MG
  * K-cycles (BIS_MG_CYCLE_K, BIS_MG_CYCLE_K_GCR) are not such operators: MINRES with
