@@ -43,6 +43,7 @@ def load_library():
         _lib.bis_mat_spmm_kernel.restype = C.c_char_p
         _lib.bis_mat_sweepm_kernel.restype = C.c_char_p
         _lib.bis_mat_fsai_kernel.restype = C.c_char_p
+        _lib.bis_mat_iluk_kernel.restype = C.c_char_p
         _lib.bis_mg_operand.restype = C.c_void_p
         _lib.bis_mg_level_matrix.restype = C.c_void_p
         _lib.bis_bj_operand.restype = C.c_void_p
@@ -51,6 +52,14 @@ def load_library():
 
 def _i64(v):
     return C.c_int64(int(v))
+
+
+def iluk_limits():
+    """(max_level, max_visit) of Context.iluk (bis_iluk_limits): the largest level-of-fill, and the vertices the symbolic
+    search of one row may visit."""
+    ml, mv = C.c_int(), C.c_int()
+    load_library().bis_iluk_limits(C.byref(ml), C.byref(mv))
+    return ml.value, mv.value
 
 
 class Context:
@@ -245,6 +254,22 @@ class Context:
                                          C.byref(hl), C.byref(hu), C.c_void_p(L_D.ptr),
                                          C.c_void_p(U_D.ptr)))
         return Mat(self, hl), L_D, Mat(self, hu), U_D
+
+    def iluk(self, A, level, pivot_tol=1e-8, pivot_repl=1e-4):
+        """(Ls, L_D, Us, U_D, n_fill): ILU(level) with level-of-fill (bis_mat_iluk); level 0 is ilu0.  The factors go to
+        preconditioners "ilu0" / "ilu0it" like those of ilu0; n_fill counts the positions added to A's pattern."""
+        n = A.n_rows
+        L_D, U_D = self.alloc(n), self.alloc(n)
+        hl, hu, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self.check(self.lib.bis_mat_iluk(self.h, A.h, C.c_int(int(level)), C.c_double(pivot_tol), C.c_double(pivot_repl),
+                                         C.byref(hl), C.byref(hu), C.c_void_p(L_D.ptr), C.c_void_p(U_D.ptr), C.byref(nf)))
+        return Mat(self, hl), L_D, Mat(self, hu), U_D, nf.value
+
+    def iluk_symbolic(self, A, level):
+        """(P, n_fill): A padded with explicit +0.0 at the fill positions of level <= `level` (bis_mat_iluk_symbolic)."""
+        h, nf = C.c_void_p(), C.c_int64()
+        self.check(self.lib.bis_mat_iluk_symbolic(self.h, A.h, C.c_int(int(level)), C.byref(h), C.byref(nf)))
+        return Mat(self, h), nf.value
 
     def fsai(self, A):
         """(G, Gt, n_fallback): the factorized sparse approximate inverse of A on the pattern of tril(A), M^-1 = Gt G
@@ -543,6 +568,11 @@ class Mat:
     def ilu0_kernel(self):
         """Name of the elimination kernel that factorised this ILU(0) L factor (bis_mat_ilu0_kernel); "" for other matrices."""
         return self.ctx.lib.bis_mat_ilu0_kernel(self.h).decode()
+
+    def iluk_kernel(self):
+        """The symbolic search that made this ILU(k) pattern or L factor, e.g. "iluk_search_kernel RP=32 two searches"
+        (bis_mat_iluk_kernel); "" for other matrices."""
+        return self.ctx.lib.bis_mat_iluk_kernel(self.h).decode()
 
     def fsai_kernel(self):
         """The instance of fsai_rows_kernel that computed this FSAI factor G, e.g. "fsai_rows_kernel M=32 RP=32"

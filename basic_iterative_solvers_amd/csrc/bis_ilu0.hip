@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void sort_rows_wave_kernel(const RP *__restric
     }
 }
 
-template <typename RP>
+template <typename RP, bool FILL>
 __global__ __launch_bounds__(256) void ilu0_level_kernel(const RP *__restrict__ rp,
                                                          const int32_t *__restrict__ wcol, double *wval,
                                                          const int64_t *__restrict__ dpos,
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void ilu0_level_kernel(const RP *__restrict__ 
                 const int64_t mid = (lo + hi) >> 1;
                 if (wcol[mid] < j) lo = mid + 1; else hi = mid;
             }
-            if (lo < e && wcol[lo] == j && wval[lo] != 0.0) wval[lo] = fma(-factor, wval[q], wval[lo]);
+            if (lo < e && wcol[lo] == j && (FILL || wval[lo] != 0.0)) wval[lo] = fma(-factor, wval[q], wval[lo]);
         }
     }
     double u_diag = dpos[i] >= 0 ? wval[dpos[i]] : 0.0; // (dpos: the first copy)
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void ilu0_level_kernel(const RP *__restrict__ 
 // serial algorithm, so the factors are identical to the lane-per-row kernel's.
 constexpr int kIluMaxRow = 1024;
 
-template <typename RP>
+template <typename RP, bool FILL>
 __global__ __launch_bounds__(256) void ilu0_level_wave_kernel(const RP *__restrict__ rp,
                                                               const int32_t *__restrict__ wcol, double *wval,
                                                               const int64_t *__restrict__ dpos,
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void ilu0_level_wave_kernel(const RP *__restri
             }
             if (lo < len && lcol[lo] == j) {
                 const double w = lval[lo];
-                if (w != 0.0) lval[lo] = fma(-factor, u, w);
+                if (FILL || w != 0.0) lval[lo] = fma(-factor, u, w);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // updates visible to the next elimination
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void ilu0_level_wave_kernel(const RP *__restri
 // loads and reads the row with sc1 loads (MI355X_MICROARCH.md, hand-offs measured with sc1 loads in place of the acquire).  The
 // arithmetic is the level kernel's, entry for entry.
 constexpr unsigned kIluSpin = 1u << 21;
-template <typename RP>
+template <typename RP, bool FILL>
 __global__ __launch_bounds__(256, 4) void ilu0_persistent_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ wcol, double *wval,
                                                                  const int64_t *__restrict__ dpos, const int64_t *__restrict__ ustart,
                                                                  const int32_t *__restrict__ perm, int64_t n, double pivot_tol,
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256, 4) void ilu0_persistent_kernel(const RP *__res
                 }
                 if (lo < len && lcol[lo] == j) {
                     const double w = lval[lo];
-                    if (w != 0.0) lval[lo] = fma(-factor, u, w);
+                    if (FILL || w != 0.0) lval[lo] = fma(-factor, u, w);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // updates visible to the next elimination
@@ -345,7 +345,9 @@ __global__ __launch_bounds__(256) void dup_check_kernel(const RP *__restrict__ r
     if (dup) atomicOr(flag, 1);
 }
 
-template <typename RP>
+// FILL (bis_mat_iluk on a pattern padded with explicit zeros): the same elimination with the reference's "only where the
+// current value is non-zero" rule switched off -- an update applies to every position of the row's pattern.
+template <typename RP, bool FILL>
 bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot_repl, bis_mat **Ls_out,
                   bis_mat **Us_out, double *L_D, double *U_D) {
     const int64_t n = A->n_rows;
@@ -401,7 +403,7 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
         const int mr = std::max(W->max_row_nnz, 1);
         const size_t smem = (size_t)4 * mr * (sizeof(double) + sizeof(int32_t));
         int nb = 0;
-        hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ilu0_persistent_kernel<RP>, 256, smem);
+        hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ilu0_persistent_kernel<RP, FILL>, 256, smem);
         (void)hipGetLastError();
         int *flag = nullptr;
         if (oe == hipSuccess && nb > 0 && hipMalloc(&flag, sizeof(int) * (size_t)n) == hipSuccess) {
@@ -413,7 +415,7 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
             const int per_cu = std::min(nb, bis_opts().ilu0_wgs > 0 ? bis_opts().ilu0_wgs : 6);
             const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)ctx->n_cus * per_cu / share));
             hipMemsetAsync(flag, 0, sizeof(int) * (size_t)n, ctx->stream);
-            hipLaunchKernelGGL(ilu0_persistent_kernel<RP>, dim3((unsigned)grid), dim3(256), smem, ctx->stream, rp, W->col, W->val, dpos, ustart,
+            hipLaunchKernelGGL((ilu0_persistent_kernel<RP, FILL>), dim3((unsigned)grid), dim3(256), smem, ctx->stream, rp, W->col, W->val, dpos, ustart,
                                perm, n, pivot_tol, pivot_repl, U_D, L_D, mr, flag, ctx->fault_dev);
             hipError_t le = hipGetLastError();
             if (le == hipSuccess) le = hipStreamSynchronize(ctx->stream);
@@ -433,11 +435,11 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
             const int64_t lo = (*level_ptr)[l], hi = (*level_ptr)[l + 1];
             if (wave_ok) {
                 const int mr = std::max(W->max_row_nnz, 1);
-                hipLaunchKernelGGL(ilu0_level_wave_kernel<RP>, dim3((unsigned)((hi - lo + 3) / 4)), dim3(256),
+                hipLaunchKernelGGL((ilu0_level_wave_kernel<RP, FILL>), dim3((unsigned)((hi - lo + 3) / 4)), dim3(256),
                                    (size_t)4 * mr * (sizeof(double) + sizeof(int32_t)), ctx->stream, rp, W->col,
                                    W->val, dpos, ustart, perm, lo, hi, pivot_tol, pivot_repl, U_D, L_D, mr);
             } else
-            hipLaunchKernelGGL(ilu0_level_kernel<RP>, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0,
+            hipLaunchKernelGGL((ilu0_level_kernel<RP, FILL>), dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0,
                                ctx->stream, rp, W->col, W->val, dpos, ustart, perm, lo, hi, pivot_tol,
                                pivot_repl, U_D, L_D);
         }
@@ -486,6 +488,15 @@ bis_status bis_mat_sorted_copy(bis_ctx *ctx, const bis_mat *A, bis_mat **W_out, 
     return BIS_OK;
 }
 
+bis_status bis_mat_ilu0_impl(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot_repl, bis_mat **L_strict,
+                             bis_mat **U_strict, double *L_D, double *U_D, bool fill) {
+    if (fill)
+        return A->rp64 ? ilu0_t<int64_t, true>(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D)
+                       : ilu0_t<int32_t, true>(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D);
+    return A->rp64 ? ilu0_t<int64_t, false>(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D)
+                   : ilu0_t<int32_t, false>(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D);
+}
+
 extern "C" {
 
 const char *bis_mat_ilu0_kernel(const bis_mat *L_strict) { return L_strict ? L_strict->ilu0_kernel : ""; }
@@ -495,8 +506,7 @@ bis_status bis_mat_ilu0(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, A && L_strict && U_strict && L_D && U_D, "bis_mat_ilu0: bad arguments");
     BIS_REQUIRE(ctx, A->n_rows == A->n_cols, "bis_mat_ilu0: square matrix required");
-    return A->rp64 ? ilu0_t<int64_t>(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D)
-                   : ilu0_t<int32_t>(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D);
+    return bis_mat_ilu0_impl(ctx, A, pivot_tol, pivot_repl, L_strict, U_strict, L_D, U_D, false);
 }
 
 } // extern "C"

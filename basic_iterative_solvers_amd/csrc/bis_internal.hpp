@@ -227,6 +227,7 @@ struct bis_mat {
     const char *ilu0_kernel = "";           // the elimination kernel that made this ILU(0) L factor (bis_mat_ilu0_kernel)
     const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
     const char *spmm_kernel = "";           // the path and template instance the last bis_spmm on this matrix launched (bis_mat_spmm_kernel)
+    const char *iluk_kernel = "";           // the symbolic search that made this ILU(k) pattern or L factor, k >= 1 (bis_mat_iluk_kernel)
     const char *fsai_kernel = "";           // the instance of fsai_rows_kernel that computed this FSAI factor G (bis_mat_fsai_kernel)
     struct bis_mg *mg = nullptr;            // the hierarchy this matrix is the preconditioner operand of (bis_mg_operand): an n x n matrix without
                                             // entries that the hierarchy owns; bis_mat_destroy leaves it alone
@@ -443,6 +444,10 @@ bool bis_trsv_holds_plans(const bis_mat *A); // some direction holds a level, ti
 void bis_trsv_plan_adopt(bis_mat *to, bis_mat *from, bool backward);
 bis_status bis_mat_split_strict_impl(bis_ctx *ctx, const bis_mat *A, bis_mat **L_strict,
                                      bis_mat **U_strict, double *D, double *D_inv, bool check_diag);
+// bis_mat_ilu0 behind its argument checks; fill = true (bis_iluk.hip): an update applies to every position of a row's
+// pattern, whether its current value is zero or not
+bis_status bis_mat_ilu0_impl(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot_repl, bis_mat **L_strict,
+                             bis_mat **U_strict, double *L_D, double *U_D, bool fill);
 // W = A with ascending columns inside each row (bis_ilu0.hip's sort, stable for repeated columns; W is not finalized), and
 // per row the position of its first diagonal entry (-1: none) and of its first entry right of the diagonal.  The caller
 // destroys W and frees the two device arrays.

@@ -69,13 +69,17 @@ struct MGCycle { int cycle = BIS_MG_CYCLE_V, levels = 0; };
 inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
 // -bs N: rows per block of -p bj (bis_bj_params.block_size); 0: not given, the dof of the matrix' grid hint where that is above 1
 inline int &precond_block_size() { static int b = 0; return b; }
+// -fill K: level-of-fill of -p ilu0 / -p ilu0it (bis_mat_iluk); 0, the default, is ILU(0) as it always ran
+inline int &precond_fill_level() { static int k = 0; return k; }
 enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES }; // FGMRES, MINRES: this build's additions (-fgm, -mr)
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
                               "symmetric-gauss-seidel", "two-stage gauss-seidel",
                               "symmetric two-stage gauss-seidel", "incomplete LU(0)"};
-    if (t == PrecondType::ILU0Iter) return "incomplete LU(0), iterative solves (" + std::to_string(precond_inner_iters()) + ")";
+    if (t == PrecondType::ILU0Iter)
+        return "incomplete LU(" + std::to_string(precond_fill_level()) + "), iterative solves (" + std::to_string(precond_inner_iters()) + ")";
+    if (t == PrecondType::ILU0 && precond_fill_level() > 0) return "incomplete LU(" + std::to_string(precond_fill_level()) + ")";
     if (t == PrecondType::FSAI) return "factorized sparse approximate inverse";
     if (t == PrecondType::MG) return "aggregation multigrid";
     if (t == PrecondType::BlockJacobi) return "block jacobi";
@@ -94,6 +98,8 @@ struct Args {
     int restart_length = 10;
     int inner_iters = PRECOND_INNER_ITERS; // -inner K (precond_inner_iters())
     int pprec = 64;                        // -pprec 32|64 (precond_value_bits())
+    int fill_level = 0;                    // -fill K (precond_fill_level())
+    bool fill_given = false;
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

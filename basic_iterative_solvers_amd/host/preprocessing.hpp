@@ -81,12 +81,25 @@ inline void factor_LU(Solver *s) {
         // section 5, defect 2); this is its serial factor_ILU0_old arithmetic,
         // level-scheduled on the device.  Overwrites L_strict/U_strict, L_D, U_D.
         bis_mat *Ls = nullptr, *Us = nullptr;
+        const int fill = precond_fill_level(); // -fill K: ILU(K) with level-of-fill; its factors are applied like ILU(0)'s
+        int64_t n_fill = 0;
+        if (fill > 0) {
+            const bis_status st = bis_mat_iluk(bis::ctx(), s->A->dev, fill, ILU0_PIVOT_TOLERANCE, ILU0_PIVOT_REPLACEMENT, &Ls, &Us,
+                                               s->L_D, s->U_D, &n_fill);
+            if (st == BIS_ERR_NO_DIAG || st == BIS_ERR_UNSUPPORTED) { fprintf(stderr, "%s\n", bis_last_error(bis::ctx())); exit(EXIT_FAILURE); }
+            bis::check(st, "bis_mat_iluk");
+        } else
         bis::check(bis_mat_ilu0(bis::ctx(), s->A->dev, ILU0_PIVOT_TOLERANCE, ILU0_PIVOT_REPLACEMENT, &Ls, &Us,
                                 s->L_D, s->U_D), "bis_mat_ilu0");
         s->L_strict->free_host();
         s->U_strict->free_host();
         s->L_strict->adopt(Ls);
         s->U_strict->adopt(Us);
+        if (fill > 0) {
+            const int64_t entries = s->L_strict->nnz + s->U_strict->nnz + (int64_t)s->N;
+            std::cout << "ILU(" << fill << "): " << n_fill << " fill entries, L+U+D entries = " << entries << " ("
+                      << (s->A->nnz > 0 ? (double)entries / (double)s->A->nnz : 1.0) << " x A)" << std::endl;
+        }
         // -p ilu0it multiplies by the pivots' reciprocals: A_D_inv carries 1 / U_D for that type (L_D is the vector of ones)
         if (s->preconditioner == PrecondType::ILU0Iter) elemwise_div_vectors(s->A_D_inv, s->L_D, s->U_D, s->N);
         if (s->preconditioner == PrecondType::ILU0Iter) round_precond_factors(s); // (the diagonals L_D, U_D, 1 / U_D stay fp64)

@@ -100,6 +100,17 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             }
             precond_block_size() = bs;
         }
+        else if (arg == "-fill" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const int k = v.find_first_not_of("0123456789") == std::string::npos && v.size() <= 2 ? atoi(v.c_str()) : -1;
+            if (k < 0 || k > 16) {
+                fprintf(stderr, "ERROR: -fill K: the level-of-fill of -p ilu0 / -p ilu0it, 0 <= K <= 16\n");
+                exit(EXIT_FAILURE);
+            }
+            a->fill_level = k;
+            a->fill_given = true;
+            precond_fill_level() = k;
+        }
         else if (arg == "-mg" && i + 1 < argc) {
             bis_mg_params &p = precond_mg_params();
             std::stringstream ss(argv[++i]);
@@ -174,6 +185,10 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     }
     if (a->method == SolverType::FGMRES && (a->unfused || a->host_scalars)) {
         fprintf(stderr, "ERROR: -fgm is a device schedule (bis_fgmres_*) and has no call-by-call form: -unfused and -hostscalars do not apply\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->fill_given && a->preconditioner != PrecondType::ILU0 && a->preconditioner != PrecondType::ILU0Iter) {
+        fprintf(stderr, "ERROR: -fill K is the level-of-fill of an incomplete LU factorisation: it needs -p ilu0 or -p ilu0it\n");
         exit(EXIT_FAILURE);
     }
     // the other types run exact sweeps on the fp64 arrays and would gain nothing from rounded values

@@ -371,6 +371,38 @@ BIS_API bis_status bis_mat_ilu0(bis_ctx *ctx, const bis_mat *A, double pivot_tol
  * or "ilu0_level_kernel" (static string; "" for any other matrix). */
 BIS_API const char *bis_mat_ilu0_kernel(const bis_mat *L_strict);
 
+/* ILU(k) with level-of-fill (bis_iluk.hip); no reference counterpart.  A must be square with a stored diagonal entry in
+ * every row and no column repeated inside a row; 0 <= level <= 16.
+ * Levels: lev(i,j) = 0 where A stores (i,j), otherwise the minimum over p < min(i,j) of lev(i,p) + lev(p,j) + 1 (infinite
+ * without such a p).  Equivalently (Hysom & Pothen) lev(i,j) + 1 is the number of edges of the shortest path i -> j in the
+ * graph of A all of whose interior vertices are < min(i,j); the device finds it by one breadth-first search per row, on A
+ * for the upper and on A^T for the lower triangle (on A alone where the pattern is structurally symmetric).
+ * Symbolic: P holds exactly the positions with lev(i,j) <= level, columns ascending, A's value where A stores the
+ * position and +0.0 elsewhere; *n_fill (may be NULL) = nnz(P) - nnz(A).  P has 64-bit row pointers when A has them or its
+ * entry count needs them, and no grid hint for level >= 1 (a filled stencil is no stencil).  For level 0, P is A with
+ * sorted rows.
+ * Numeric: row-wise IKJ elimination on the pattern of P, pivots k < i of row i in ascending order; for each,
+ * skip if |u_kk| < 1e-16, else l_ik = w_ik / u_kk and w_ij = fma(-l_ik, u_kj, w_ij) for EVERY j > k that rows i and k of
+ * P share -- bis_mat_ilu0's arithmetic and kernels without its rule that a position whose current value is 0.0 is left
+ * alone; then |u_ii| < pivot_tol becomes sign(u_ii) * pivot_repl.  Outputs as bis_mat_ilu0: the strict factors with
+ * ascending columns, L_D = 1, U_D = diag(U); BIS_PC_ILU0 and BIS_PC_ILU0_ITER take them unchanged.  Without a grid hint
+ * the factors run the level-scheduled and chained sweeps.
+ * bis_mat_iluk with level == 0 IS bis_mat_ilu0 (same checks, bits, grid hint and kernel, the non-zero rule included);
+ * *n_fill = 0.
+ * BIS_ERR_INVALID: null arguments, A not square, a row-range view, level outside 0..16; BIS_ERR_NO_DIAG: a row without a
+ * stored diagonal entry; BIS_ERR_UNSUPPORTED: a column repeated inside a row, or a row whose search visits more than
+ * max_visit vertices (bis_iluk_limits; the message names the row -- nothing is truncated).  *P, *L_strict, *U_strict and
+ * *n_fill are written on success only.  n = 0: BIS_OK.  Blocking.  No floating-point value is accumulated with atomics
+ * and the pattern does not depend on the order in which the search claims vertices: two calls give the same bits.
+ * bis_mat_iluk_kernel: the symbolic instance that made P or L_strict, "iluk_search_kernel RP=32 two searches" or
+ * "... one search, transposed" (static string; "" for the factors of level 0 and for any other matrix); bis_mat_ilu0_kernel names the
+ * numeric kernel as for ILU(0).  bis_iluk_limits: max_level = 16, max_visit = 4096 (either may be NULL). */
+BIS_API bis_status bis_mat_iluk_symbolic(bis_ctx *ctx, const bis_mat *A, int level, bis_mat **P, int64_t *n_fill);
+BIS_API bis_status bis_mat_iluk(bis_ctx *ctx, const bis_mat *A, int level, double pivot_tol, double pivot_repl,
+                                bis_mat **L_strict, bis_mat **U_strict, double *L_D, double *U_D, int64_t *n_fill);
+BIS_API const char *bis_mat_iluk_kernel(const bis_mat *L_strict);
+BIS_API bis_status bis_iluk_limits(int *max_level, int *max_visit);
+
 /* Factorized sparse approximate inverse (FSAI, Kolotilina-Yeremin) on the pattern of tril(A); no reference counterpart.
  * Only the entries of A with column <= row are read; the result is the FSAI of the symmetric matrix they define.  For row
  * i let J be the columns <= i of row i in ascending order (the last one is i, |J| = m <= 64) and S = A[J,J], S[p,q]
