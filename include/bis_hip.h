@@ -845,6 +845,10 @@ BIS_API bis_status bis_stat_create(bis_ctx *ctx, int kind, const bis_mat *A,
                                    const bis_mat *L_strict, const bis_mat *U_strict,
                                    const double *D, const double *b, double *x,
                                    bis_stat **out);
+/* Reuse: bis_stat_init may be called again at any time, on a handle that is live, has stopped or holds NaN.  It reads b
+ * and x as they are at that call (x as the new x_0; Jacobi's iterate is in x again, whichever buffer held it), discards
+ * every earlier state -- iteration count, history, stop and converged flags -- and the solve that follows is, bit for
+ * bit, that of a new handle on the same operands.  There is no set_preconditioner: the kind is fixed at creation. */
 /* init_residual: ||b - A x_0|| (returned), stopping threshold tol * that. */
 BIS_API bis_status bis_stat_init(bis_ctx *ctx, bis_stat *s, double tol,
                                  double *r0_norm_host);
@@ -881,6 +885,11 @@ BIS_API bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int preco
                                              const double *A_D, const double *A_D_inv,
                                              const double *L_D, const double *U_D,
                                              int outer_iters, int inner_iters);
+/* Reuse: bis_cg_init may be called again at any time, on a handle that is live, has stopped or holds NaN.  It reads b
+ * and x as they are at that call, discards every earlier state -- r, z, p, the scalars, the iteration count, the
+ * history, the stop and converged flags -- and the solve that follows is, bit for bit, that of a new handle with the
+ * same operands and preconditioner.  The preconditioner stays as set: bis_cg_set_preconditioner after the first
+ * bis_cg_init (or bis_cg_iterate) is refused with BIS_ERR_INVALID, on a used handle as well. */
 /* init_residual (cg.hpp:100-118) + init_stopping_criteria (solver.hpp:173):
  * r0 = b - A x0, z0 = M^-1 r0, p0 = z0; returns ||r0||_2 (blocking). */
 BIS_API bis_status bis_cg_init(bis_ctx *ctx, bis_cg *cg, double tol,
@@ -926,6 +935,10 @@ BIS_API bis_status bis_mcg_set_preconditioner(bis_ctx *ctx, bis_mcg *m, int prec
                                               const double *A_D, const double *A_D_inv,
                                               const double *L_D, const double *U_D,
                                               int outer_iters, int inner_iters);
+/* Reuse: bis_mcg_init may be called again at any time, whatever the columns' states (live, stopped at different
+ * iterations, NaN).  It reads B and X as they are at that call and discards every earlier state of every column --
+ * the frozen bits, counts, histories and scalars included; the solve that follows is, bit for bit, that of a new
+ * handle.  bis_mcg_set_preconditioner stays refused (BIS_ERR_INVALID) once bis_mcg_init has run. */
 /* r0 = b - A x0, z0, p0 per column; r0_norms_host (n_rhs entries, may be NULL) receives ||r0_j||_2 (blocking) */
 BIS_API bis_status bis_mcg_init(bis_ctx *ctx, bis_mcg *m, double tol, double *r0_norms_host);
 BIS_API bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters); /* non-blocking */
@@ -966,6 +979,10 @@ BIS_API bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab 
                                                     const double *A_D, const double *A_D_inv,
                                                     const double *L_D, const double *U_D,
                                                     int outer_iters, int inner_iters);
+/* Reuse: as bis_mcg_init -- bis_mbicgstab_init may be called again at any time, reads B and X as they are then, and
+ * discards every earlier state of every column (frozen bits, a breakdown's NaN, counts, histories, scalars); the
+ * solve that follows is, bit for bit, that of a new handle.  bis_mbicgstab_set_preconditioner stays refused
+ * (BIS_ERR_INVALID) once bis_mbicgstab_init has run. */
 /* r0_norms_host (n_rhs entries, may be NULL) receives ||r0_j||_2 (blocking) */
 BIS_API bis_status bis_mbicgstab_init(bis_ctx *ctx, bis_mbicgstab *m, double tol, double *r0_norms_host);
 BIS_API bis_status bis_mbicgstab_iterate(bis_ctx *ctx, bis_mbicgstab *m, int n_iters); /* non-blocking */
@@ -1025,6 +1042,11 @@ BIS_API bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, in
                                                  const double *A_D, const double *A_D_inv,
                                                  const double *L_D, const double *U_D,
                                                  int outer_iters, int inner_iters);
+/* Reuse: bis_mgmres_init may be called again at any time, inside a cycle as well.  It reads B and X as they are at
+ * that call and discards every earlier state of every column: the cycle position starts at 0 again, the basis, the
+ * rotations, g, the pending combine, the frozen bits, counts and histories are dropped, NaN included;
+ * bis_mgmres_solution straight after it gives X.  The solve that follows is, bit for bit, that of a new handle.
+ * bis_mgmres_set_preconditioner stays refused (BIS_ERR_INVALID) once bis_mgmres_init has run. */
 /* r0_norms_host (n_rhs entries, may be NULL) receives the unpreconditioned ||r0_j||_2 (blocking) */
 BIS_API bis_status bis_mgmres_init(bis_ctx *ctx, bis_mgmres *m, double tol, double *r0_norms_host);
 /* non-blocking; the cycle position persists across calls (no call boundary restarts a cycle) */
@@ -1104,6 +1126,11 @@ BIS_API bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, in
                                                  const double *A_D, const double *A_D_inv,
                                                  const double *L_D, const double *U_D,
                                                  int outer_iters, int inner_iters);
+/* Reuse: bis_fgmres_init may be called again at any time, inside a cycle as well.  It reads b and x as they are at
+ * that call and discards every earlier state: the cycle position starts at 0 again, V, Z, the rotations, g, a pending
+ * combine, the count and the history are dropped, NaN included; bis_fgmres_solution straight after it gives x.  The
+ * solve that follows is, bit for bit, that of a new handle.  bis_fgmres_set_preconditioner stays refused
+ * (BIS_ERR_INVALID) once bis_fgmres_init has run. */
 /* r0_norm_host (may be NULL) receives ||b - A x0||_2 (blocking) */
 BIS_API bis_status bis_fgmres_init(bis_ctx *ctx, bis_fgmres *s, double tol, double *r0_norm_host);
 /* non-blocking; the cycle position persists across calls (no call boundary restarts a cycle) */
@@ -1190,6 +1217,11 @@ BIS_API bis_status bis_minres_set_preconditioner(bis_ctx *ctx, bis_minres *s, in
                                                  const double *A_D, const double *A_D_inv,
                                                  const double *L_D, const double *U_D,
                                                  int outer_iters, int inner_iters);
+/* Reuse: bis_minres_init may be called again at any time (after a failed bis_minres_iterate it must be).  It reads b
+ * and x as they are at that call and discards every earlier state: the buffer rotations of r1, r2, y and w1, w2, w
+ * start at iteration 1 again, w and w2 are zero, the scalars, the count, the history and the flags are dropped, NaN
+ * included.  The solve that follows is, bit for bit, that of a new handle.  bis_minres_set_preconditioner stays
+ * refused (BIS_ERR_INVALID) once bis_minres_init has run. */
 /* blocking; r0_norm_host (may be NULL) receives beta1 */
 BIS_API bis_status bis_minres_init(bis_ctx *ctx, bis_minres *s, double tol, double *r0_norm_host);
 /* non-blocking: enqueues n_iters iterations */
