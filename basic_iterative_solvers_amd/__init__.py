@@ -749,30 +749,48 @@ def _handle_pc(pc, Ls):
     return pc, Ls
 
 
-class CG:
+class _Solver:
+    """What the six solver handles share; a class names its library symbols bis_<_sym>_*."""
+
+    _sym = None
+
+    def _fn(self, what):
+        return getattr(self.ctx.lib, f"bis_{self._sym}_{what}")
+
+    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
+        """The preconditioner of the solve, before init: a PC name or number with the operands its type reads; an MG or a BJ
+        object stands for "mg" / "bj" with its operand as Ls."""
+        def p(v):
+            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
+        pc, Ls = _handle_pc(pc, Ls)
+        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
+        self.ctx.check(self._fn("set_preconditioner")(
+            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
+            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
+            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
+
+    def iterate(self, n):
+        self.ctx.check(self._fn("iterate")(self.ctx.h, self.h, C.c_int(int(n))))
+
+    def free(self):
+        if self.h:
+            self._fn("destroy")(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
+class CG(_Solver):
+    _sym = "cg"
+
     def __init__(self, ctx, A, b, x, A_D=None):
         self.ctx = ctx
         self.h = C.c_void_p()
         ctx.check(ctx.lib.bis_cg_create(ctx.h, A.h, C.c_void_p(A_D.ptr) if A_D else C.c_void_p(),
                                         C.c_void_p(b.ptr), C.c_void_p(x.ptr), C.byref(self.h)))
 
-    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
-        def p(v):
-            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        pc, Ls = _handle_pc(pc, Ls)
-        self._keep = (Ls, Us, A_D, A_D_inv, L_D, U_D)
-        self.ctx.check(self.ctx.lib.bis_cg_set_preconditioner(
-            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
-            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
-            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
-
     def init(self, tol):
         r0 = C.c_double()
         self.ctx.check(self.ctx.lib.bis_cg_init(self.ctx.h, self.h, C.c_double(tol), C.byref(r0)))
         return r0.value
-
-    def iterate(self, n):
-        self.ctx.check(self.ctx.lib.bis_cg_iterate(self.ctx.h, self.h, C.c_int(n)))
 
     def status(self, hist_cap=4096):
         iters, conv = C.c_int(), C.c_int()
@@ -781,14 +799,11 @@ class CG:
                                                   hist.ctypes, C.c_int(hist_cap)))
         return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
 
-    def free(self):
-        if self.h:
-            self.ctx.lib.bis_cg_destroy(self.ctx.h, self.h)
-            self.h = C.c_void_p()
 
-
-class MCG:
+class MCG(_Solver):
     """k CG solves in lock-step on one matrix stream (bis_mcg_*): B, X are n x k interleaved device blocks."""
+
+    _sym = "mcg"
 
     def __init__(self, ctx, A, B, X, k, A_D=None):
         self.ctx, self.k = ctx, int(k)
@@ -797,23 +812,10 @@ class MCG:
         ctx.check(ctx.lib.bis_mcg_create(ctx.h, A.h, C.c_void_p(A_D.ptr) if A_D else C.c_void_p(),
                                          C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k), C.byref(self.h)))
 
-    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
-        def p(v):
-            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        pc, Ls = _handle_pc(pc, Ls)
-        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
-        self.ctx.check(self.ctx.lib.bis_mcg_set_preconditioner(
-            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
-            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
-            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
-
     def init(self, tol):
         r0 = np.zeros(self.k)
         self.ctx.check(self.ctx.lib.bis_mcg_init(self.ctx.h, self.h, C.c_double(tol), r0.ctypes))
         return r0
-
-    def iterate(self, n):
-        self.ctx.check(self.ctx.lib.bis_mcg_iterate(self.ctx.h, self.h, C.c_int(int(n))))
 
     def status(self, j, hist_cap=4096):
         iters, conv = C.c_int(), C.c_int()
@@ -822,15 +824,12 @@ class MCG:
                                                    hist.ctypes, C.c_int(hist_cap)))
         return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
 
-    def free(self):
-        if self.h:
-            self.ctx.lib.bis_mcg_destroy(self.ctx.h, self.h)
-            self.h = C.c_void_p()
 
-
-class MBiCGSTAB:
+class MBiCGSTAB(_Solver):
     """k BiCGSTAB solves in lock-step (bis_mbicgstab_*): B, X are n x k interleaved device blocks; two SpMMs and two
     preconditioner applies per iteration for all columns."""
+
+    _sym = "mbicgstab"
 
     def __init__(self, ctx, A, B, X, k):
         self.ctx, self.k = ctx, int(k)
@@ -838,23 +837,10 @@ class MBiCGSTAB:
         self._keep = (A, B, X)
         ctx.check(ctx.lib.bis_mbicgstab_create(ctx.h, A.h, C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k), C.byref(self.h)))
 
-    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
-        def p(v):
-            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        pc, Ls = _handle_pc(pc, Ls)
-        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
-        self.ctx.check(self.ctx.lib.bis_mbicgstab_set_preconditioner(
-            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
-            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
-            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
-
     def init(self, tol):
         r0 = np.zeros(self.k)
         self.ctx.check(self.ctx.lib.bis_mbicgstab_init(self.ctx.h, self.h, C.c_double(tol), r0.ctypes))
         return r0
-
-    def iterate(self, n):
-        self.ctx.check(self.ctx.lib.bis_mbicgstab_iterate(self.ctx.h, self.h, C.c_int(int(n))))
 
     def status(self, j, hist_cap=4096):
         iters, conv = C.c_int(), C.c_int()
@@ -863,16 +849,13 @@ class MBiCGSTAB:
                                                          hist.ctypes, C.c_int(hist_cap)))
         return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
 
-    def free(self):
-        if self.h:
-            self.ctx.lib.bis_mbicgstab_destroy(self.ctx.h, self.h)
-            self.h = C.c_void_p()
 
-
-class MGMRES:
+class MGMRES(_Solver):
     """k restarted GMRES(restart) solves in lock-step (bis_mgmres_*): B, X are n x k interleaved device blocks; one SpMM and one
     preconditioner apply per iteration for all columns, the Gram-Schmidt coefficients and the Givens algebra stay on the
     device.  X of a live column is x_old of its cycle: `solution` gives the explicit iterate."""
+
+    _sym = "mgmres"
 
     def __init__(self, ctx, A, B, X, k, restart=10):
         self.ctx, self.k, self.restart = ctx, int(k), int(restart)
@@ -881,23 +864,10 @@ class MGMRES:
         ctx.check(ctx.lib.bis_mgmres_create(ctx.h, A.h, C.c_void_p(B.ptr), C.c_void_p(X.ptr), C.c_int(self.k),
                                             C.c_int(self.restart), C.byref(self.h)))
 
-    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
-        def p(v):
-            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        pc, Ls = _handle_pc(pc, Ls)
-        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
-        self.ctx.check(self.ctx.lib.bis_mgmres_set_preconditioner(
-            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
-            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
-            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
-
     def init(self, tol):
         r0 = np.zeros(self.k)
         self.ctx.check(self.ctx.lib.bis_mgmres_init(self.ctx.h, self.h, C.c_double(tol), r0.ctypes))
         return r0
-
-    def iterate(self, n):
-        self.ctx.check(self.ctx.lib.bis_mgmres_iterate(self.ctx.h, self.h, C.c_int(int(n))))
 
     def status(self, j, hist_cap=4096):
         """(iterations, converged, history): the history has iterations + 1 + restarts entries (n_hist of bis_mgmres_status)."""
@@ -911,16 +881,13 @@ class MGMRES:
         """The explicit x of every column into the n x k block `out` (bis_mgmres_solution); the solve does not change."""
         self.ctx.check(self.ctx.lib.bis_mgmres_solution(self.ctx.h, self.h, C.c_void_p(out.ptr)))
 
-    def free(self):
-        if self.h:
-            self.ctx.lib.bis_mgmres_destroy(self.ctx.h, self.h)
-            self.h = C.c_void_p()
 
-
-class FGMRES:
+class FGMRES(_Solver):
     """Restarted flexible GMRES(restart) on one right-hand side as a device schedule (bis_fgmres_*): the preconditioner stands
     on the right and may change from step to step (an MG K-cycle), the history is the true residual's.  x changes only at a
     restart or a stop: `solution` gives the explicit iterate."""
+
+    _sym = "fgmres"
 
     def __init__(self, ctx, A, b, x, restart=10):
         self.ctx, self.restart = ctx, int(restart)
@@ -929,24 +896,10 @@ class FGMRES:
         ctx.check(ctx.lib.bis_fgmres_create(ctx.h, A.h, C.c_void_p(b.ptr), C.c_void_p(x.ptr), C.c_int(self.restart),
                                             C.byref(self.h)))
 
-    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
-        """MGMRES.set_preconditioner's keywords, every type; an MG object stands for "mg" with its operand as Ls."""
-        def p(v):
-            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        pc, Ls = _handle_pc(pc, Ls)
-        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
-        self.ctx.check(self.ctx.lib.bis_fgmres_set_preconditioner(
-            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
-            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
-            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
-
     def init(self, tol):
         r0 = C.c_double()
         self.ctx.check(self.ctx.lib.bis_fgmres_init(self.ctx.h, self.h, C.c_double(tol), C.byref(r0)))
         return r0.value
-
-    def iterate(self, n):
-        self.ctx.check(self.ctx.lib.bis_fgmres_iterate(self.ctx.h, self.h, C.c_int(int(n))))
 
     def status(self, hist_cap=4096):
         """(iterations, converged, history): the history has iterations + 1 + restarts entries (n_hist of bis_fgmres_status)."""
@@ -960,16 +913,13 @@ class FGMRES:
         """The explicit iterate into the n-vector `out` (bis_fgmres_solution); the solve does not change."""
         self.ctx.check(self.ctx.lib.bis_fgmres_solution(self.ctx.h, self.h, C.c_void_p(out.ptr)))
 
-    def free(self):
-        if self.h:
-            self.ctx.lib.bis_fgmres_destroy(self.ctx.h, self.h)
-            self.h = C.c_void_p()
 
-
-class MINRES:
+class MINRES(_Solver):
     """Preconditioned MINRES on one right-hand side as a device schedule (bis_minres_*): symmetric A, definite or not, and
     one fixed symmetric positive definite preconditioner (not checked).  The history is phibar: the residual norm in the
     M^-1 norm, the 2-norm without a preconditioner; it never increases.  x is the iterate of the last history entry."""
+
+    _sym = "minres"
 
     def __init__(self, ctx, A, b, x):
         self.ctx = ctx
@@ -977,24 +927,10 @@ class MINRES:
         self._keep = (A, b, x)
         ctx.check(ctx.lib.bis_minres_create(ctx.h, A.h, C.c_void_p(b.ptr), C.c_void_p(x.ptr), C.byref(self.h)))
 
-    def set_preconditioner(self, pc, Ls=None, Us=None, A_D=None, A_D_inv=None, L_D=None, U_D=None, outer=1, inner=0):
-        """CG.set_preconditioner's keywords, every type; an MG object stands for "mg" with its operand as Ls."""
-        def p(v):
-            return C.c_void_p(v.ptr) if v is not None else C.c_void_p()
-        pc, Ls = _handle_pc(pc, Ls)
-        self._keep_pc = (Ls, Us, A_D, A_D_inv, L_D, U_D)
-        self.ctx.check(self.ctx.lib.bis_minres_set_preconditioner(
-            self.ctx.h, self.h, C.c_int(PC[pc] if isinstance(pc, str) else pc),
-            Ls.h if Ls is not None else C.c_void_p(), Us.h if Us is not None else C.c_void_p(),
-            p(A_D), p(A_D_inv), p(L_D), p(U_D), C.c_int(outer), C.c_int(inner)))
-
     def init(self, tol):
         r0 = C.c_double()
         self.ctx.check(self.ctx.lib.bis_minres_init(self.ctx.h, self.h, C.c_double(tol), C.byref(r0)))
         return r0.value
-
-    def iterate(self, n):
-        self.ctx.check(self.ctx.lib.bis_minres_iterate(self.ctx.h, self.h, C.c_int(int(n))))
 
     def status(self, hist_cap=4096):
         """(iterations, converged, history[0 .. iterations])"""
@@ -1003,11 +939,6 @@ class MINRES:
         self.ctx.check(self.ctx.lib.bis_minres_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv),
                                                       hist.ctypes, C.c_int(hist_cap)))
         return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
-
-    def free(self):
-        if self.h:
-            self.ctx.lib.bis_minres_destroy(self.ctx.h, self.h)
-            self.h = C.c_void_p()
 
 
 # ---- multi-GPU (1-D row partition) -------------------------------------------

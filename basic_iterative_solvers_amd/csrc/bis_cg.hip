@@ -19,7 +19,7 @@
 // host only enqueues iterations and reads the status when it wants to.  Once
 // the stop test fires, the remaining enqueued passes are no-ops, so the result
 // is exactly the state at the reference's stopping iteration.
-#include "bis_internal.hpp"
+#include "bis_pc.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -49,12 +49,7 @@ struct bis_cg {
     int enqueued = 0;
     bool initialised = false; // bis_cg_init has run: p0 and (r,z) were made with the preconditioner set at that time
     unsigned *counters = nullptr; // device: arrival tickets of the last-arriver reductions ([0] pap, [1] pass B, [4...] pass B's per-group counters)
-    // general preconditioner (bis_cg_set_preconditioner): z = M^-1 r through bis_apply_preconditioner
-    int pc = -1;
-    const bis_mat *pcL = nullptr, *pcU = nullptr;
-    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
-    double *pc_work = nullptr;
-    int pc_outer = 1, pc_inner = 0;
+    bis_pc_binding pc; // general preconditioner (bis_cg_set_preconditioner), once set: z = M^-1 r through bis_pc_apply; its tmp is the handle's
 };
 
 namespace {
@@ -262,10 +257,10 @@ static bis_status cg_create_common(bis_ctx *ctx, bis_dist *dist, const bis_mat *
     if (st == BIS_OK) st = bis_vec_alloc(ctx, S_COUNT, &cg->sc);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, kPapBlocks, &cg->pap_stage);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, cg->hist_cap, &cg->hist);
-    if (st == BIS_OK && hipMalloc(&cg->flags, sizeof(int) * 4) != hipSuccess) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&cg->counters, sizeof(unsigned) * (4 + kArriveSubs)) != hipSuccess ||
-                         hipMemsetAsync(cg->counters, 0, sizeof(unsigned) * (4 + kArriveSubs), ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &cg->flags, 4);
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &cg->counters, 4 + kArriveSubs);
     if (st != BIS_OK) { bis_cg_destroy(ctx, cg); return st; }
+    cg->pc.tmp = cg->tmp; // lent: the binding owns only its work vector
     if (!A_D) cg->z = cg->r; // z aliases r without a preconditioner
     *out = cg;
     return BIS_OK;
@@ -290,38 +285,10 @@ bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                      const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D,
                                      int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, cg && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_BLOCK_JACOBI && outer_iters >= 1 && inner_iters >= 0,
-                "bis_cg_set_preconditioner: bad arguments");
-    BIS_REQUIRE(ctx, !cg->initialised && cg->enqueued == 0, "bis_cg_set_preconditioner: call it before bis_cg_init / bis_cg_iterate");
-    BIS_REQUIRE(ctx, precond_type != BIS_PC_FSAI || (L_strict && U_strict && L_strict->n_rows == cg->n && U_strict->n_rows == cg->n),
-                "bis_cg_set_preconditioner: FSAI needs both factors, of the solver's size");
-    if (precond_type == BIS_PC_MG) {
-        BIS_REQUIRE(ctx, L_strict && L_strict->mg && L_strict->n_rows == cg->n,
-                    "bis_cg_set_preconditioner: MG needs the operand of a hierarchy of the solver's size in L_strict");
-        if (cg->dist || outer_iters != 1) {
-            ctx->err = "bis_cg_set_preconditioner: MG on a distributed handle, or with outer_iters != 1, is not built";
-            return BIS_ERR_UNSUPPORTED;
-        }
-    }
-    if (precond_type == BIS_PC_BLOCK_JACOBI) {
-        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == cg->n,
-                    "bis_cg_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
-        if (cg->dist || outer_iters != 1) {
-            ctx->err = "bis_cg_set_preconditioner: block Jacobi on a distributed handle, or with outer_iters != 1, is not built";
-            return BIS_ERR_UNSUPPORTED;
-        }
-    }
-    if (cg->z == cg->r) { // z aliased r (no preconditioner at creation): it needs its own storage now
-        cg->z = nullptr;
-        bis_status st = bis_vec_alloc(ctx, cg->n, &cg->z);
-        if (st != BIS_OK) { cg->z = cg->r; return st; }
-    }
-    if (!cg->pc_work && precond_type != BIS_PC_FSAI && precond_type != BIS_PC_MG && precond_type != BIS_PC_BLOCK_JACOBI) { bis_status st = bis_vec_alloc(ctx, cg->n, &cg->pc_work); if (st != BIS_OK) return st; }
-    cg->pc = precond_type;
-    cg->pcL = L_strict; cg->pcU = U_strict;
-    cg->pcAD = A_D; cg->pcADinv = A_D_inv; cg->pcLD = L_D; cg->pcUD = U_D;
-    cg->pc_outer = outer_iters; cg->pc_inner = inner_iters;
-    return BIS_OK;
+    if (!cg) return bis_pc_no_handle(ctx, "bis_cg", 0, precond_type);
+    return bis_pc_bind(ctx, &cg->pc, {"bis_cg", cg->n, cg->n, 0, cg->initialised || cg->enqueued != 0, cg->dist ? 2 : 1},
+                       {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
+                       {{&cg->z, cg->n, cg->z == cg->r}}); // z aliased r (no preconditioner at creation): it needs its own storage now
 }
 
 bis_status bis_cg_destroy(bis_ctx *ctx, bis_cg *cg) {
@@ -337,7 +304,7 @@ bis_status bis_cg_destroy(bis_ctx *ctx, bis_cg *cg) {
     hipFree(cg->hist);
     hipFree(cg->flags);
     hipFree(cg->counters);
-    hipFree(cg->pc_work);
+    bis_pc_release(cg->pc);
     delete cg;
     return BIS_OK;
 }
@@ -356,9 +323,7 @@ bis_status bis_cg_init(bis_ctx *ctx, bis_cg *cg, double tol, double *r0_norm_hos
     } else {
         st = bis_compute_residual(ctx, cg->A, cg->x, cg->b, cg->r, cg->tmp);
     }
-    if (st == BIS_OK && cg->pc >= 0)
-        st = bis_apply_preconditioner(ctx, cg->pc, n, cg->pcL, cg->pcU, cg->pcAD, cg->pcADinv, cg->pcLD, cg->pcUD, cg->z, cg->r, cg->tmp,
-                                      cg->pc_work, cg->pc_outer, cg->pc_inner);
+    if (st == BIS_OK && cg->pc.set) st = bis_pc_apply(ctx, cg->pc, n, 0, cg->z, cg->r);
     else if (st == BIS_OK && cg->A_D) st = bis_elemwise_div_vectors(ctx, cg->z, cg->r, cg->A_D, n, 1.0);
     if (st == BIS_OK) st = bis_copy_vector(ctx, cg->p, cg->z, n);
     if (cg->dist) {
@@ -404,13 +369,12 @@ static bis_status cg_enqueue_iteration(bis_ctx *ctx, bis_cg *cg, int g, int it) 
     hipLaunchKernelGGL((cg_update_kernel<J, D>), dim3(g), dim3(kT), 0, ctx->stream, n, cg->sc, cg->flags,    \
                        cg->tmp, cg->A_D, cg->r, cg->z, ctx->partials, (size_t)kMaxReduceBlocks,              \
                        cg->counters + 1, cg->hist, cg->hist_cap, bis_opts().cg_nt_x != 0 && bis_opts().cg_nt_x != 2, bis_opts().cg_nt_x == 3)
-    if (cg->pc >= 0) BIS_CG_UPDATE(false, true); // r update and (r,r) only; z and (r,z) follow below
+    if (cg->pc.set) BIS_CG_UPDATE(false, true); // r update and (r,r) only; z and (r,z) follow below
     else if (cg->dist) { if (cg->A_D) BIS_CG_UPDATE(true, true); else BIS_CG_UPDATE(false, true); }
     else { if (cg->A_D) BIS_CG_UPDATE(true, false); else BIS_CG_UPDATE(false, false); }
 #undef BIS_CG_UPDATE
-    if (cg->pc >= 0) { // general preconditioner: z = M^-1 r (triangular sweeps ...), then (r,z) with the stream-ordered dot
-        st = bis_apply_preconditioner(ctx, cg->pc, n, cg->pcL, cg->pcU, cg->pcAD, cg->pcADinv, cg->pcLD, cg->pcUD, cg->z, cg->r, cg->tmp,
-                                      cg->pc_work, cg->pc_outer, cg->pc_inner);
+    if (cg->pc.set) { // general preconditioner: z = M^-1 r (triangular sweeps ...), then (r,z) with the stream-ordered dot
+        st = bis_pc_apply(ctx, cg->pc, n, 0, cg->z, cg->r);
         if (st == BIS_OK) st = bis_dot_dev(ctx, cg->r, cg->z, n, cg->sc + S_RZ_NEW);
         if (st != BIS_OK) return st;
         if (!cg->dist)

@@ -30,7 +30,7 @@
 // Elementwise and reduction traffic at position n, per row: pass 0 reads W, V_0 (16 B), each of the n middle passes reads W,
 // V_{i-1}, V_i and writes W (32 B), the last reads W, V_n and writes W (24 B), the scale reads W and writes V_{n+1} (16 B):
 // 56 + 32 n bytes, as bis_mgmres_* per column.
-#include "bis_internal.hpp"
+#include "bis_pc.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -52,11 +52,7 @@ struct bis_fgmres {
     int enqueued = 0;
     unsigned *counters = nullptr; // last-arriver counter sets: Gram-Schmidt passes, residual pass, combine
     bool initialised = false;
-    int pc = BIS_PC_NONE;
-    const bis_mat *pcL = nullptr, *pcU = nullptr;
-    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
-    double *pc_tmp = nullptr, *pc_work = nullptr;
-    int pc_outer = 1, pc_inner = 0;
+    bis_pc_binding pc;
 };
 
 namespace {
@@ -345,10 +341,8 @@ bis_status bis_fgmres_create(bis_ctx *ctx, const bis_mat *A, const double *b, do
     if (st == BIS_OK) st = bis_vec_alloc(ctx, s->ld, &s->W);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, L.size(), &s->st);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, s->hist_cap, &s->hist);
-    if (st == BIS_OK && (hipMalloc(&s->flags, sizeof(int) * F_COUNT) != hipSuccess ||
-                         hipMemsetAsync(s->flags, 0, sizeof(int) * F_COUNT, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&s->counters, sizeof(unsigned) * 3 * kCounterSet) != hipSuccess ||
-                         hipMemsetAsync(s->counters, 0, sizeof(unsigned) * 3 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->flags, F_COUNT);
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->counters, 3 * kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) { bis_fgmres_destroy(ctx, s); return st; }
     *out = s;
@@ -359,61 +353,18 @@ bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, int precon
                                          const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, s && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_BLOCK_JACOBI && outer_iters >= 1 && inner_iters >= 0,
-                "bis_fgmres_set_preconditioner: bad arguments");
-    BIS_REQUIRE(ctx, !s->initialised && s->enqueued == 0,
-                "bis_fgmres_set_preconditioner: call it before bis_fgmres_init / bis_fgmres_iterate");
-    const int pc = precond_type;
-    if (pc == BIS_PC_MG) { // bis_apply_preconditioner's checks, in its order
-        BIS_REQUIRE(ctx, L_strict && L_strict->mg && L_strict->n_rows == s->n,
-                    "bis_fgmres_set_preconditioner: MG needs the operand of a hierarchy of the solver's size in L_strict");
-        if (outer_iters != 1) { ctx->err = "bis_fgmres_set_preconditioner: MG with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
-    }
-    if (pc == BIS_PC_BLOCK_JACOBI) {
-        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == s->n,
-                    "bis_fgmres_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
-        if (outer_iters != 1) { ctx->err = "bis_fgmres_set_preconditioner: block Jacobi with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
-    }
-    // the operands the type reads (bis_apply_preconditioner would refuse them only inside bis_fgmres_iterate)
-    const bool two = pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
-    const bool ilu = pc == BIS_PC_ILU0 || pc == BIS_PC_ILU0_ITER;
-    const bool lower = pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || two || ilu || pc == BIS_PC_FSAI;
-    const bool upper = pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS || ilu || pc == BIS_PC_FSAI;
-    const bool need_AD = pc == BIS_PC_JACOBI || pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL ||
-                         pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
-    const bool need_ADinv = two || pc == BIS_PC_ILU0_ITER;
-    if (pc != BIS_PC_MG && pc != BIS_PC_BLOCK_JACOBI) {
-        BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_fgmres_set_preconditioner: the type needs a triangle that is null");
-        BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == s->n) && (!upper || U_strict->n_rows == s->n),
-                    "bis_fgmres_set_preconditioner: a triangle of another size");
-        BIS_REQUIRE(ctx, s->n == 0 || ((!need_AD || A_D) && (!need_ADinv || A_D_inv) && (!ilu || L_D) && (pc != BIS_PC_ILU0 || U_D)),
-                    "bis_fgmres_set_preconditioner: the type needs a diagonal that is null");
-    }
-    // every allocation first: a failure leaves the handle as it was
-    const bool need_tmp = pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || two || ilu || pc == BIS_PC_FSAI;
-    const bool need_work = two || pc == BIS_PC_ILU0_ITER;
-    double *Z = nullptr, *tmp = nullptr, *work = nullptr;
-    bis_status st = BIS_OK;
-    if (pc != BIS_PC_NONE && !s->Z) st = bis_vec_alloc(ctx, s->ld * s->m, &Z);
-    if (st == BIS_OK && need_tmp && !s->pc_tmp) st = bis_vec_alloc(ctx, s->ld, &tmp);
-    if (st == BIS_OK && need_work && !s->pc_work) st = bis_vec_alloc(ctx, s->ld, &work);
-    if (st != BIS_OK) { hipFree(Z); hipFree(tmp); hipFree(work); return st; }
-    if (Z) s->Z = Z;
-    if (tmp) s->pc_tmp = tmp;
-    if (work) s->pc_work = work;
-    s->pc = pc;
-    s->pcL = L_strict; s->pcU = U_strict;
-    s->pcAD = A_D; s->pcADinv = A_D_inv; s->pcLD = L_D; s->pcUD = U_D;
-    s->pc_outer = outer_iters; s->pc_inner = inner_iters;
-    return BIS_OK;
+    if (!s) return bis_pc_no_handle(ctx, "bis_fgmres", 0, precond_type);
+    return bis_pc_bind(ctx, &s->pc, {"bis_fgmres", s->n, s->ld, 0, s->initialised || s->enqueued != 0, 0},
+                       {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
+                       {{&s->Z, s->ld * s->m, precond_type != BIS_PC_NONE && !s->Z}});
 }
 
 bis_status bis_fgmres_destroy(bis_ctx *ctx, bis_fgmres *s) {
     BIS_CTX_OK(ctx);
     if (!s) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *v : {s->V, s->Z, s->W, s->st, s->hist, s->pc_tmp, s->pc_work}) hipFree(v);
+    for (double *v : {s->V, s->Z, s->W, s->st, s->hist}) hipFree(v);
+    bis_pc_release(s->pc);
     hipFree(s->flags);
     hipFree(s->counters);
     delete s;
@@ -466,7 +417,7 @@ bis_status bis_fgmres_iterate(bis_ctx *ctx, bis_fgmres *s, int n_iters) {
     BIS_REQUIRE(ctx, s->initialised, "bis_fgmres_iterate: call bis_fgmres_init first");
     const int g = fgm_grid(n, kMaxDotBlocks), g_wide = fgm_grid(n, kMaxEwBlocks);
     const fgm_layout L{len};
-    const bool pc = s->pc != BIS_PC_NONE;
+    const bool pc = s->pc.type != BIS_PC_NONE;
     bis_status st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) return st;
     ctx->spmv_stop = s->flags; // the SpMV returns at once when the solve has stopped
@@ -484,13 +435,11 @@ bis_status bis_fgmres_iterate(bis_ctx *ctx, bis_fgmres *s, int n_iters) {
         if (pc) { // Z_n = M^-1 V_n; V_n must survive: outer_iters > 1 writes its input (and puts it back), so it gets a copy
             Zn = s->Z + pos * ld;
             double *in = Vn;
-            if (s->pc_outer > 1) {
+            if (s->pc.outer > 1) {
                 st = bis_copy_vector(ctx, s->W, Vn, n);
                 in = s->W;
             }
-            if (st == BIS_OK)
-                st = bis_apply_preconditioner(ctx, s->pc, n, s->pcL, s->pcU, s->pcAD, s->pcADinv, s->pcLD, s->pcUD, Zn, in, s->pc_tmp,
-                                              s->pc_work, s->pc_outer, s->pc_inner);
+            if (st == BIS_OK) st = bis_pc_apply(ctx, s->pc, n, 0, Zn, in);
         }
         if (st == BIS_OK) st = bis_spmv_launch(ctx, s->A, Zn, s->W, nullptr, nullptr);
         if (st != BIS_OK) { s->enqueued += done; return st; }
@@ -526,7 +475,7 @@ bis_status bis_fgmres_solution(bis_ctx *ctx, bis_fgmres *s, double *x_out) {
     const fgm_layout L{s->m};
     hipLaunchKernelGGL(fgm_ysol_kernel, dim3(1), dim3(64), 0, ctx->stream, L, s->st, (const int *)s->flags);
     hipLaunchKernelGGL((fgm_combine_kernel<true>), dim3(fgm_grid(s->n, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, s->n, s->ld, L,
-                       (const double *)s->st, s->flags, (const double *)(s->pc != BIS_PC_NONE ? s->Z : s->V), (const double *)s->x,
+                       (const double *)s->st, s->flags, (const double *)(s->pc.type != BIS_PC_NONE ? s->Z : s->V), (const double *)s->x,
                        x_out, (unsigned *)nullptr);
     BIS_HIP_CHECK(ctx, hipGetLastError());
     BIS_SYNC_CHECK(ctx);

@@ -264,6 +264,13 @@ bis_status bis_fault_check(bis_ctx *ctx);
         if (!(ctx)) return BIS_ERR_NO_DEVICE;                                  \
     } while (0)
 
+// `count` device words, zeroed on the stream: a handle's flags and arrival counters
+template <class T>
+inline bis_status bis_alloc_zeroed(bis_ctx *ctx, T **out, size_t count) {
+    const size_t bytes = sizeof(T) * count;
+    return hipMalloc(out, bytes) == hipSuccess && hipMemsetAsync(*out, 0, bytes, ctx->stream) == hipSuccess ? BIS_OK : BIS_ERR_HIP;
+}
+
 // ---- device helpers ---------------------------------------------------------
 // wave64 sum via DPP-free shuffles (ds_bpermute under the hood for doubles).
 __device__ __forceinline__ double wave_sum(double v) {

@@ -23,6 +23,7 @@
 // breakdown (rho, d1 or d3 reaching 0) gives a non-finite norm, which the divergence test turns into "stopped, not
 // converged" for that column alone.  No kernel here waits for another workgroup: there is the arrive ticket and nothing else.
 #include "bis_lockstep.hpp"
+#include "bis_pc.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -43,11 +44,7 @@ struct bis_mbicgstab {
     int enqueued = 0;
     unsigned *counters = nullptr; // one last-arriver counter set per reduction: passes 1, 3, 4
     bool initialised = false;
-    int pc = BIS_PC_NONE;
-    const bis_mat *pcL = nullptr, *pcU = nullptr;
-    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
-    double *pc_tmp = nullptr, *pc_work = nullptr; // n x k blocks of the apply's scratch, where the type needs them
-    int pc_inner = 0;
+    bis_pc_binding pc; // its scratch: n x k blocks
 };
 
 namespace {
@@ -234,12 +231,6 @@ __global__ __launch_bounds__(kT) void mbi_p_kernel(int64_t n, int k, const doubl
     }
 }
 
-// OUT = M^-1 IN with the preconditioner of bis_mbicgstab_set_preconditioner (never called for BIS_PC_NONE)
-inline bis_status mbi_apply_pc(bis_ctx *ctx, bis_mbicgstab *m, double *out, double *in) {
-    return bis_mapply_preconditioner(ctx, m->pc, m->n, m->k, m->pcL, m->pcU, m->pcAD, m->pcADinv, m->pcLD, m->pcUD, out, in,
-                                     m->pc_tmp, m->pc_work, 1, m->pc_inner);
-}
-
 constexpr size_t kPartials = (size_t)2 * kMaxK * kMaxReduceBlocks;
 
 } // namespace
@@ -263,10 +254,8 @@ bis_status bis_mbicgstab_create(bis_ctx *ctx, const bis_mat *A, const double *B,
         if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, v);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)B_COUNT * n_rhs, &m->sc);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
-    if (st == BIS_OK && (hipMalloc(&m->flags, sizeof(int) * n_flags) != hipSuccess ||
-                         hipMemsetAsync(m->flags, 0, sizeof(int) * n_flags, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&m->counters, sizeof(unsigned) * 3 * kCounterSet) != hipSuccess ||
-                         hipMemsetAsync(m->counters, 0, sizeof(unsigned) * 3 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->flags, n_flags);
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->counters, 3 * kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) { bis_mbicgstab_destroy(ctx, m); return st; }
     *out = m;
@@ -277,61 +266,20 @@ bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab *m, int 
                                             const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                             const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    if (precond_type == BIS_PC_MG) { ctx->err = "bis_mbicgstab_set_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
-    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && (precond_type <= BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI) && outer_iters >= 1 && inner_iters >= 0,
-                "bis_mbicgstab_set_preconditioner: bad arguments");
-    BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0,
-                "bis_mbicgstab_set_preconditioner: call it before bis_mbicgstab_init / bis_mbicgstab_iterate");
-    if (precond_type == BIS_PC_TWO_STAGE_GS || precond_type == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {
-        ctx->err = "bis_mbicgstab_set_preconditioner: the two-stage Gauss-Seidel types have no multi-vector form";
-        return BIS_ERR_UNSUPPORTED;
-    }
-    if (outer_iters != 1) {
-        ctx->err = "bis_mbicgstab_set_preconditioner: outer_iters must be 1 on interleaved blocks";
-        return BIS_ERR_UNSUPPORTED;
-    }
-    // the operands the type reads (bis_mapply_preconditioner would refuse them only at bis_mbicgstab_init)
-    const bool lower = precond_type == BIS_PC_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || precond_type == BIS_PC_ILU0 ||
-                       precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
-    const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
-    const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
-    if (precond_type == BIS_PC_BLOCK_JACOBI) // the handle's operand (bis_bj_operand) and nothing else: no diagonal, no TMP, no WORK
-        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == m->n,
-                    "bis_mbicgstab_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
-    BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mbicgstab_set_preconditioner: the type needs a triangle that is null");
-    BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n),
-                "bis_mbicgstab_set_preconditioner: a triangle of another size");
-    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
-                                   (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
-                "bis_mbicgstab_set_preconditioner: the type needs a diagonal that is null");
-    // every allocation first: a failure leaves the handle as it was
+    if (!m) return bis_pc_no_handle(ctx, "bis_mbicgstab", 1, precond_type);
     const int64_t nk = m->n * m->k;
     const bool need_blocks = precond_type != BIS_PC_NONE;
-    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu || precond_type == BIS_PC_FSAI; // (FSAI: the factors and TMP only)
-    double *y = nullptr, *s_t = nullptr, *tmp = nullptr, *work = nullptr;
-    bis_status st = BIS_OK;
-    if (need_blocks && !m->Y) st = bis_vec_alloc(ctx, nk, &y);
-    if (st == BIS_OK && need_blocks && !m->St) st = bis_vec_alloc(ctx, nk, &s_t);
-    if (st == BIS_OK && need_tmp && !m->pc_tmp) st = bis_vec_alloc(ctx, nk, &tmp);
-    if (st == BIS_OK && precond_type == BIS_PC_ILU0_ITER && !m->pc_work) st = bis_vec_alloc(ctx, nk, &work);
-    if (st != BIS_OK) { hipFree(y); hipFree(s_t); hipFree(tmp); hipFree(work); return st; }
-    if (y) m->Y = y;
-    if (s_t) m->St = s_t;
-    if (tmp) m->pc_tmp = tmp;
-    if (work) m->pc_work = work;
-    m->pc = precond_type;
-    m->pcL = L_strict; m->pcU = U_strict;
-    m->pcAD = A_D; m->pcADinv = A_D_inv; m->pcLD = L_D; m->pcUD = U_D;
-    m->pc_inner = inner_iters;
-    return BIS_OK;
+    return bis_pc_bind(ctx, &m->pc, {"bis_mbicgstab", m->n, m->n, m->k, m->initialised || m->enqueued != 0, 0},
+                       {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
+                       {{&m->Y, nk, need_blocks && !m->Y}, {&m->St, nk, need_blocks && !m->St}});
 }
 
 bis_status bis_mbicgstab_destroy(bis_ctx *ctx, bis_mbicgstab *m) {
     BIS_CTX_OK(ctx);
     if (!m) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *v : {m->R, m->R0, m->P, m->V, m->Z, m->Y, m->St, m->sc, m->hist, m->pc_tmp, m->pc_work}) hipFree(v);
+    for (double *v : {m->R, m->R0, m->P, m->V, m->Z, m->Y, m->St, m->sc, m->hist}) hipFree(v);
+    bis_pc_release(m->pc);
     hipFree(m->flags);
     hipFree(m->counters);
     delete m;
@@ -348,7 +296,7 @@ bis_status bis_mbicgstab_init(bis_ctx *ctx, bis_mbicgstab *m, double tol, double
         if (r0_norms_host) for (int j = 0; j < k; ++j) r0_norms_host[j] = 0.0;
         return BIS_OK;
     }
-    const bool pc = m->pc != BIS_PC_NONE;
+    const bool pc = m->pc.type != BIS_PC_NONE;
     bis_status st = bis_ensure_partials(ctx, kPartials);
     if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, m->X, m->Z, k); // init_residual, bicgstab.hpp:148
     if (st != BIS_OK) return st;
@@ -358,7 +306,7 @@ bis_status bis_mbicgstab_init(bis_ctx *ctx, bis_mbicgstab *m, double tol, double
                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, m->Z, (const double *)nullptr, m->R,
                        (double *)nullptr, ctx->partials, stride, m->counters + 2 * kCounterSet, m->hist, m->hist_cap, tol);
     if (pc) {
-        st = mbi_apply_pc(ctx, m, m->P, m->R); // bicgstab.hpp:157
+        st = bis_pc_apply(ctx, m->pc, n, k, m->P, m->R); // bicgstab.hpp:157
         if (st != BIS_OK) return st;
         hipLaunchKernelGGL((mbi_d1_kernel<true, false>), dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->R, m->R0, m->P,
                            (const double *)nullptr, ctx->partials, stride, m->counters);
@@ -384,20 +332,20 @@ bis_status bis_mbicgstab_iterate(bis_ctx *ctx, bis_mbicgstab *m, int n_iters) {
     if (n == 0) return BIS_OK;
     const int g = lockstep_grid(n, k);
     const size_t stride = (size_t)kMaxReduceBlocks;
-    const bool pc = m->pc != BIS_PC_NONE;
+    const bool pc = m->pc.type != BIS_PC_NONE;
     double *Y = pc ? m->Y : m->P, *St = pc ? m->St : m->R;
     bis_status st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) return st;
     ctx->spmv_stop = m->flags; // the SpMM and the sweeps return at once when every column has stopped
     struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
     for (int done = 0; done < n_iters; ++done) {
-        if (pc) st = mbi_apply_pc(ctx, m, m->Y, m->P);
+        if (pc) st = bis_pc_apply(ctx, m->pc, n, k, m->Y, m->P);
         if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, Y, m->V, k);
         if (st != BIS_OK) { m->enqueued += done; return st; }
         hipLaunchKernelGGL((mbi_d1_kernel<false, false>), dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->R, m->R0, m->P,
                            m->V, ctx->partials, stride, m->counters);
         hipLaunchKernelGGL(mbi_s_kernel, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->V, m->R);
-        if (pc) st = mbi_apply_pc(ctx, m, m->St, m->R);
+        if (pc) st = bis_pc_apply(ctx, m->pc, n, k, m->St, m->R);
         if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, St, m->Z, k);
         if (st != BIS_OK) { m->enqueued += done; return st; }
         hipLaunchKernelGGL(mbi_omega_kernel, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->Z, m->R, ctx->partials, stride,

@@ -21,6 +21,7 @@
 // pass C.  The sweeps and the elementwise kernels of the apply may still compute a frozen column's z: nothing of that
 // column is read afterwards.  Without the call, the None / Jacobi schedule above is launched exactly as before.
 #include "bis_lockstep.hpp"
+#include "bis_pc.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -42,12 +43,7 @@ struct bis_mcg {
     int enqueued = 0;
     unsigned *counters = nullptr; // three last-arriver counter sets (pass A', pass B, the (r,z) pass of a general preconditioner)
     bool initialised = false;     // bis_mcg_init has run
-    // general preconditioner (bis_mcg_set_preconditioner): Z = M^-1 R through bis_mapply_preconditioner
-    int pc = -1;
-    const bis_mat *pcL = nullptr, *pcU = nullptr;
-    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
-    double *pc_tmp = nullptr, *pc_work = nullptr; // n x k blocks of the apply's scratch, where the type needs them
-    int pc_inner = 0;
+    bis_pc_binding pc; // general preconditioner (bis_mcg_set_preconditioner), once set: Z = M^-1 R through bis_pc_apply; its scratch: n x k blocks
 };
 
 namespace {
@@ -271,12 +267,6 @@ __global__ __launch_bounds__(kT) void mcg_p_update_kernel(int64_t n, int k, cons
     }
 }
 
-// Z = M^-1 R with the preconditioner of bis_mcg_set_preconditioner
-inline bis_status mcg_apply_pc(bis_ctx *ctx, bis_mcg *m) {
-    return bis_mapply_preconditioner(ctx, m->pc, m->n, m->k, m->pcL, m->pcU, m->pcAD, m->pcADinv, m->pcLD, m->pcUD, m->Z, m->R,
-                                     m->pc_tmp, m->pc_work, 1, m->pc_inner);
-}
-
 } // namespace
 
 extern "C" {
@@ -299,10 +289,8 @@ bis_status bis_mcg_create(bis_ctx *ctx, const bis_mat *A, const double *A_D, con
     if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, &m->T);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)M_COUNT * n_rhs, &m->sc);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
-    if (st == BIS_OK && (hipMalloc(&m->flags, sizeof(int) * n_flags) != hipSuccess ||
-                         hipMemsetAsync(m->flags, 0, sizeof(int) * n_flags, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&m->counters, sizeof(unsigned) * 3 * kCounterSet) != hipSuccess ||
-                         hipMemsetAsync(m->counters, 0, sizeof(unsigned) * 3 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->flags, n_flags);
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->counters, 3 * kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, (size_t)2 * kMaxK * kMaxReduceBlocks);
     if (st != BIS_OK) { bis_mcg_destroy(ctx, m); return st; }
     if (!A_D) m->Z = m->R; // z aliases r without a preconditioner
@@ -314,49 +302,10 @@ bis_status bis_mcg_set_preconditioner(bis_ctx *ctx, bis_mcg *m, int precond_type
                                       const double *A_D, const double *A_D_inv, const double *L_D, const double *U_D,
                                       int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    if (precond_type == BIS_PC_MG) { ctx->err = "bis_mcg_set_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
-    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && (precond_type <= BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI) && outer_iters >= 1 && inner_iters >= 0,
-                "bis_mcg_set_preconditioner: bad arguments");
-    BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0, "bis_mcg_set_preconditioner: call it before bis_mcg_init / bis_mcg_iterate");
-    if (precond_type == BIS_PC_TWO_STAGE_GS || precond_type == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {
-        ctx->err = "bis_mcg_set_preconditioner: the two-stage Gauss-Seidel types have no multi-vector form";
-        return BIS_ERR_UNSUPPORTED;
-    }
-    if (outer_iters != 1) {
-        ctx->err = "bis_mcg_set_preconditioner: outer_iters must be 1 on interleaved blocks";
-        return BIS_ERR_UNSUPPORTED;
-    }
-    // the operands the type reads (bis_mapply_preconditioner would refuse them only at bis_mcg_init)
-    const bool lower = precond_type == BIS_PC_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || precond_type == BIS_PC_ILU0 ||
-                       precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
-    const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
-    const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
-    if (precond_type == BIS_PC_BLOCK_JACOBI) // the handle's operand (bis_bj_operand) and nothing else: no diagonal, no TMP, no WORK
-        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == m->n,
-                    "bis_mcg_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
-    BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mcg_set_preconditioner: the type needs a triangle that is null");
-    BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n), "bis_mcg_set_preconditioner: a triangle of another size");
-    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
-                                   (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
-                "bis_mcg_set_preconditioner: the type needs a diagonal that is null");
-    // every allocation first: a failure leaves the handle as it was
-    const int64_t nk = m->n * m->k;
-    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu || precond_type == BIS_PC_FSAI; // (FSAI: the factors and TMP only)
-    double *z = nullptr, *tmp = nullptr, *work = nullptr;
-    bis_status st = BIS_OK;
-    if (m->Z == m->R) st = bis_vec_alloc(ctx, nk, &z); // z aliased r (no preconditioner at creation): it needs its own storage now
-    if (st == BIS_OK && need_tmp && !m->pc_tmp) st = bis_vec_alloc(ctx, nk, &tmp);
-    if (st == BIS_OK && precond_type == BIS_PC_ILU0_ITER && !m->pc_work) st = bis_vec_alloc(ctx, nk, &work);
-    if (st != BIS_OK) { hipFree(z); hipFree(tmp); hipFree(work); return st; }
-    if (z) m->Z = z;
-    if (tmp) m->pc_tmp = tmp;
-    if (work) m->pc_work = work;
-    m->pc = precond_type;
-    m->pcL = L_strict; m->pcU = U_strict;
-    m->pcAD = A_D; m->pcADinv = A_D_inv; m->pcLD = L_D; m->pcUD = U_D;
-    m->pc_inner = inner_iters;
-    return BIS_OK;
+    if (!m) return bis_pc_no_handle(ctx, "bis_mcg", 1, precond_type);
+    return bis_pc_bind(ctx, &m->pc, {"bis_mcg", m->n, m->n, m->k, m->initialised || m->enqueued != 0, 0},
+                       {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
+                       {{&m->Z, m->n * m->k, m->Z == m->R}}); // z aliased r (no preconditioner at creation): it needs its own storage now
 }
 
 bis_status bis_mcg_destroy(bis_ctx *ctx, bis_mcg *m) {
@@ -371,8 +320,7 @@ bis_status bis_mcg_destroy(bis_ctx *ctx, bis_mcg *m) {
     hipFree(m->hist);
     hipFree(m->flags);
     hipFree(m->counters);
-    hipFree(m->pc_tmp);
-    hipFree(m->pc_work);
+    bis_pc_release(m->pc);
     delete m;
     return BIS_OK;
 }
@@ -391,10 +339,10 @@ bis_status bis_mcg_init(bis_ctx *ctx, bis_mcg *m, double tol, double *r0_norms_h
     if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, m->X, m->T, k); // init_residual, cg.hpp:100-118
     if (st != BIS_OK) return st;
     const int g = lockstep_grid(n, k);
-    if (m->pc >= 0) { // general preconditioner: r0 and (r,r), z0 = M^-1 r0, then p0 = z0, (r,z) and the start of the solve
+    if (m->pc.set) { // general preconditioner: r0 and (r,r), z0 = M^-1 r0, then p0 = z0, (r,z) and the start of the solve
         hipLaunchKernelGGL(mcg_update_pc_kernel<true>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->B, m->R,
                            ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet);
-        st = mcg_apply_pc(ctx, m);
+        st = bis_pc_apply(ctx, m->pc, n, k, m->Z, m->R);
         if (st != BIS_OK) return st;
         hipLaunchKernelGGL(mcg_rz_kernel<true>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->R, m->Z, m->P,
                            ctx->partials, (size_t)kMaxReduceBlocks, m->counters + 2 * kCounterSet, m->hist, m->hist_cap, tol);
@@ -433,10 +381,10 @@ bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters) {
         if (st != BIS_OK) { m->enqueued += done; return st; }
         hipLaunchKernelGGL(mcg_pap_kernel, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->T, m->P, m->sc, m->flags, ctx->partials,
                            (size_t)kMaxReduceBlocks, m->counters);
-        if (m->pc >= 0) { // general preconditioner: bis_cg.hip's schedule (cg_enqueue_iteration, cg->pc >= 0) per column
+        if (m->pc.set) { // general preconditioner: bis_cg.hip's schedule (cg_enqueue_iteration, cg->pc.set) per column
             hipLaunchKernelGGL(mcg_update_pc_kernel<false>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->T, m->B, m->R,
                                ctx->partials, (size_t)kMaxReduceBlocks, m->counters + kCounterSet);
-            st = mcg_apply_pc(ctx, m);
+            st = bis_pc_apply(ctx, m->pc, n, k, m->Z, m->R);
             if (st != BIS_OK) { m->enqueued += done; return st; }
             hipLaunchKernelGGL(mcg_rz_kernel<false>, dim3(g), dim3(kT), 0, ctx->stream, n, k, m->sc, m->flags, m->R, m->Z, m->P,
                                ctx->partials, (size_t)kMaxReduceBlocks, m->counters + 2 * kCounterSet, m->hist, m->hist_cap, 0.0);

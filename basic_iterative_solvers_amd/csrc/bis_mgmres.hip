@@ -28,6 +28,7 @@
 // passes reads W, V_{i-1}, V_i and writes W (32 B), the last reads W, V_n and writes W (24 B), the scale reads W and
 // writes V_{n+1} (16 B): 56 + 32 n bytes.
 #include "bis_lockstep.hpp"
+#include "bis_pc.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -48,11 +49,7 @@ struct bis_mgmres {
     int enqueued = 0;
     unsigned *counters = nullptr; // last-arriver counter sets: Gram-Schmidt passes, residual / norm passes, combine
     bool initialised = false;
-    int pc = BIS_PC_NONE;
-    const bis_mat *pcL = nullptr, *pcU = nullptr;
-    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
-    double *pc_tmp = nullptr, *pc_work = nullptr;
-    int pc_inner = 0;
+    bis_pc_binding pc; // its scratch: n x k blocks
 };
 
 namespace {
@@ -329,12 +326,6 @@ __global__ void mgm_ysol_kernel(int k, mgm_layout L, double *st, const int *flag
     mgm_backsub(L, s, flags[4 + 4 * k + 4 * t + X_POS], s + L.ysol());
 }
 
-// W = M^-1 W with the preconditioner of bis_mgmres_set_preconditioner (never called for BIS_PC_NONE)
-inline bis_status mgm_apply_pc(bis_ctx *ctx, bis_mgmres *m) {
-    return bis_mapply_preconditioner(ctx, m->pc, m->n, m->k, m->pcL, m->pcU, m->pcAD, m->pcADinv, m->pcLD, m->pcUD, m->W, m->W,
-                                     m->pc_tmp, m->pc_work, 1, m->pc_inner);
-}
-
 constexpr size_t kPartials = (size_t)kMaxK * kMaxReduceBlocks;
 constexpr size_t kStride = (size_t)kMaxReduceBlocks;
 
@@ -343,7 +334,7 @@ bis_status mgm_start_cycle(bis_ctx *ctx, bis_mgmres *m, bool restart, double tol
     const int64_t n = m->n;
     const int k = m->k, g = lockstep_grid(n, k);
     const mgm_layout L{m->m};
-    const bool pc = m->pc != BIS_PC_NONE;
+    const bool pc = m->pc.type != BIS_PC_NONE;
     const int first = restart ? 0 : BK_INIT0, beta = BK_BETA | (restart ? BK_RESTART : 0);
     unsigned *counter = m->counters + kCounterSet;
 #define BIS_MGM_RESID(RESID, REDUCE, BOOK)                                                                                     \
@@ -353,7 +344,7 @@ bis_status mgm_start_cycle(bis_ctx *ctx, bis_mgmres *m, bool restart, double tol
         BIS_MGM_RESID(true, true, first | beta);
     } else {
         if (restart) BIS_MGM_RESID(true, false, 0); else BIS_MGM_RESID(true, true, first);
-        bis_status st = mgm_apply_pc(ctx, m);
+        bis_status st = bis_pc_apply(ctx, m->pc, n, k, m->W, m->W); // W = M^-1 W
         if (st != BIS_OK) return st;
         BIS_MGM_RESID(false, true, beta);
     }
@@ -386,10 +377,8 @@ bis_status bis_mgmres_create(bis_ctx *ctx, const bis_mat *A, const double *B, do
     if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, &m->W);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)L.size() * n_rhs, &m->st);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
-    if (st == BIS_OK && (hipMalloc(&m->flags, sizeof(int) * n_flags) != hipSuccess ||
-                         hipMemsetAsync(m->flags, 0, sizeof(int) * n_flags, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&m->counters, sizeof(unsigned) * 3 * kCounterSet) != hipSuccess ||
-                         hipMemsetAsync(m->counters, 0, sizeof(unsigned) * 3 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->flags, n_flags);
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->counters, 3 * kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) { bis_mgmres_destroy(ctx, m); return st; }
     *out = m;
@@ -400,56 +389,17 @@ bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precon
                                          const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    if (precond_type == BIS_PC_MG) { ctx->err = "bis_mgmres_set_preconditioner: the multigrid preconditioner has no multi-vector form"; return BIS_ERR_UNSUPPORTED; }
-    BIS_REQUIRE(ctx, m && precond_type >= BIS_PC_NONE && (precond_type <= BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI) && outer_iters >= 1 && inner_iters >= 0,
-                "bis_mgmres_set_preconditioner: bad arguments");
-    BIS_REQUIRE(ctx, !m->initialised && m->enqueued == 0,
-                "bis_mgmres_set_preconditioner: call it before bis_mgmres_init / bis_mgmres_iterate");
-    if (precond_type == BIS_PC_TWO_STAGE_GS || precond_type == BIS_PC_SYMMETRIC_TWO_STAGE_GS) {
-        ctx->err = "bis_mgmres_set_preconditioner: the two-stage Gauss-Seidel types have no multi-vector form";
-        return BIS_ERR_UNSUPPORTED;
-    }
-    if (outer_iters != 1) {
-        ctx->err = "bis_mgmres_set_preconditioner: outer_iters must be 1 on interleaved blocks";
-        return BIS_ERR_UNSUPPORTED;
-    }
-    // the operands the type reads (bis_mapply_preconditioner would refuse them only at bis_mgmres_init)
-    const bool lower = precond_type == BIS_PC_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || precond_type == BIS_PC_ILU0 ||
-                       precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
-    const bool upper = precond_type == BIS_PC_BACKWARDS_GAUSS_SEIDEL || precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER || precond_type == BIS_PC_FSAI;
-    const bool ilu = precond_type == BIS_PC_ILU0 || precond_type == BIS_PC_ILU0_ITER;
-    if (precond_type == BIS_PC_BLOCK_JACOBI) // the handle's operand (bis_bj_operand) and nothing else: no diagonal, no TMP, no WORK
-        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == m->n,
-                    "bis_mgmres_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
-    BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_mgmres_set_preconditioner: the type needs a triangle that is null");
-    BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == m->n) && (!upper || U_strict->n_rows == m->n),
-                "bis_mgmres_set_preconditioner: a triangle of another size");
-    BIS_REQUIRE(ctx, m->n == 0 || ((precond_type == BIS_PC_NONE || precond_type == BIS_PC_FSAI || precond_type == BIS_PC_BLOCK_JACOBI || ilu || A_D) && (!ilu || L_D) && (precond_type != BIS_PC_ILU0 || U_D) &&
-                                   (precond_type != BIS_PC_ILU0_ITER || A_D_inv)),
-                "bis_mgmres_set_preconditioner: the type needs a diagonal that is null");
-    // every allocation first: a failure leaves the handle as it was
-    const int64_t nk = m->n * m->k;
-    const bool need_tmp = precond_type == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || ilu || precond_type == BIS_PC_FSAI; // (FSAI: the factors and TMP only)
-    double *tmp = nullptr, *work = nullptr;
-    bis_status st = BIS_OK;
-    if (need_tmp && !m->pc_tmp) st = bis_vec_alloc(ctx, nk, &tmp);
-    if (st == BIS_OK && precond_type == BIS_PC_ILU0_ITER && !m->pc_work) st = bis_vec_alloc(ctx, nk, &work);
-    if (st != BIS_OK) { hipFree(tmp); hipFree(work); return st; }
-    if (tmp) m->pc_tmp = tmp;
-    if (work) m->pc_work = work;
-    m->pc = precond_type;
-    m->pcL = L_strict; m->pcU = U_strict;
-    m->pcAD = A_D; m->pcADinv = A_D_inv; m->pcLD = L_D; m->pcUD = U_D;
-    m->pc_inner = inner_iters;
-    return BIS_OK;
+    if (!m) return bis_pc_no_handle(ctx, "bis_mgmres", 1, precond_type);
+    return bis_pc_bind(ctx, &m->pc, {"bis_mgmres", m->n, m->n, m->k, m->initialised || m->enqueued != 0, 0},
+                       {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters}, {});
 }
 
 bis_status bis_mgmres_destroy(bis_ctx *ctx, bis_mgmres *m) {
     BIS_CTX_OK(ctx);
     if (!m) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *v : {m->V, m->W, m->st, m->hist, m->pc_tmp, m->pc_work}) hipFree(v);
+    for (double *v : {m->V, m->W, m->st, m->hist}) hipFree(v);
+    bis_pc_release(m->pc);
     hipFree(m->flags);
     hipFree(m->counters);
     delete m;
@@ -490,7 +440,7 @@ bis_status bis_mgmres_iterate(bis_ctx *ctx, bis_mgmres *m, int n_iters) {
     const int g = lockstep_grid(n, k);
     const mgm_layout L{len};
     const int64_t blk = n * k;
-    const bool pc = m->pc != BIS_PC_NONE;
+    const bool pc = m->pc.type != BIS_PC_NONE;
     bis_status st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) return st;
     ctx->spmv_stop = m->flags; // the SpMM and the sweeps return at once when every column has stopped
@@ -505,7 +455,7 @@ bis_status bis_mgmres_iterate(bis_ctx *ctx, bis_mgmres *m, int n_iters) {
     for (int done = 0; done < n_iters; ++done) {
         const int pos = (m->enqueued + done) % len; // every live column is at this position of its cycle
         st = bis_spmm_launch(ctx, m->A, m->V + pos * blk, m->W, k);
-        if (st == BIS_OK && pc) st = mgm_apply_pc(ctx, m);
+        if (st == BIS_OK && pc) st = bis_pc_apply(ctx, m->pc, m->n, m->k, m->W, m->W);
         if (st != BIS_OK) { m->enqueued += done; return st; }
         BIS_MGM_GS(0, 0, nullptr, m->V);
         for (int i = 1; i <= pos; ++i) BIS_MGM_GS(1, i - 1, m->V + (i - 1) * blk, m->V + i * blk);

@@ -32,7 +32,7 @@
 // order.  No kernel waits for another workgroup; no floating-point atomics; two runs give the same bits.  After the stop
 // every launch of the schedule returns at once, except pass D of the stopping iteration: x is the iterate the last history
 // entry belongs to.  (Launches of a preconditioner queued behind the stop may still run; nothing reads their results.)
-#include "bis_internal.hpp"
+#include "bis_pc.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -53,11 +53,7 @@ struct bis_minres {
     int enqueued = 0;
     unsigned *counters = nullptr; // two last-arriver counter sets: pass B, pass C
     bool initialised = false;
-    int pc = BIS_PC_NONE;
-    const bis_mat *pcL = nullptr, *pcU = nullptr;
-    const double *pcAD = nullptr, *pcADinv = nullptr, *pcLD = nullptr, *pcUD = nullptr;
-    double *pc_tmp = nullptr, *pc_work = nullptr;
-    int pc_outer = 1, pc_inner = 0;
+    bis_pc_binding pc;
 };
 
 namespace {
@@ -260,7 +256,7 @@ inline int mr_grid(int64_t n, int cap) {
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // pass C reads D 16 bytes per lane: a diagonal off a 16-byte boundary takes the general path (the apply, then the dot pass)
-inline bool fused_jacobi(const bis_minres *s) { return s->pc == BIS_PC_JACOBI && s->pc_outer == 1 && aligned16(s->pcAD); }
+inline bool fused_jacobi(const bis_minres *s) { return s->pc.type == BIS_PC_JACOBI && s->pc.outer == 1 && aligned16(s->pc.AD); }
 
 } // namespace
 
@@ -281,10 +277,8 @@ bis_status bis_minres_create(bis_ctx *ctx, const bis_mat *A, const double *b, do
     for (int i = 0; i < 3 && st == BIS_OK; ++i) st = bis_vec_alloc(ctx, s->ld, &s->W[i]);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, S_COUNT, &s->sc);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, s->hist_cap, &s->hist);
-    if (st == BIS_OK && (hipMalloc(&s->flags, sizeof(int) * 4) != hipSuccess ||
-                         hipMemsetAsync(s->flags, 0, sizeof(int) * 4, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
-    if (st == BIS_OK && (hipMalloc(&s->counters, sizeof(unsigned) * 2 * kCounterSet) != hipSuccess ||
-                         hipMemsetAsync(s->counters, 0, sizeof(unsigned) * 2 * kCounterSet, ctx->stream) != hipSuccess)) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->flags, 4);
+    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->counters, 2 * kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) { bis_minres_destroy(ctx, s); return st; }
     *out = s;
@@ -295,59 +289,17 @@ bis_status bis_minres_set_preconditioner(bis_ctx *ctx, bis_minres *s, int precon
                                          const bis_mat *U_strict, const double *A_D, const double *A_D_inv, const double *L_D,
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
-    BIS_REQUIRE(ctx, s && precond_type >= BIS_PC_NONE && precond_type <= BIS_PC_BLOCK_JACOBI && outer_iters >= 1 && inner_iters >= 0,
-                "bis_minres_set_preconditioner: bad arguments");
-    BIS_REQUIRE(ctx, !s->initialised && s->enqueued == 0,
-                "bis_minres_set_preconditioner: call it before bis_minres_init / bis_minres_iterate");
-    const int pc = precond_type;
-    if (pc == BIS_PC_MG) { // bis_apply_preconditioner's checks, in its order
-        BIS_REQUIRE(ctx, L_strict && L_strict->mg && L_strict->n_rows == s->n,
-                    "bis_minres_set_preconditioner: MG needs the operand of a hierarchy of the solver's size in L_strict");
-        if (outer_iters != 1) { ctx->err = "bis_minres_set_preconditioner: MG with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
-    }
-    if (pc == BIS_PC_BLOCK_JACOBI) {
-        BIS_REQUIRE(ctx, L_strict && L_strict->bj && L_strict->n_rows == s->n,
-                    "bis_minres_set_preconditioner: block Jacobi needs the operand of a handle of the solver's size in L_strict");
-        if (outer_iters != 1) { ctx->err = "bis_minres_set_preconditioner: block Jacobi with outer_iters != 1 is not built"; return BIS_ERR_UNSUPPORTED; }
-    }
-    // the operands the type reads (bis_apply_preconditioner would refuse them only inside bis_minres_iterate)
-    const bool two = pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
-    const bool ilu = pc == BIS_PC_ILU0 || pc == BIS_PC_ILU0_ITER;
-    const bool lower = pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || two || ilu || pc == BIS_PC_FSAI;
-    const bool upper = pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
-                       pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS || ilu || pc == BIS_PC_FSAI;
-    const bool need_AD = pc == BIS_PC_JACOBI || pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL ||
-                         pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
-    const bool need_ADinv = two || pc == BIS_PC_ILU0_ITER;
-    if (pc != BIS_PC_MG && pc != BIS_PC_BLOCK_JACOBI) {
-        BIS_REQUIRE(ctx, (!lower || L_strict) && (!upper || U_strict), "bis_minres_set_preconditioner: the type needs a triangle that is null");
-        BIS_REQUIRE(ctx, (!lower || L_strict->n_rows == s->n) && (!upper || U_strict->n_rows == s->n),
-                    "bis_minres_set_preconditioner: a triangle of another size");
-        BIS_REQUIRE(ctx, s->n == 0 || ((!need_AD || A_D) && (!need_ADinv || A_D_inv) && (!ilu || L_D) && (pc != BIS_PC_ILU0 || U_D)),
-                    "bis_minres_set_preconditioner: the type needs a diagonal that is null");
-    }
-    // every allocation first: a failure leaves the handle as it was
-    const bool need_tmp = pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || two || ilu || pc == BIS_PC_FSAI;
-    const bool need_work = two || pc == BIS_PC_ILU0_ITER;
-    double *tmp = nullptr, *work = nullptr;
-    bis_status st = BIS_OK;
-    if (need_tmp && !s->pc_tmp) st = bis_vec_alloc(ctx, s->ld, &tmp);
-    if (st == BIS_OK && need_work && !s->pc_work) st = bis_vec_alloc(ctx, s->ld, &work);
-    if (st != BIS_OK) { hipFree(tmp); hipFree(work); return st; }
-    if (tmp) s->pc_tmp = tmp;
-    if (work) s->pc_work = work;
-    s->pc = pc;
-    s->pcL = L_strict; s->pcU = U_strict;
-    s->pcAD = A_D; s->pcADinv = A_D_inv; s->pcLD = L_D; s->pcUD = U_D;
-    s->pc_outer = outer_iters; s->pc_inner = inner_iters;
-    return BIS_OK;
+    if (!s) return bis_pc_no_handle(ctx, "bis_minres", 0, precond_type);
+    return bis_pc_bind(ctx, &s->pc, {"bis_minres", s->n, s->ld, 0, s->initialised || s->enqueued != 0, 0},
+                       {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters}, {});
 }
 
 bis_status bis_minres_destroy(bis_ctx *ctx, bis_minres *s) {
     BIS_CTX_OK(ctx);
     if (!s) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *p : {s->v, s->R[0], s->R[1], s->R[2], s->W[0], s->W[1], s->W[2], s->sc, s->hist, s->pc_tmp, s->pc_work}) hipFree(p);
+    for (double *p : {s->v, s->R[0], s->R[1], s->R[2], s->W[0], s->W[1], s->W[2], s->sc, s->hist}) hipFree(p);
+    bis_pc_release(s->pc);
     hipFree(s->flags);
     hipFree(s->counters);
     delete s;
@@ -365,11 +317,9 @@ bis_status bis_minres_init(bis_ctx *ctx, bis_minres *s, double tol, double *r0_n
         if (r0_norm_host) *r0_norm_host = 0.0;
         return BIS_OK;
     }
-    double *r2 = s->R[0], *y = s->pc == BIS_PC_NONE ? r2 : s->R[2]; // what iteration 0 would have left
+    double *r2 = s->R[0], *y = s->pc.type == BIS_PC_NONE ? r2 : s->R[2]; // what iteration 0 would have left
     bis_status st = bis_compute_residual(ctx, s->A, s->x, s->b, r2, s->v);
-    if (st == BIS_OK && s->pc != BIS_PC_NONE)
-        st = bis_apply_preconditioner(ctx, s->pc, n, s->pcL, s->pcU, s->pcAD, s->pcADinv, s->pcLD, s->pcUD, y, r2, s->pc_tmp,
-                                      s->pc_work, s->pc_outer, s->pc_inner);
+    if (st == BIS_OK && s->pc.type != BIS_PC_NONE) st = bis_pc_apply(ctx, s->pc, n, 0, y, r2);
     double rzy = 0.0;
     if (st == BIS_OK) st = bis_dot(ctx, r2, y, n, &rzy);
     if (st != BIS_OK) return st;
@@ -406,7 +356,7 @@ bis_status bis_minres_iterate(bis_ctx *ctx, bis_minres *s, int n_iters) {
     unsigned *cnt_b = s->counters, *cnt_c = s->counters + kCounterSet;
 #define BIS_MR_C(MODE, Y)                                                                                                      \
     hipLaunchKernelGGL((mr_c_kernel<MODE>), dim3(g), dim3(kT), 0, ctx->stream, n, s->sc, s->flags, t, (const double *)r2,     \
-                       s->pcAD, Y, ctx->partials, cnt_c, s->hist, s->hist_cap)
+                       s->pc.AD, Y, ctx->partials, cnt_c, s->hist, s->hist_cap)
     for (int done = 0; done < n_iters; ++done) {
         const int k = s->enqueued + done + 1;
         double *t = s->R[k % 3], *r1 = s->R[(k + 1) % 3], *r2 = s->R[(k + 2) % 3];
@@ -416,7 +366,7 @@ bis_status bis_minres_iterate(bis_ctx *ctx, bis_minres *s, int n_iters) {
         if (st != BIS_OK) { s->enqueued += done; return st; }
         hipLaunchKernelGGL(mr_b_kernel, dim3(g), dim3(kT), 0, ctx->stream, n, k >= 2 ? 1 : 0, s->sc, (const int *)s->flags, t,
                            (const double *)r1, (const double *)s->v, ctx->partials, cnt_b);
-        if (s->pc == BIS_PC_NONE) {
+        if (s->pc.type == BIS_PC_NONE) {
             BIS_MR_C(C_NONE, (double *)nullptr);
         } else if (fused_jacobi(s)) {
             y = r1;
@@ -424,8 +374,7 @@ bis_status bis_minres_iterate(bis_ctx *ctx, bis_minres *s, int n_iters) {
         } else {
             y = r1;
             BIS_MR_C(C_UPDATE_ONLY, (double *)nullptr);
-            st = bis_apply_preconditioner(ctx, s->pc, n, s->pcL, s->pcU, s->pcAD, s->pcADinv, s->pcLD, s->pcUD, y, t, s->pc_tmp,
-                                          s->pc_work, s->pc_outer, s->pc_inner);
+            st = bis_pc_apply(ctx, s->pc, n, 0, y, t);
             if (st != BIS_OK) { s->enqueued += done; return st; } // (the device's count stays behind: call bis_minres_init again)
             BIS_MR_C(C_DOT_ONLY, y);
         }

@@ -1,9 +1,103 @@
 // bis_precond.hip -- the preconditioner dispatcher (reference kernels.hpp:312-414) over the library's own kernels: the
 // triangular sweeps (bis_sptrsv.hip), the iterative triangular solves (bis_itrsv.hip), SpMV (the FSAI factors of
 // bis_fsai.hip), the multigrid cycle (bis_mg.hip) and the vector kernels.
-#include "bis_internal.hpp"
+#include "bis_pc.hpp"
 
 #include <algorithm>
+
+// ---- the binding of the solver handles (bis_pc.hpp) ----------------------------------------------------------------------
+// The one place that says what bis_apply_preconditioner / bis_mapply_preconditioner below read for a type.
+bis_pc_needs bis_pc_needs_of(int pc) {
+    const bool two = pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
+    const bool ilu = pc == BIS_PC_ILU0 || pc == BIS_PC_ILU0_ITER;
+    const bool lower = pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || two || ilu || pc == BIS_PC_FSAI;
+    const bool upper = pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL ||
+                       pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS || ilu || pc == BIS_PC_FSAI;
+    const bool need_AD = pc == BIS_PC_JACOBI || pc == BIS_PC_GAUSS_SEIDEL || pc == BIS_PC_BACKWARDS_GAUSS_SEIDEL ||
+                         pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS;
+    const bool need_ADinv = two || pc == BIS_PC_ILU0_ITER; // (ILU0_ITER: A_D_inv carries 1 / U_D)
+    const bool need_tmp = pc == BIS_PC_SYMMETRIC_GAUSS_SEIDEL || two || ilu || pc == BIS_PC_FSAI;
+    return {lower, upper, need_AD, need_ADinv, /*LD*/ ilu, /*UD*/ pc == BIS_PC_ILU0, need_tmp, /*work*/ need_ADinv};
+}
+
+bis_status bis_pc_bind(bis_ctx *ctx, bis_pc_binding *b, const bis_pc_site &site, const bis_pc_args &a,
+                       std::initializer_list<bis_pc_block> blocks) {
+    auto refuse = [&](bis_status st, std::initializer_list<const char *> why) { // ctx->err = "<solver>_set_preconditioner: <why...>"
+        ctx->err.assign(site.solver).append("_set_preconditioner: ");
+        for (const char *w : why) ctx->err.append(w);
+        return st;
+    };
+    const int pc = a.type;
+    const int64_t n = site.n;
+    const bool lockstep = site.n_rhs > 0, mg = pc == BIS_PC_MG;
+    if (lockstep && mg) return refuse(BIS_ERR_UNSUPPORTED, {"the multigrid preconditioner has no multi-vector form"});
+    if (!b || pc < BIS_PC_NONE || pc > BIS_PC_BLOCK_JACOBI || a.outer < 1 || a.inner < 0) return refuse(BIS_ERR_INVALID, {"bad arguments"});
+    if (site.live) return refuse(BIS_ERR_INVALID, {"call it before ", site.solver, "_init / ", site.solver, "_iterate"});
+    if (lockstep && (pc == BIS_PC_TWO_STAGE_GS || pc == BIS_PC_SYMMETRIC_TWO_STAGE_GS))
+        return refuse(BIS_ERR_UNSUPPORTED, {"the two-stage Gauss-Seidel types have no multi-vector form"});
+    if (lockstep && a.outer != 1) return refuse(BIS_ERR_UNSUPPORTED, {"outer_iters must be 1 on interleaved blocks"});
+    if (site.cg && pc == BIS_PC_FSAI && !(a.L && a.U && a.L->n_rows == n && a.U->n_rows == n))
+        return refuse(BIS_ERR_INVALID, {"FSAI needs both factors, of the solver's size"});
+    if (mg || pc == BIS_PC_BLOCK_JACOBI) { // bis_apply_preconditioner's checks, in its order
+        const char *what = mg ? "MG" : "block Jacobi";
+        if (!(a.L && (mg ? a.L->mg != nullptr : a.L->bj != nullptr) && a.L->n_rows == n))
+            return refuse(BIS_ERR_INVALID, {what, " needs the operand of a ", mg ? "hierarchy" : "handle", " of the solver's size in L_strict"});
+        if (site.cg == 2 || a.outer != 1)
+            return refuse(BIS_ERR_UNSUPPORTED, {what, site.cg ? " on a distributed handle, or with outer_iters != 1, is not built" : " with outer_iters != 1 is not built"});
+    }
+    // the operands the type reads (the dispatchers would refuse them only inside init / iterate)
+    const bis_pc_needs need = bis_pc_needs_of(pc);
+    if (!site.cg) { // bis_cg's laxity is kept on purpose: it leaves these refusals to the apply inside bis_cg_init
+        if ((need.lower && !a.L) || (need.upper && !a.U)) return refuse(BIS_ERR_INVALID, {"the type needs a triangle that is null"});
+        if ((need.lower && a.L->n_rows != n) || (need.upper && a.U->n_rows != n)) return refuse(BIS_ERR_INVALID, {"a triangle of another size"});
+        if (n != 0 && ((need.AD && !a.AD) || (need.ADinv && !a.ADinv) || (need.LD && !a.LD) || (need.UD && !a.UD)))
+            return refuse(BIS_ERR_INVALID, {"the type needs a diagonal that is null"});
+    }
+    // every allocation first: a failure leaves the handle as it was
+    const int64_t scratch = site.ld * std::max(1, site.n_rhs);
+    double *tmp = nullptr, *work = nullptr, *made[4] = {nullptr, nullptr, nullptr, nullptr};
+    bis_status st = blocks.size() <= 4 ? BIS_OK : BIS_ERR_INVALID;
+    int i = 0;
+    for (const bis_pc_block &blk : blocks) {
+        if (st == BIS_OK && blk.wanted) st = bis_vec_alloc(ctx, blk.count, &made[i]);
+        ++i;
+    }
+    if (st == BIS_OK && need.tmp && !b->tmp) st = bis_vec_alloc(ctx, scratch, &tmp);
+    if (st == BIS_OK && need.work && !b->work) st = bis_vec_alloc(ctx, scratch, &work);
+    if (st != BIS_OK) {
+        for (double *p : {made[0], made[1], made[2], made[3], tmp, work}) hipFree(p);
+        return st;
+    }
+    i = 0;
+    for (const bis_pc_block &blk : blocks) {
+        if (made[i]) *blk.slot = made[i];
+        ++i;
+    }
+    if (tmp) { b->tmp = tmp; b->own_tmp = true; }
+    if (work) { b->work = work; b->own_work = true; }
+    b->set = true;
+    b->type = pc;
+    b->L = a.L; b->U = a.U;
+    b->AD = a.AD; b->ADinv = a.ADinv; b->LD = a.LD; b->UD = a.UD;
+    b->outer = a.outer; b->inner = a.inner;
+    return BIS_OK;
+}
+
+bis_status bis_pc_no_handle(bis_ctx *ctx, const char *solver, int n_rhs, int type) {
+    return bis_pc_bind(ctx, nullptr, {solver, 0, 0, n_rhs, false, 0}, {type, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0}, {});
+}
+
+bis_status bis_pc_apply(bis_ctx *ctx, const bis_pc_binding &b, int64_t n, int n_rhs, double *out, double *in) {
+    if (n_rhs > 0)
+        return bis_mapply_preconditioner(ctx, b.type, n, n_rhs, b.L, b.U, b.AD, b.ADinv, b.LD, b.UD, out, in, b.tmp, b.work, b.outer, b.inner);
+    return bis_apply_preconditioner(ctx, b.type, n, b.L, b.U, b.AD, b.ADinv, b.LD, b.UD, out, in, b.tmp, b.work, b.outer, b.inner);
+}
+
+void bis_pc_release(bis_pc_binding &b) {
+    if (b.own_tmp) hipFree(b.tmp);
+    if (b.own_work) hipFree(b.work);
+    b = bis_pc_binding{};
+}
 
 extern "C" {
 
