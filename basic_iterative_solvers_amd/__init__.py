@@ -441,6 +441,9 @@ class Context:
     def minres(self, A, b, x):
         return MINRES(self, A, b, x)
 
+    def idr(self, A, b, x, s=4):
+        return IDR(self, A, b, x, s)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -750,7 +753,7 @@ def _handle_pc(pc, Ls):
 
 
 class _Solver:
-    """What the six solver handles share; a class names its library symbols bis_<_sym>_*."""
+    """What the seven solver handles share; a class names its library symbols bis_<_sym>_*."""
 
     _sym = None
 
@@ -938,6 +941,40 @@ class MINRES(_Solver):
         hist = np.zeros(hist_cap)
         self.ctx.check(self.ctx.lib.bis_minres_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv),
                                                       hist.ctypes, C.c_int(hist_cap)))
+        return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
+
+
+class IDR(_Solver):
+    """Right-preconditioned IDR(s), 1 <= s <= 8, on one right-hand side as a device schedule (bis_idr_*): nonsymmetric A,
+    one fixed preconditioner (not checked), short recurrences and no restart; one SpMV, one apply and one history entry per
+    iteration.  The history is the recurrence of the true residual norm.  x is the iterate of the last history entry."""
+
+    _sym = "idr"
+
+    def __init__(self, ctx, A, b, x, s=4):
+        self.ctx, self.s = ctx, int(s)
+        self.h = C.c_void_p()
+        self._keep = (A, b, x)
+        ctx.check(ctx.lib.bis_idr_create(ctx.h, A.h, C.c_void_p(b.ptr), C.c_void_p(x.ptr), C.c_int(self.s), C.byref(self.h)))
+
+    def set_shadow(self, P):
+        """The shadow space: an n x s array (column j is P[:, j]) instead of the hashed default; before init."""
+        P = np.asfortranarray(P, dtype=np.float64)
+        if P.ndim != 2 or P.shape[1] != self.s:
+            raise BisError(f"IDR.set_shadow: P must have {self.s} columns")
+        self.ctx.check(self.ctx.lib.bis_idr_set_shadow(self.ctx.h, self.h, P.ctypes))
+
+    def init(self, tol):
+        r0 = C.c_double()
+        self.ctx.check(self.ctx.lib.bis_idr_init(self.ctx.h, self.h, C.c_double(tol), C.byref(r0)))
+        return r0.value
+
+    def status(self, hist_cap=4096):
+        """(iterations, converged, history[0 .. iterations])"""
+        iters, conv = C.c_int(), C.c_int()
+        hist = np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_idr_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv),
+                                                   hist.ctypes, C.c_int(hist_cap)))
         return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
 
 

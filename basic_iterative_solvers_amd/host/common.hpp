@@ -71,7 +71,9 @@ inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
 inline int &precond_block_size() { static int b = 0; return b; }
 // -fill K: level-of-fill of -p ilu0 / -p ilu0it (bis_mat_iluk); 0, the default, is ILU(0) as it always ran
 inline int &precond_fill_level() { static int k = 0; return k; }
-enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES }; // FGMRES, MINRES: this build's additions (-fgm, -mr)
+// -ids S: the dimension s of the shadow space of -idr (bis_idr_create), 1..8
+inline int &idr_shadow_dim() { static int s = 4; return s; }
+enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR }; // FGMRES, MINRES, IDR: this build's additions (-fgm, -mr, -idr)
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
@@ -88,6 +90,7 @@ inline std::string to_string(PrecondType t) {
 inline std::string to_string(SolverType t) {
     static const char *n[] = {"jacobi", "gauss-seidel", "symmetric-gauss-seidel", "gmres",
                               "conjugate-gradient", "bicgstab", "fgmres", "minres"};
+    if (t == SolverType::IDR) return "idr(" + std::to_string(idr_shadow_dim()) + ")";
     return n[static_cast<int>(t)];
 }
 
@@ -100,6 +103,7 @@ struct Args {
     int pprec = 64;                        // -pprec 32|64 (precond_value_bits())
     int fill_level = 0;                    // -fill K (precond_fill_level())
     bool fill_given = false;
+    bool ids_given = false;                // -ids S (idr_shadow_dim())
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

@@ -1,6 +1,6 @@
 // main.cpp -- CLI driver of the MI355X build; same command line and the same
 // stdout (residual table, summary, timer tree) as the reference's main.cpp.
-//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-bi>
+//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-idr [-ids S]|-bi>
 //        [-p j|gs|bgs|sgs|2st|s2st|ilu0|ilu0it|fsai|mg|bj] [-mg KEY=VALUE,... (nu, cs, limit, levels, scale, omega, coarsening, cycle=v|w|k|kgcr, klev)] [-bs N] [-fill K (level-of-fill of ilu0 / ilu0it, 0..16)] [-inner K] [-pprec 32|64] [-scale 0|1] [-rl N] [-unfused] [-dev K]
 #include <chrono>
 
@@ -10,6 +10,7 @@
 #include "methods/fgmres.hpp"
 #include "methods/gauss_seidel.hpp"
 #include "methods/gmres.hpp"
+#include "methods/idr.hpp"
 #include "methods/jacobi.hpp"
 #include "methods/minres.hpp"
 #include "postprocessing.hpp"
@@ -30,6 +31,7 @@ static void run(Args *cli_args, Timers *timers) {
     case SolverType::BiCGSTAB: solver = new BiCGSTABSolver(cli_args); break;
     case SolverType::FGMRES: solver = new FGMRESSolver(cli_args); break;
     case SolverType::MINRES: solver = new MINRESSolver(cli_args); break;
+    case SolverType::IDR: solver = new IDRSolver(cli_args); break;
     }
     auto A = std::make_unique<MatrixCRS>();
     if (!make_generated_matrix(cli_args->matrix_file_name, A.get())) {

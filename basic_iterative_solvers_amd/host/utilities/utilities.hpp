@@ -12,6 +12,7 @@
 // (or, with `-mg cycle=w|k|kgcr`, one W- or K-cycle) and `-mg key=value,...` sets its parameters; the method `-fgm` is flexible
 // GMRES(m) on the device schedule bis_fgmres_* (methods/fgmres.hpp), which takes every -p type, the K-cycles included; the method
 // `-mr` is MINRES for symmetric, possibly indefinite matrices on the device schedule bis_minres_* (methods/minres.hpp);
+// the method `-idr` is IDR(s) for nonsymmetric matrices on the device schedule bis_idr_* (methods/idr.hpp) and `-ids S` its s (default 4);
 // `-p bj` is block Jacobi (bis_bj_create) on blocks of `-bs N` consecutive rows (default: the dof of the grid hint).
 #pragma once
 
@@ -36,13 +37,15 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     else if (st == "-bi") a->method = SolverType::BiCGSTAB;
     else if (st == "-fgm") a->method = SolverType::FGMRES;
     else if (st == "-mr") a->method = SolverType::MINRES;
+    else if (st == "-idr") a->method = SolverType::IDR;
     else {
         printf("ERROR: parse_cli: Please choose an available solver:"
                "\n-j (Jacobi)\n-gs (Gauss-Seidel)\n-sgs (Symmetric Gauss-Seidel)"
                "\n-gm ([Preconditioned] GMRES)\n-cg ([Preconditioned] Conjugate Gradient)"
                "\n-bi ([Preconditioned] BiCGSTAB)"
                "\n-fgm ([Preconditioned] flexible GMRES, right-preconditioned)"
-               "\n-mr ([Preconditioned] MINRES, symmetric indefinite matrices)\n");
+               "\n-mr ([Preconditioned] MINRES, symmetric indefinite matrices)"
+               "\n-idr ([Preconditioned] IDR(s), nonsymmetric matrices, -ids S = 1..8)\n");
         exit(EXIT_FAILURE);
     }
     for (int i = 3; i < argc; ++i) {
@@ -111,6 +114,16 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             a->fill_given = true;
             precond_fill_level() = k;
         }
+        else if (arg == "-ids" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const int sd = v.find_first_not_of("0123456789") == std::string::npos && !v.empty() && v.size() <= 2 ? atoi(v.c_str()) : 0;
+            if (sd < 1 || sd > 8) {
+                fprintf(stderr, "ERROR: -ids S: the dimension of the shadow space of -idr, 1 <= S <= 8\n");
+                exit(EXIT_FAILURE);
+            }
+            a->ids_given = true;
+            idr_shadow_dim() = sd;
+        }
         else if (arg == "-mg" && i + 1 < argc) {
             bis_mg_params &p = precond_mg_params();
             std::stringstream ss(argv[++i]);
@@ -157,12 +170,14 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else std::cout << "ERROR: assign_cli_inputs: Arguement \"" << arg << "\" not recongnized." << std::endl;
     }
     if (a->preconditioner == PrecondType::MG && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
-        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES) {
+        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES &&
+        a->method != SolverType::IDR) {
         fprintf(stderr, "ERROR: -p mg needs a Krylov method: -cg, -gm or -bi\n");
         exit(EXIT_FAILURE);
     }
     if (a->preconditioner == PrecondType::BlockJacobi && a->method != SolverType::ConjugateGradient && a->method != SolverType::GMRES &&
-        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES) {
+        a->method != SolverType::BiCGSTAB && a->method != SolverType::FGMRES && a->method != SolverType::MINRES &&
+        a->method != SolverType::IDR) {
         fprintf(stderr, "ERROR: -p bj needs a Krylov method: -cg, -gm, -fgm, -mr or -bi\n");
         exit(EXIT_FAILURE);
     }
@@ -181,6 +196,20 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     }
     if (a->method == SolverType::MINRES && (a->unfused || a->host_scalars)) {
         fprintf(stderr, "ERROR: -mr is a device schedule (bis_minres_*) and has no call-by-call form: -unfused and -hostscalars do not apply\n");
+        exit(EXIT_FAILURE);
+    }
+    // IDR(s) assumes one fixed M: its recurrences carry G_k = A M^-1 (...) from cycle to cycle
+    if (a->preconditioner == PrecondType::MG && a->method == SolverType::IDR &&
+        (precond_mg_cycle().cycle == BIS_MG_CYCLE_K || precond_mg_cycle().cycle == BIS_MG_CYCLE_K_GCR)) {
+        fprintf(stderr, "ERROR: -mg cycle=k|kgcr is not a fixed preconditioner, which -idr (IDR(s)) assumes: use -fgm, or cycle=v|w\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->method == SolverType::IDR && (a->unfused || a->host_scalars)) {
+        fprintf(stderr, "ERROR: -idr is a device schedule (bis_idr_*) and has no call-by-call form: -unfused and -hostscalars do not apply\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->ids_given && a->method != SolverType::IDR) {
+        fprintf(stderr, "ERROR: -ids S is the dimension of the shadow space of IDR(s): it needs the method -idr\n");
         exit(EXIT_FAILURE);
     }
     if (a->method == SolverType::FGMRES && (a->unfused || a->host_scalars)) {

@@ -1231,6 +1231,113 @@ BIS_API bis_status bis_minres_status(bis_ctx *ctx, bis_minres *s, int *iters, in
                                      int hist_cap);
 BIS_API bis_status bis_minres_destroy(bis_ctx *ctx, bis_minres *s);
 
+/* ---- IDR(s) on the device (no reference counterpart) ---------------------------
+ * Right-preconditioned IDR(s) with biorthogonalisation (Sonneveld and van Gijzen),
+ * 1 <= s <= 8, for a nonsymmetric A and one right-hand side: short recurrences, no
+ * restart, one SpMV, one preconditioner apply and one history entry per iteration,
+ * 3 s + 3 n-vectors at any iteration count.
+ * State: the n-vectors r, v, t; the column blocks P (the shadow space), G, U of s
+ * n-vectors each; the s x s lower-triangular M; f, c, alpha (s entries each), omega
+ * and ||r||.  One iteration is one position of a cycle of s + 1 positions:
+ *   init:  r = b - A x;  history[0] = ||r||;  threshold = tol history[0];  G = U = 0;
+ *          M = I;  omega = 1;  f = P^T r;  position 0
+ *   position k < s:
+ *     c[k..s):  forward substitution  M[k.., k..] c = f[k..]
+ *     v   = r - sum_{j >= k} c_j G_j
+ *     v^  = M^-1 v                        (bis_apply_preconditioner; v^ is v without one)
+ *     U_k = omega v^ + sum_{j >= k} c_j U_j
+ *     G_k = A U_k                         (bis_spmv)
+ *     q   = P^T G_k                       (s dots in one pass over G_k)
+ *     alpha_i = (q_i - sum_{l < i} M_il alpha_l) / M_ii         for i < k
+ *     M_ik    =  q_i - sum_{l < k} M_il alpha_l                 for i >= k
+ *     G_k -= sum_{i < k} alpha_i G_i;   U_k -= sum_{i < k} alpha_i U_i
+ *     beta = f_k / M_kk;   r -= beta G_k;   x += beta U_k;   f_i -= beta M_ik for i > k
+ *     history[it] = ||r||;  stop test
+ *   position s:
+ *     v^ = M^-1 r;  t = A v^;  tt = (t, t), tr = (t, r);  omega = tr / tt;
+ *     rho = |tr| / (sqrt(tt) ||r||);  if rho < 0.7: omega = omega 0.7 / rho
+ *     x += omega v^;  r -= omega t;  history[it] = ||r||;  stop test;  f = P^T r;
+ *     position 0
+ * The alpha line is the one deliberate change from the published loop, which takes
+ * one dot (p_i, G_k) and updates G_k and U_k once for every i < k in turn.  M is
+ * lower triangular (p_i is orthogonal to G_l for l > i), so every alpha follows from
+ * the ONE multi-dot q by a forward substitution, and the new column of M from the
+ * same q: one reduction pass and one update pass at every k instead of 2 (k - 1).
+ * In exact arithmetic it is the same method; the two forms, restated in numpy, needed
+ * the same number of products to within 3 on the tests' inputs.
+ * The stop test is the other handles': ||r|| < threshold stops the solve as
+ * converged, a non-finite ||r|| as not converged with that value in the history.
+ * The published breakdowns M_kk = 0 and tt = 0 arrive there through beta or omega
+ * (no separate flag).  b = 0 with x0 = 0 stops at iteration 1, not converged (0/0);
+ * A = I converges at iteration 1 with history entry 0.  The history is the
+ * recurrence of the TRUE residual b - A x (right preconditioning), the quantity
+ * bis_fgmres_* records.  M^-1 must be ONE fixed operator: the recurrences assume
+ * G_k = A M^-1 (...) with the same M at every step.  Nothing checks this; an MG
+ * K-cycle (BIS_MG_CYCLE_K, BIS_MG_CYCLE_K_GCR) is not such an operator (use
+ * bis_fgmres_*).
+ * The shadow space: P[i][j] = (h + 0.5) 2^-31 - 1 for row i, column j, with
+ * h = hash32(hash32(i) ^ ((j + 1) 0x9e3779b9 mod 2^32)) and the hash32 of the MIS key
+ * above: uniform in (-1, 1), exact in fp64, the same on every device and host, not
+ * orthonormalised.  bis_idr_set_shadow replaces it by the caller's n x s matrix
+ * P_host (HOST memory, column-major, leading dimension n); the call blocks and
+ * copies, and is refused (BIS_ERR_INVALID) once bis_idr_init has run.
+ * Schedule at a position k < s, beside the SpMV and the apply: the pass for v (with
+ * U_k in the same pass where there is no preconditioner), the pass for U_k, the
+ * multi-dot q with s accumulators per lane, whose last workgroup does the alpha / M /
+ * beta / f lines in one lane, and the update of G_k, U_k, r and x with the partial
+ * sums of (r, r) fused, whose last workgroup writes the history, does the stop test
+ * and computes the next c.  Position s: one pass for (tt, tr), whose last workgroup
+ * computes omega, and the update of x and r with (r, r) and f = P^T r fused.  All on
+ * 16-byte accesses with a scalar path for an odd tail; every "vector -+ scalar *
+ * vector" is one fma per element, sums over columns run over ascending column index,
+ * the small algebra rounds every operation separately.  A position k < s moves
+ * 3 s + 13 vectors, 24 s + 104 bytes per row whatever k is (200 at s = 4, against
+ * 56 + 32 n of bis_fgmres_* at position n); position s moves s + 8.  4 s + 3 launches
+ * per cycle without a preconditioner, 5 s + 3 and the applies' own with one.  The
+ * reductions go by per-workgroup partial sums that the workgroup arriving last adds
+ * in index order (no floating-point atomics, no waiting; the grid depends on n
+ * only): two runs give the same bits.  Scalars, M, the history and the stop flag
+ * stay on the device; bis_idr_iterate reads nothing back and knows the cycle
+ * position from the number of iterations enqueued, which persists across calls.
+ * After the stop every launch of the schedule returns at once, so no later call
+ * changes x, the history or the status, and x is the iterate the last history entry
+ * belongs to (launches of the preconditioner queued behind the stop may still run;
+ * nothing reads their results).
+ * Memory: (3 s + 3) n doubles (n rounded up to even: every column starts on 16 bytes
+ * and is an SpMV operand), 96 doubles of state and the history, plus the
+ * preconditioner's scratch (SGS, ILU0, FSAI: one n-vector; the two-stage types and
+ * ILU0_ITER: two; MG, block Jacobi: the handle's own).
+ * bis_idr_set_preconditioner takes the arguments of bis_fgmres_set_preconditioner:
+ * every type, outer_iters and inner_iters that bis_apply_preconditioner takes for
+ * one vector, BIS_PC_MG and BIS_PC_BLOCK_JACOBI (the operand in L_strict) included.
+ * Call it before bis_idr_init.
+ * Errors: null arguments, s outside 1 .. 8, a non-square A, b or x off a 16-byte
+ * boundary, set_preconditioner or set_shadow after init, a missing operand, an MG
+ * operand of another size: BIS_ERR_INVALID; MG with outer_iters != 1:
+ * BIS_ERR_UNSUPPORTED; n = 0: BIS_OK, nothing is launched; *out is written on
+ * success only. */
+typedef struct bis_idr bis_idr;
+BIS_API bis_status bis_idr_create(bis_ctx *ctx, const bis_mat *A, const double *b, double *x, int s, bis_idr **out);
+BIS_API bis_status bis_idr_set_preconditioner(bis_ctx *ctx, bis_idr *h, int precond_type,
+                                              const bis_mat *L_strict, const bis_mat *U_strict,
+                                              const double *A_D, const double *A_D_inv,
+                                              const double *L_D, const double *U_D,
+                                              int outer_iters, int inner_iters);
+/* blocking: P = P_host (n x s, column-major, leading dimension n); before bis_idr_init */
+BIS_API bis_status bis_idr_set_shadow(bis_ctx *ctx, bis_idr *h, const double *P_host);
+/* Reuse: bis_idr_init may be called again at any time, inside a cycle as well.  It reads b and x as they are at that
+ * call and discards every earlier state: the position starts at 0 again, G and U are zero, M = I, omega = 1, the count,
+ * the history and the flags are dropped, NaN included; P stays.  The solve that follows is, bit for bit, that of a new
+ * handle.  bis_idr_set_preconditioner and bis_idr_set_shadow stay refused (BIS_ERR_INVALID) once bis_idr_init has run. */
+/* blocking; r0_norm_host (may be NULL) receives ||b - A x0||_2 */
+BIS_API bis_status bis_idr_init(bis_ctx *ctx, bis_idr *h, double tol, double *r0_norm_host);
+/* non-blocking: enqueues n_iters iterations; the cycle position persists across calls */
+BIS_API bis_status bis_idr_iterate(bis_ctx *ctx, bis_idr *h, int n_iters);
+/* blocking: iterations, converged flag, history entries 0 .. iterations (at most hist_cap of them; may be NULL) */
+BIS_API bis_status bis_idr_status(bis_ctx *ctx, bis_idr *h, int *iters, int *converged, double *hist_host,
+                                  int hist_cap);
+BIS_API bis_status bis_idr_destroy(bis_ctx *ctx, bis_idr *h);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
