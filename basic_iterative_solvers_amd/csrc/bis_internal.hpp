@@ -122,7 +122,8 @@ struct bis_options {
     int spmv_colslab = -1;     // column slabs for matrices without locality (bis_spmv_slab.hip): 0 never, -1 where a build-time trial measures them faster, k >= 2: k slabs wherever the plan applies (tests)
     int spmv_win8 = -1;        // window + sliced-ELL SpMV with the 8-byte values streamed (matrices without a dictionary form, or with spmv_valdict = 0): 0 off, 1 on where its plan applies (-1: default = on)
     int spmv_win8_rows = -1;   // ... rows per lane: 1, 2 or 4 (blocks of 256, 512, 1024 rows; default 2)
-    int spmv_win8_depth = -1;  // ... chunks requested ahead per lane: 1, 2, 3, 4 or 6 (default by block size)
+    int spmv_win8_depth = -1;  // ... chunks requested ahead per lane: 1, 2, 3, 4 or 6 (default 3; 2 for 256-row blocks)
+    int spmv_win8_sets = -1;   // ... register sets of the chunk ring: 1 = one set, drained once per round, 2 = two sets, never drained (depths 1-4; default by measurement, bis_spmv_win8_launch)
     int spmv_win8_implicit = -1; // ... implied window slots in the slices of a stencil (0: every chunk keeps its slots; default on where >= half the chunks qualify)
     int spmv_win8_tune = -1;   // ... placement tuning of the stream at build time: up to k re-allocations, the fastest kept (default 12 for streams of >= 1 GiB; 0 off)
     int spmv_win4 = -1;        // ... the same form with 4-byte values for a matrix that bis_mat_round_f32 flagged ("win4"): 0 off (such a matrix then streams win8), -1: default = on

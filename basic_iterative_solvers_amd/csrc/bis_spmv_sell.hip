@@ -1590,7 +1590,8 @@ __device__ __forceinline__ void w8_consume(const unsigned char *win, const W8Chu
 // IMPL: the implied-slot layout (w8_fill_kernel PHASE 2): a chunk's 8 slot bytes per lane come from desc[chunk] (the same 8 bytes
 // for every lane: implicit slice) or from its record in side (explicit slice), chosen per chunk by its slice (wave-uniform).
 // VT: the stream's value type, double, or float for win4 (chunks of 1536 / 1024 bytes, everything else the same).
-template <int MODE, int R, int D, bool IMPL, typename VT = double>
+// TWO: the ring has two register sets (see the walk below); false: one set, whose loads the compiler drains once per round.
+template <int MODE, int R, int D, bool IMPL, typename VT = double, bool TWO = false>
 __global__ __launch_bounds__(256) void spmv_win8_kernel(
     const double *x, double *__restrict__ y, int64_t n_rows, int64_t n_cols, int n_blocks, int remap_arg, const double *w,
     double *__restrict__ partials, const int *stop, const int32_t *__restrict__ hdr, const int64_t *__restrict__ slice_chunk0,
@@ -1710,22 +1711,60 @@ __global__ __launch_bounds__(256) void spmv_win8_kernel(
             if (IMPL) cur_off = off2[rr + 1 < R ? rr + 1 : R - 1];                         \
         }
     W8_END_SLICES()
-    while (c < C1) { // (wave-uniform)
+    // one step of the walk: chunk c is taken from FROM, chunk c + D is requested INTO, chunk c is summed
+#define W8_STEP(FROM, INTO)                                                                \
+    {                                                                                      \
+        W8Chunk<VT> cur = FROM;                                                            \
+        INTO = load(min(c + D, c_last));                                                   \
+        if (IMPL) {                                                                        \
+            cur.code.x = w8_imply(cur.code.x, cur_off);                                    \
+            cur.code.y = w8_imply(cur.code.y, cur_off);                                    \
+        }                                                                                  \
+        w8_consume(lds, cur, acc);                                                         \
+        ++c;                                                                               \
+        W8_END_SLICES()                                                                    \
+    }
+    // the last steps of a wave, fewer than D: nothing is left to request
+#define W8_TAIL(FROM)                                                                      \
+    _Pragma("unroll") for (int d = 0; d < D - 1; ++d)                                      \
+        if (c < C1) {                                                                      \
+            W8Chunk<VT> cur = FROM[d];                                                     \
+            if (IMPL) {                                                                    \
+                cur.code.x = w8_imply(cur.code.x, cur_off);                                \
+                cur.code.y = w8_imply(cur.code.y, cur_off);                                \
+            }                                                                              \
+            w8_consume(lds, cur, acc);                                                     \
+            ++c;                                                                           \
+            W8_END_SLICES()                                                                \
+        }
+    if constexpr (TWO) {
+        // two register sets: a round takes its chunks from one set and requests the chunks of the next round into the OTHER, so no
+        // step writes a register that holds a chunk still to be summed, the loop's back edge carries no copy of a loaded value,
+        // and the only waits in the loop are counted ones that leave the youngest D chunks' loads in flight
+        W8Chunk<VT> ring2[D];
+        while (c + 2 * D <= C1) { // (wave-uniform) two whole rounds per trip, no guard inside
 #pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (c < C1) {
-                W8Chunk<VT> cur = ring[d];
-                ring[d] = load(min(c + D, c_last));
-                if (IMPL) {
-                    cur.code.x = w8_imply(cur.code.x, cur_off);
-                    cur.code.y = w8_imply(cur.code.y, cur_off);
-                }
-                w8_consume(lds, cur, acc);
-                ++c;
-                W8_END_SLICES()
+            for (int d = 0; d < D; ++d) W8_STEP(ring[d], ring2[d])
+#pragma unroll
+            for (int d = 0; d < D; ++d) W8_STEP(ring2[d], ring[d])
+        }
+        if (c + D <= C1) { // at most one more whole round, then fewer than D chunks, already requested
+#pragma unroll
+            for (int d = 0; d < D; ++d) W8_STEP(ring[d], ring2[d])
+            W8_TAIL(ring2)
+        } else {
+            W8_TAIL(ring)
+        }
+    } else {
+        while (c < C1) { // (wave-uniform)
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                if (c < C1) W8_STEP(ring[d], ring[d])
             }
         }
     }
+#undef W8_TAIL
+#undef W8_STEP
 #undef W8_END_SLICES
     if (MODE == 1) {
         const double t = wave_sum(dot_acc);
@@ -1789,17 +1828,19 @@ size_t bis_spmv_win8_stream_bytes(const bis_mat *A, int vb) {
 
 // the placement searches' test for the fast level of the stream's placement, priced on the bytes a launch moves (the same
 // measure for both layouts): the form's own arrays, the x granules copied into the blocks' windows, y.  HPCG-256 moves 5.43 GB
-// in today's layout (plain product: fast level 0.755-0.79 ms = 6.9-7.2 TB/s, slow 0.855-0.89 ms = 6.1-6.35) and 4.59 GB with implied
-// slots (fused product, as the search times it there: 0.664-0.688 ms = 6.7-6.9 TB/s on good allocations, 0.81 ms on bad ones);
-// 6.6 TB/s lies between the levels of either.  (The 4-byte stream is held to the same rate on its own, smaller, byte count: whether
-// it reaches that rate has not been measured -- docs/EXPERIMENTS.md section 23 -- and no other threshold is invented for it.)
+// in today's layout and 4.59 GB with implied slots, where the search times the fused product.  With the two-set chunk ring
+// (docs/EXPERIMENTS.md section 32) the first allocations of eight processes gave 0.639-0.655 ms = 7.0-7.2 TB/s (the fast level),
+// 0.693 ms = 6.63 TB/s and 0.72-0.79 ms; the explicit layout's plain product 0.755-0.79 ms = 6.9-7.2 TB/s against 0.855-0.89 ms.
+// 6.85 TB/s (0.671 ms with implied slots) lies between the fast level and the next one of either.  (The 4-byte stream is held to
+// the same rate on its own, smaller, byte count: whether it reaches that rate has not been measured -- docs/EXPERIMENTS.md
+// section 23 -- and no other threshold is invented for it.)
 double bis_spmv_win8_moved_bytes(const bis_mat *A, int vb) {
     const bis_sellwin *sw = w8_get(A, vb);
     if (!sw) return 0.0;
     return (double)bis_spmv_win8_bytes(A, vb) + 64.0 * (double)sw->win_gran_sum + 8.0 * (double)A->n_rows;
 }
 bool bis_spmv_win8_fast(const bis_mat *A, double ms, int vb) {
-    return w8_get(A, vb) && ms > 0.0 && bis_spmv_win8_moved_bytes(A, vb) / (ms * 1e-3) >= 6.6e12;
+    return w8_get(A, vb) && ms > 0.0 && bis_spmv_win8_moved_bytes(A, vb) / (ms * 1e-3) >= 6.85e12;
 }
 void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream, int vb) {
     bis_sellwin *sw = w8_ptr(A, vb);
@@ -2064,14 +2105,21 @@ bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
     const size_t lds = (size_t)(2 + 8 * sw->max_gran) * 8;
     const unsigned char *stream = reinterpret_cast<const unsigned char *>(sw->codes);
     const int32_t *own = (mode == 1 && w == x + A->view_row0 && x_al16) ? sw->own_rank : nullptr; // the fused dot's w is x itself (CG: p)
-    // chunks requested ahead per lane.  1024-row blocks: 1 where the slices are uniform (HPCG-256 in the CG loop 0.758 ms; 2: 0.771,
-    // 3: 0.764; HPCG-512 6.16 / 6.70 / 6.38), 2 with ragged rows (fem:80,80,81: 0.211 ms; 1: 0.221, 3: 0.221); 512-row blocks: 3
-    // (HPCG-256 0.861; 2: 0.945, 4: 1.030).  The waves of the other workgroups on the CU cover the rest of the latency.
+    // The chunk ring.  Two register sets (spmv_win8_sets, default 2; depths 1-4): the loop never drains the loads it has issued, so
+    // `depth` chunks per lane stay in flight at every wait; one set: the ring is drained once per round.  Chunks requested ahead
+    // per lane (spmv_win8_depth), by measurement in the CG loop (docs/EXPERIMENTS.md section 32), two sets: 3 for 512- and
+    // 1024-row blocks (HPCG-256 0.673-0.778 ms by placement, one set at its best depth 0.767-0.812; HPCG-512 5.16 against 5.30;
+    // fem:80,80,80 0.177 against 0.184; win4 HPCG-256 0.439 against 0.459), 2 for 256-row blocks, whose occupancy the VGPRs bound
+    // (HPCG-256 0.758 ms; 3: 0.808; one set 0.826).  One set (spmv_win8_sets = 1) keeps its earlier rule: 1024-row blocks 1 where
+    // the slices are uniform, 2 with ragged rows, smaller blocks 3.
     const bool ragged = (double)sw->total_chunks * 256.0 > 1.08 * (double)A->nnz;
-    const int depth = bis_opts().spmv_win8_depth > 0 ? bis_opts().spmv_win8_depth : (sw->R == 4 ? (ragged ? 2 : 1) : 3);
+    const bool two = bis_opts().spmv_win8_sets > 0 ? bis_opts().spmv_win8_sets >= 2 : true;
+    const int depth = bis_opts().spmv_win8_depth > 0 ? bis_opts().spmv_win8_depth
+                      : two ? (sw->R == 1 ? 2 : 3) : (sw->R == 4 ? (ragged ? 2 : 1) : 3);
 #define W8_L3(MODE, RR, DD) do { if (sw->slice_rec) W8_L5(MODE, RR, DD, true); else W8_L5(MODE, RR, DD, false); } while (0)
-#define W8_L5(MODE, RR, DD, IMPL) do { if (vb == 4) W8_L4(MODE, RR, DD, IMPL, float); else W8_L4(MODE, RR, DD, IMPL, double); } while (0)
-#define W8_L4(MODE, RR, DD, IMPL, VT) hipLaunchKernelGGL((spmv_win8_kernel<MODE, RR, DD, IMPL, VT>), dim3(grid), dim3(256), lds, ctx->stream, x, y, A->n_rows, A->n_cols, \
+#define W8_L5(MODE, RR, DD, IMPL) do { if (vb == 4) W8_L6(MODE, RR, DD, IMPL, float); else W8_L6(MODE, RR, DD, IMPL, double); } while (0)
+#define W8_L6(MODE, RR, DD, IMPL, VT) do { if (two && DD <= 4) W8_L4(MODE, RR, DD, IMPL, VT, (DD <= 4)); else W8_L4(MODE, RR, DD, IMPL, VT, false); } while (0)
+#define W8_L4(MODE, RR, DD, IMPL, VT, TWO) hipLaunchKernelGGL((spmv_win8_kernel<MODE, RR, DD, IMPL, VT, TWO>), dim3(grid), dim3(256), lds, ctx->stream, x, y, A->n_rows, A->n_cols, \
                                                sw->n_blocks, remap_arg, w, partials, stop, sw->hdr, sw->slice_chunk0, stream, x_al16, own, sw->row_of, \
                                                reinterpret_cast<const w8_v2u *>(stream + sw->w8_desc), stream + sw->w8_side, sw->slice_rec)
 #define W8_L2(MODE, RR) do { if (depth <= 1) W8_L3(MODE, RR, 1); else if (depth == 2) W8_L3(MODE, RR, 2); else if (depth == 3) W8_L3(MODE, RR, 3); else if (depth <= 5) W8_L3(MODE, RR, 4); else W8_L3(MODE, RR, 6); } while (0)
@@ -2082,6 +2130,7 @@ bis_status bis_spmv_win8_launch(bis_ctx *ctx, const bis_mat *A, const double *x,
 #undef W8_L3
 #undef W8_L4
 #undef W8_L5
+#undef W8_L6
     BIS_HIP_CHECK(ctx, hipGetLastError());
     return BIS_OK;
 }
