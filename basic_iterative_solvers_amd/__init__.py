@@ -44,7 +44,10 @@ def load_library():
         _lib.bis_mat_sweepm_kernel.restype = C.c_char_p
         _lib.bis_mat_fsai_kernel.restype = C.c_char_p
         _lib.bis_mat_iluk_kernel.restype = C.c_char_p
+        _lib.bis_spgemm_kernel.restype = C.c_char_p
         _lib.bis_mg_operand.restype = C.c_void_p
+        _lib.bis_mg_level_prolongator.restype = C.c_void_p
+        _lib.bis_mg_level_restrictor.restype = C.c_void_p
         _lib.bis_mg_level_matrix.restype = C.c_void_p
         _lib.bis_bj_operand.restype = C.c_void_p
     return _lib
@@ -60,6 +63,15 @@ def iluk_limits():
     ml, mv = C.c_int(), C.c_int()
     load_library().bis_iluk_limits(C.byref(ml), C.byref(mv))
     return ml.value, mv.value
+
+
+def spgemm_limits():
+    """dict(wave_cap, row_cap, row_cap_max, batch) of Context.spgemm (bis_spgemm_limits): the products per row up to which
+    one wave / the row path takes a row (row_cap is the default of option spgemm_row_cap, row_cap_max its largest
+    value), and the default of option spgemm_batch."""
+    w, r, m, b = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+    load_library().bis_spgemm_limits(C.byref(w), C.byref(r), C.byref(m), C.byref(b))
+    return dict(wave_cap=w.value, row_cap=r.value, row_cap_max=m.value, batch=b.value)
 
 
 class Context:
@@ -278,12 +290,19 @@ class Context:
         self.check(self.lib.bis_mat_fsai(self.h, A.h, C.byref(hg), C.byref(hgt), C.byref(nf)))
         return Mat(self, hg), Mat(self, hgt), nf.value
 
-    def mg(self, A, cycle=None, cycle_levels=0, **params):
+    def spgemm(self, A, B):
+        """C = A B as a new Mat (bis_spgemm); Mat.spgemm_kernel() names the path that made it."""
+        h = C.c_void_p()
+        self.check(self.lib.bis_spgemm(self.h, A.h, B.h, C.byref(h)))
+        return Mat(self, h)
+
+    def mg(self, A, cycle=None, cycle_levels=0, smooth=False, prolong_omega=0.0, **params):
         """The aggregation multigrid hierarchy of A (bis_mg_create): an MG object.  Parameters: max_levels, coarse_limit,
         coarsening (0 / "auto", 1 / "grid", 2 / "mis"), nu, coarse_sweeps, omega, coarse_scale.  `cycle` (0 / "v", 1 / "w",
         2 / "k", 3 / "kgcr") and `cycle_levels` go to MG.set_cycle after creation; without `cycle` the hierarchy stays V.
+        `smooth` builds smoothed aggregation (bis_mg_create_smoothed) with the factor `prolong_omega` (0: 4/3).
         Preconditioner "mg" takes Ls=MG.operand."""
-        m = MG(self, A, **params)
+        m = MG(self, A, smooth=smooth, prolong_omega=prolong_omega, **params)
         if cycle is not None:
             try:
                 m.set_cycle(cycle, cycle_levels)
@@ -587,6 +606,17 @@ class Mat:
         "itrsv spmv+epilogue form=F"."""
         return self.ctx.lib.bis_itrsv_kernel(self.h).decode()
 
+    def spgemm_kernel(self):
+        """The path(s) of bis_spgemm that made this product: "spgemm_row_kernel", "spgemm_sort_fallback" or both
+        (bis_spgemm_kernel); "" for other matrices."""
+        return self.ctx.lib.bis_spgemm_kernel(self.h).decode()
+
+    def transpose(self):
+        """A^T as a new Mat (bis_mat_transpose)."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.bis_mat_transpose(self.ctx.h, self.h, C.byref(h)))
+        return Mat(self.ctx, h)
+
     def round_f32(self):
         """Round every value to fp32 in place in the fp64 CRS array and flag the matrix fp32-exact (bis_mat_round_f32): its SpMV
         may then stream 4-byte values (form 8).  Returns the largest relative change of a value."""
@@ -634,12 +664,19 @@ class MG:
     COARSENING = dict(auto=0, grid=1, mis=2)
     CYCLE = dict(v=0, w=1, k=2, kgcr=3)
 
-    def __init__(self, ctx, A, max_levels=10, coarse_limit=256, coarsening=0, nu=1, coarse_sweeps=4, omega=0.0, coarse_scale=1.0):
+    def __init__(self, ctx, A, max_levels=10, coarse_limit=256, coarsening=0, nu=1, coarse_sweeps=4, omega=0.0, coarse_scale=1.0,
+                 smooth=False, prolong_omega=0.0):
         self.ctx, self._keep = ctx, A
         self.h = C.c_void_p()
+        self.smoothed = bool(smooth)
         p = MGParams(int(max_levels), int(coarse_limit), int(self.COARSENING.get(coarsening, coarsening)), int(nu),
                      int(coarse_sweeps), float(omega), float(coarse_scale))
-        ctx.check(ctx.lib.bis_mg_create(ctx.h, A.h, C.byref(p), C.byref(self.h)))
+        if self.smoothed:
+            ctx.check(ctx.lib.bis_mg_create_smoothed(ctx.h, A.h, C.byref(p), C.c_double(float(prolong_omega)), C.byref(self.h)))
+        else:
+            if prolong_omega:
+                raise BisError("MG: prolong_omega needs smooth=True")
+            ctx.check(ctx.lib.bis_mg_create(ctx.h, A.h, C.byref(p), C.byref(self.h)))
         n = C.c_int()
         rows, nnz, kinds = (C.c_int64 * 16)(), (C.c_int64 * 16)(), (C.c_int * 16)()
         ctx.lib.bis_mg_info(self.h, C.byref(n), rows, nnz, kinds)
@@ -653,6 +690,22 @@ class MG:
         if not h:
             raise BisError(f"MG.level_matrix: no level {l}")
         return Mat(self.ctx, C.c_void_p(h))
+
+    def prolongator(self, l):
+        """P of the transition from level l as a Mat the hierarchy owns (bis_mg_level_prolongator); None on the coarsest
+        level and on a hierarchy without smoothed prolongators."""
+        h = self.ctx.lib.bis_mg_level_prolongator(self.h, C.c_int(int(l)))
+        return Mat(self.ctx, C.c_void_p(h)) if h else None
+
+    def restrictor(self, l):
+        """R = P^T of the transition from level l, like prolongator (bis_mg_level_restrictor)."""
+        h = self.ctx.lib.bis_mg_level_restrictor(self.h, C.c_int(int(l)))
+        return Mat(self.ctx, C.c_void_p(h)) if h else None
+
+    def prolong_omega(self, l):
+        """omega_l of the transition from level l (bis_mg_level_prolong_omega); None where there is no prolongator."""
+        w = C.c_double()
+        return w.value if self.ctx.lib.bis_mg_level_prolong_omega(self.h, C.c_int(int(l)), C.byref(w)) == 0 else None
 
     def aggregates(self, l):
         """agg[i] of every row of level l (numpy int32); the coarsest level has none."""

@@ -131,6 +131,8 @@ struct bis_options {
     int device_share = -1;  // k > 1: this device is shared by k processes that all run persistent grids (several ranks on one GPU in a test
                             // or rehearsal): kernels that need their whole grid resident keep to 1/k of the device
     int trsm_form = -1;     // multi-vector sweeps (bis_sptrsm.hip): -1 / 0 by level count, 1 = a launch per level at any level count, 2 = the persistent wave-per-row kernel at any level count
+    int spgemm_row_cap = -1;   // bis_spgemm: products per row up to which the row path (candidate columns sorted in LDS) is used; 0: every row takes the sort fallback (default and most: 4096)
+    int spgemm_batch = -1;     // bis_spgemm: products per batch of the sort fallback (default 2^26)
     int trsv_inject_oom = -1;  // test hook: 1 makes the tiled sweep's device plan run out of memory
     int trsv_inject_loss = -1; // test hook: k > 0 makes row k-1 of the next natural-order sweep wait for a result nobody publishes
 };
@@ -229,6 +231,7 @@ struct bis_mat {
     const char *itrsv_kernel = "";          // the path the last step of bis_itrsv took on this triangle (bis_itrsv_kernel)
     const char *spmm_kernel = "";           // the path and template instance the last bis_spmm on this matrix launched (bis_mat_spmm_kernel)
     const char *iluk_kernel = "";           // the symbolic search that made this ILU(k) pattern or L factor, k >= 1 (bis_mat_iluk_kernel)
+    const char *spgemm_kernel = "";         // the path(s) of bis_spgemm that made this product (bis_spgemm_kernel)
     const char *fsai_kernel = "";           // the instance of fsai_rows_kernel that computed this FSAI factor G (bis_mat_fsai_kernel)
     struct bis_mg *mg = nullptr;            // the hierarchy this matrix is the preconditioner operand of (bis_mg_operand): an n x n matrix without
                                             // entries that the hierarchy owns; bis_mat_destroy leaves it alone
@@ -278,6 +281,15 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
+}
+
+// a b rounded on its own.  __dmul_rn is a plain `*` in this toolchain's headers and the default contraction mode fuses it
+// into a following addition (pragmas notwithstanding); a value that went through an opaque register cannot be fused.  For
+// results that are promised bit for bit against "product rounded, then sum rounded".
+__device__ __forceinline__ double bis_mul_sep(double a, double b) {
+    double p = a * b;
+    asm volatile("" : "+v"(p));
+    return p;
 }
 
 // Block sum for blockDim.x == T (multiple of 64). Result valid in thread 0.

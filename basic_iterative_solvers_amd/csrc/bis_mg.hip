@@ -8,6 +8,11 @@
 // then one lane per coarse entry sums its run left to right.  No floating-point atomics and no inter-workgroup waits: two
 // calls give the same bits.
 //
+// Smoothed aggregation (bis_mg_create_smoothed): the same levels, aggregates and weights, but every transition gets a
+// Jacobi-smoothed prolongator P = T - omega_l D^-1 A T (Q = A T by bis_spgemm, then P from Q in place), R = P^T
+// (bis_mat_transpose) and the Galerkin operator R (A P) by two more products; the cycle then restricts with a wave per row
+// of R and prolongs with a lane per row of P.
+//
 // Apply (bis_mg_apply, stream-ordered, allocates nothing): per level bis_spmv and three streaming kernels -- relax
 // (x += w o (b - y), and its from-zero form x = w o b), restrict (r_c[I] = sum over the members of b_i - y_i, a lane per
 // aggregate) and prolong (x_i += scale e_c[agg[i]]).  Products, subtractions and additions are rounded separately.
@@ -38,10 +43,15 @@ struct bis_mg_level {
     double *x = nullptr, *b = nullptr, *y = nullptr; // cycle scratch; level 0 owns y only (x, b are the caller's vectors)
     // the coarse level of a W or K transition only (bis_mg_set_cycle): kr = r_2 or r~, kd = e_2 or d, kv = v (K; w lives in y)
     double *kr = nullptr, *kd = nullptr, *kv = nullptr;
+    // a smoothed hierarchy only (bis_mg_create_smoothed): the transfer operators towards the next level and their omega_l
+    bis_mat *P = nullptr, *R = nullptr;
+    double pomega = 0.0;
 };
 
 struct bis_mg {
     bis_mg_params p;
+    bool smoothed = false;      // bis_mg_create_smoothed made it
+    double prolong_omega = 0.0; // ... with this factor (4/3 for the caller's 0)
     std::vector<bis_mg_level> lv;
     bis_mat *operand = nullptr;
     double *b0 = nullptr; // level 0: the copy of the right-hand side when out aliases in
@@ -158,6 +168,46 @@ __global__ __launch_bounds__(kMgT) void mg_prolong_kernel(double *x, const int32
         if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = __dadd_rn(x[n - 1], __dmul_rn(scale, ec[agg[n - 1]]));
     } else {
         for (; i < n; i += stride) x[i] = __dadd_rn(__builtin_nontemporal_load(x + i), __dmul_rn(scale, ec[agg[i]]));
+    }
+}
+
+// ---- the transfers of a smoothed hierarchy ----------------------------------------------------------------------------
+__device__ __forceinline__ int64_t mg_rp_at(const void *rp, int w64, int64_t i) {
+    return w64 ? static_cast<const int64_t *>(rp)[i] : (int64_t) static_cast<const int32_t *>(rp)[i];
+}
+
+// r_c[I] = sum over row I of R of R_t (b - y)_{col t}: a wave per row.  Lane q sums the products at q, q + 64, ... in that
+// order from 0; the 64 sums are added lane q + 32 to lane q, then + 16, ..., + 1.  b and y are read directly: nothing is
+// materialised between the SpMV and this pass.
+__global__ __launch_bounds__(kMgT) void mg_restrict_sa_kernel(const void *rp, int w64, const int32_t *__restrict__ col, const double *__restrict__ val,
+                                                              const double *__restrict__ b, const double *__restrict__ y, double *__restrict__ rc,
+                                                              int64_t nc) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (kMgT / 64);
+    for (int64_t I = (int64_t)blockIdx.x * (kMgT / 64) + (threadIdx.x >> 6); I < nc; I += waves) {
+        double acc = 0.0;
+        for (int64_t t = mg_rp_at(rp, w64, I) + lane, e = mg_rp_at(rp, w64, I + 1); t < e; t += 64) {
+            const int32_t c = __builtin_nontemporal_load(col + t);
+            acc = __dadd_rn(acc, bis_mul_sep(__builtin_nontemporal_load(val + t), __dsub_rn(b[c], y[c])));
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc = __dadd_rn(acc, __shfl_down(acc, off, 64));
+        if (lane == 0) rc[I] = acc;
+    }
+}
+
+// x_i += scale (sum over row i of P of P_t e_c[col t]): a lane per row (the rows are short), left to right, the first
+// product starting the sum; then the product with scale and the sum with x_i, each rounded
+__global__ __launch_bounds__(kMgT) void mg_prolong_sa_kernel(double *x, const void *rp, int w64, const int32_t *__restrict__ col,
+                                                             const double *__restrict__ val, const double *__restrict__ ec, double scale, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        const int64_t s = mg_rp_at(rp, w64, i), e = mg_rp_at(rp, w64, i + 1);
+        if (s == e) continue;
+        double acc = bis_mul_sep(__builtin_nontemporal_load(val + s), ec[__builtin_nontemporal_load(col + s)]);
+        for (int64_t t = s + 1; t < e; ++t)
+            acc = __dadd_rn(acc, bis_mul_sep(__builtin_nontemporal_load(val + t), ec[__builtin_nontemporal_load(col + t)]));
+        x[i] = __dadd_rn(x[i], bis_mul_sep(scale, acc));
     }
 }
 
@@ -533,6 +583,44 @@ __global__ __launch_bounds__(kMgT) void mg_run_sum_kernel(const double *__restri
     }
 }
 
+// smoothed aggregation: d_i = the first diagonal entry of row i, q_i = (sum_j |a_ij|, left to right from 0) / |d_i|
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_rho_kernel(const RP *__restrict__ rp, const int32_t *__restrict__ col, const double *__restrict__ val,
+                                                      int64_t n, double *d, double *q) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        double sum = 0.0, dii = 0.0;
+        bool have = false;
+        for (int64_t k = (int64_t)rp[i], e = (int64_t)rp[i + 1]; k < e; ++k) {
+            const double a = val[k];
+            sum = __dadd_rn(sum, fabs(a));
+            if (!have && (int64_t)col[k] == i) { dii = a; have = true; }
+        }
+        d[i] = dii;
+        q[i] = __ddiv_rn(sum, fabs(dii)); // (the weights' pass refused a row without a diagonal entry, or with a zero there)
+    }
+}
+// T: row i holds the one entry (agg[i], 1)
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_tentative_kernel(const int32_t *__restrict__ agg, int64_t n, RP *rp, int32_t *col, double *val) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i <= n; i += stride) {
+        rp[i] = (RP)i;
+        if (i < n) { col[i] = agg[i]; val[i] = 1.0; }
+    }
+}
+// Q = A T becomes P in place: p_iJ = t_iJ - c_i q_iJ, c_i = omega_l / a_ii
+__global__ __launch_bounds__(kMgT) void mg_smooth_p_kernel(const void *rp, int w64, const int32_t *__restrict__ col, double *val,
+                                                           const int32_t *__restrict__ agg, const double *__restrict__ d, double omega_l, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        const double c = __ddiv_rn(omega_l, d[i]);
+        const int32_t mine = agg[i];
+        for (int64_t k = mg_rp_at(rp, w64, i), e = mg_rp_at(rp, w64, i + 1); k < e; ++k)
+            val[k] = __dsub_rn(col[k] == mine ? 1.0 : 0.0, bis_mul_sep(c, val[k]));
+    }
+}
+
 struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { hipFree(p); }
@@ -690,10 +778,65 @@ bis_status galerkin(bis_ctx *ctx, const bis_mg_level &L, bis_mat **out) {
     return BIS_OK;
 }
 
+struct MatHold { // destroys the matrix unless it was handed on
+    bis_ctx *ctx;
+    bis_mat *m = nullptr;
+    ~MatHold() { if (m) { hipStreamSynchronize(ctx->stream); bis_mat_destroy(ctx, m); } }
+    bis_mat *release() { bis_mat *r = m; m = nullptr; return r; }
+};
+
+// the transition of level L of a smoothed hierarchy: omega_l, P and R into L, the Galerkin operator R (A P) into *out
+template <typename RP>
+bis_status smoothed_transition(bis_ctx *ctx, double prolong_omega, bis_mg_level &L, bis_mat **out) {
+    const int64_t n = L.n, nc = L.n_coarse;
+    DevBuf d, q, red, tmp;
+    MG_CHECK(d.alloc(8 * (size_t)n));
+    MG_CHECK(q.alloc(8 * (size_t)n));
+    MG_CHECK(red.alloc(8));
+    hipLaunchKernelGGL(mg_rho_kernel<RP>, dim3(mg_grid(n)), dim3(kMgT), 0, ctx->stream, (const RP *)L.A->row_ptr, L.A->col, L.A->val, n,
+                       d.as<double>(), q.as<double>());
+    MG_CHECK(hipGetLastError());
+    size_t bytes = 0;
+    MG_CHECK(rocprim::reduce(nullptr, bytes, q.as<double>(), red.as<double>(), 0.0, (size_t)n, rocprim::maximum<double>(), ctx->stream));
+    MG_CHECK(tmp.alloc(bytes));
+    MG_CHECK(rocprim::reduce(tmp.p, bytes, q.as<double>(), red.as<double>(), 0.0, (size_t)n, rocprim::maximum<double>(), ctx->stream));
+    double rho = 0.0;
+    MG_CHECK(hipMemcpyAsync(&rho, red.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MG_CHECK(hipStreamSynchronize(ctx->stream));
+    if (!(rho > 0.0) || !(rho <= DBL_MAX)) {
+        ctx->err = "bis_mg_create_smoothed: the bound on the spectral radius of D^-1 A is not a positive finite number";
+        return BIS_ERR_INVALID;
+    }
+    const double omega_l = prolong_omega / rho;
+    MatHold T{ctx}, P{ctx}, R{ctx}, AP{ctx}, C{ctx};
+    if (bis_status st = bis_mat_alloc(ctx, n, nc, n, bis_want_rp64(n), &T.m)) return st;
+    if (T.m->rp64) hipLaunchKernelGGL(mg_tentative_kernel<int64_t>, dim3(mg_grid(n + 1)), dim3(kMgT), 0, ctx->stream, L.agg, n, (int64_t *)T.m->row_ptr,
+                                      T.m->col, T.m->val);
+    else hipLaunchKernelGGL(mg_tentative_kernel<int32_t>, dim3(mg_grid(n + 1)), dim3(kMgT), 0, ctx->stream, L.agg, n, (int32_t *)T.m->row_ptr,
+                            T.m->col, T.m->val);
+    MG_CHECK(hipGetLastError());
+    if (bis_status st = bis_spgemm(ctx, L.A, T.m, &P.m)) return st; // Q
+    hipLaunchKernelGGL(mg_smooth_p_kernel, dim3(mg_grid(n)), dim3(kMgT), 0, ctx->stream, P.m->row_ptr, P.m->rp64 ? 1 : 0, P.m->col, P.m->val, L.agg,
+                       d.as<double>(), omega_l, n);
+    MG_CHECK(hipGetLastError());
+    MG_CHECK(hipStreamSynchronize(ctx->stream));
+    bis_mat_values_changed(P.m);
+    if (bis_status st = bis_mat_transpose(ctx, P.m, &R.m)) return st;
+    if (bis_status st = bis_spgemm(ctx, L.A, P.m, &AP.m)) return st;
+    if (bis_status st = bis_spgemm(ctx, R.m, AP.m, &C.m)) return st;
+    L.P = P.release();
+    L.R = R.release();
+    L.pomega = omega_l;
+    *out = C.release();
+    return BIS_OK;
+}
+
 void free_level(bis_ctx *ctx, bis_mg_level &L) {
     hipFree(L.w); hipFree(L.agg); hipFree(L.agg_ptr); hipFree(L.agg_idx); hipFree(L.x); hipFree(L.b); hipFree(L.y);
     hipFree(L.kr); hipFree(L.kd); hipFree(L.kv);
     if (L.owned) bis_mat_destroy(ctx, L.owned);
+    if (L.P) bis_mat_destroy(ctx, L.P);
+    if (L.R) bis_mat_destroy(ctx, L.R);
     L = bis_mg_level();
 }
 
@@ -747,9 +890,15 @@ bis_status mg_build(bis_ctx *ctx, const bis_mat *A, bis_mg *mg) {
         }
         L.kind = grid_ok ? 1 : 2;
         L.n_coarse = nc;
-        if (bis_status st = members_lists(ctx, L)) return st;
         bis_mat *C = nullptr;
-        if (bis_status st = L.A->rp64 ? galerkin<int64_t>(ctx, L, &C) : galerkin<int32_t>(ctx, L, &C)) return st;
+        if (mg->smoothed) {
+            if (bis_status st = L.A->rp64 ? smoothed_transition<int64_t>(ctx, mg->prolong_omega, L, &C)
+                                          : smoothed_transition<int32_t>(ctx, mg->prolong_omega, L, &C))
+                return st;
+        } else {
+            if (bis_status st = members_lists(ctx, L)) return st;
+            if (bis_status st = L.A->rp64 ? galerkin<int64_t>(ctx, L, &C) : galerkin<int32_t>(ctx, L, &C)) return st;
+        }
         if (grid_ok) for (int k = 0; k < 4; ++k) C->grid[k] = cg[k];
         if (bis_status st = bis_mat_finalize(ctx, C)) { bis_mat_destroy(ctx, C); return st; }
         mg->lv.emplace_back(); // (reserved: L stays valid, but is not used below)
@@ -822,10 +971,18 @@ bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const doub
     if (bis_status st = smooth(ctx, L, x, b, mg->p.nu - 1)) return st;
     const bis_mg_level &N = mg->lv[l + 1];
     if (bis_status st = bis_spmv_launch(ctx, L.A, x, L.y, nullptr, nullptr)) return st;
-    hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_grid(N.n)), dim3(kMgT), 0, ctx->stream, L.agg_ptr, L.agg_idx, b, L.y, N.b, N.n);
+    if (L.R) // a smoothed hierarchy: the transfers are R and P
+        hipLaunchKernelGGL(mg_restrict_sa_kernel, dim3(mg_grid(N.n * 64)), dim3(kMgT), 0, ctx->stream, L.R->row_ptr, L.R->rp64 ? 1 : 0, L.R->col,
+                           L.R->val, b, L.y, N.b, N.n);
+    else
+        hipLaunchKernelGGL(mg_restrict_kernel, dim3(mg_grid(N.n)), dim3(kMgT), 0, ctx->stream, L.agg_ptr, L.agg_idx, b, L.y, N.b, N.n);
     BIS_HIP_CHECK(ctx, hipGetLastError());
     if (bis_status st = coarse_solve(ctx, mg, l)) return st;
-    if (bis_status st = launch_prolong(ctx, x, L.agg, N.x, mg->p.coarse_scale, L.n)) return st;
+    if (L.P) {
+        hipLaunchKernelGGL(mg_prolong_sa_kernel, dim3(mg_grid(L.n)), dim3(kMgT), 0, ctx->stream, x, L.P->row_ptr, L.P->rp64 ? 1 : 0, L.P->col, L.P->val,
+                           N.x, mg->p.coarse_scale, L.n);
+        BIS_HIP_CHECK(ctx, hipGetLastError());
+    } else if (bis_status st = launch_prolong(ctx, x, L.agg, N.x, mg->p.coarse_scale, L.n)) return st;
     return smooth(ctx, L, x, b, mg->p.nu);
 }
 
@@ -833,7 +990,19 @@ bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const doub
 
 extern "C" {
 
+static bis_status mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, bool smoothed, double prolong_omega, bis_mg **out);
+
 bis_status bis_mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, bis_mg **out) {
+    return mg_create(ctx, A, params, false, 0.0, out);
+}
+
+bis_status bis_mg_create_smoothed(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, double prolong_omega, bis_mg **out) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, prolong_omega == 0.0 || (prolong_omega > 0.0 && prolong_omega < 2.0), "bis_mg_create_smoothed: prolong_omega is 0 (4/3) or in (0, 2)");
+    return mg_create(ctx, A, params, true, prolong_omega == 0.0 ? 4.0 / 3.0 : prolong_omega, out);
+}
+
+static bis_status mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, bool smoothed, double prolong_omega, bis_mg **out) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, A && out, "bis_mg_create: bad arguments");
     BIS_REQUIRE(ctx, A->n_rows == A->n_cols, "bis_mg_create: square matrix required");
@@ -845,6 +1014,8 @@ bis_status bis_mg_create(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *pa
                 "bis_mg_create: bad parameters (1 <= max_levels <= 16, coarse_limit >= 1, coarsening 0..2, nu >= 1, coarse_sweeps >= 1, omega >= 0)");
     bis_mg *mg = new bis_mg;
     mg->p = p;
+    mg->smoothed = smoothed;
+    mg->prolong_omega = prolong_omega;
     const bis_status st = mg_build(ctx, A, mg);
     if (st != BIS_OK) { mg_free(ctx, mg); return st; }
     *out = mg;
@@ -937,6 +1108,20 @@ bis_status bis_mg_info(const bis_mg *mg, int *levels, int64_t *rows, int64_t *nn
 
 const bis_mat *bis_mg_level_matrix(const bis_mg *mg, int level) {
     return (mg && level >= 0 && (size_t)level < mg->lv.size()) ? mg->lv[(size_t)level].A : nullptr;
+}
+
+const bis_mat *bis_mg_level_prolongator(const bis_mg *mg, int level) {
+    return (mg && level >= 0 && (size_t)level < mg->lv.size()) ? mg->lv[(size_t)level].P : nullptr;
+}
+
+const bis_mat *bis_mg_level_restrictor(const bis_mg *mg, int level) {
+    return (mg && level >= 0 && (size_t)level < mg->lv.size()) ? mg->lv[(size_t)level].R : nullptr;
+}
+
+bis_status bis_mg_level_prolong_omega(const bis_mg *mg, int level, double *omega_l) {
+    if (!bis_mg_level_prolongator(mg, level) || !omega_l) return BIS_ERR_INVALID;
+    *omega_l = mg->lv[(size_t)level].pomega;
+    return BIS_OK;
 }
 
 bis_status bis_mg_level_aggregates(bis_ctx *ctx, const bis_mg *mg, int level, int32_t *host) {

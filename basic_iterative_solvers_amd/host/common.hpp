@@ -67,6 +67,9 @@ inline bis_mg_params &precond_mg_params() { static bis_mg_params p = {10, 256, 0
 // -mg cycle=v|w|k|kgcr,klev=N: the cycle of -p mg and the number of transitions it covers (bis_mg_set_cycle; 0: all but the last)
 struct MGCycle { int cycle = BIS_MG_CYCLE_V, levels = 0; };
 inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
+// -mg smooth=1[,pomega=X]: smoothed aggregation (bis_mg_create_smoothed) with the prolongator's factor X in (0, 2); 0: the library's 4/3
+struct MGSmooth { bool smooth = false; double pomega = 0.0; };
+inline MGSmooth &precond_mg_smooth() { static MGSmooth s; return s; }
 // -bs N: rows per block of -p bj (bis_bj_params.block_size); 0: not given, the dof of the matrix' grid hint where that is above 1
 inline int &precond_block_size() { static int b = 0; return b; }
 // -fill K: level-of-fill of -p ilu0 / -p ilu0it (bis_mat_iluk); 0, the default, is ILU(0) as it always ran

@@ -118,7 +118,9 @@ inline void factor_LU(Solver *s) {
     }
     if (s->preconditioner == PrecondType::MG) {
         // -p mg: the hierarchy of A (after -scale and -perm); its operand takes the place of the strict lower triangle
-        const bis_status st = bis_mg_create(bis::ctx(), s->A->dev, &precond_mg_params(), &s->mg);
+        const MGSmooth &sm = precond_mg_smooth();
+        const bis_status st = sm.smooth ? bis_mg_create_smoothed(bis::ctx(), s->A->dev, &precond_mg_params(), sm.pomega, &s->mg)
+                                        : bis_mg_create(bis::ctx(), s->A->dev, &precond_mg_params(), &s->mg);
         if (st == BIS_ERR_ZERO_DIAG || st == BIS_ERR_UNSUPPORTED || st == BIS_ERR_INVALID) { fprintf(stderr, "%s\n", bis_last_error(bis::ctx())); exit(EXIT_FAILURE); }
         bis::check(st, "bis_mg_create");
         s->L_strict->free_host();
@@ -133,6 +135,7 @@ inline void factor_LU(Solver *s) {
         std::cout << ", operator complexity " << (nnz[0] > 0 ? total / (double)nnz[0] : 1.0) << ", aggregates";
         for (int l = 0; l + 1 < levels; ++l) std::cout << (l ? " / " : " ") << (kind[l] == 1 ? "grid" : "mis");
         if (levels < 2) std::cout << " none";
+        if (sm.smooth) std::cout << ", smoothed prolongators (omega " << (sm.pomega == 0.0 ? 4.0 / 3.0 : sm.pomega) << ")";
         std::cout << std::endl;
         const MGCycle &cyc = precond_mg_cycle();
         if (cyc.cycle != BIS_MG_CYCLE_V) { // (a command line without cycle= prints and computes what it always did)

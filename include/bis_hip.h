@@ -422,6 +422,41 @@ BIS_API bis_status bis_iluk_limits(int *max_level, int *max_visit);
 BIS_API bis_status bis_mat_fsai(bis_ctx *ctx, const bis_mat *A, bis_mat **G, bis_mat **Gt, int64_t *n_fallback_rows);
 BIS_API const char *bis_mat_fsai_kernel(const bis_mat *G);
 
+/* ---- sparse matrix-matrix product and transpose (bis_spgemm.hip); no reference counterpart --------------------------------
+ * bis_spgemm: C = A B for A (n x m) and B (m x p), either may be rectangular; nothing is assumed about the order of the
+ * columns inside the rows of A or B, or about repeats.
+ * Enumeration: for row i the products are taken in this order: position s in row i of A (CRS order, j = col[s]), then
+ * position t in row j of B (k = col[t]).
+ * Pattern: entry (i, k) of C exists iff at least one product lands on it -- also where the values cancel to 0.
+ * Value: the sum of a_ij b_jk in enumeration order, the first product starting the sum, every product and every addition
+ * rounded separately in fp64 (no fused multiply-add).
+ * Rows: columns ascend inside a row, without repeats.  Row pointers: 64-bit when nnz(C) needs them or option force_rp64
+ * is set.  C carries no grid hint and no fp32 flag.
+ * Two paths give these bits.  With u_i = sum over the entries (i, j) of A of nnz(B_j): a row with u_i <= spgemm_row_cap
+ * (option; default and at most 4096) takes the row path -- a workgroup per row of C (one wave up to 256 products, four
+ * waves beyond) sorts the candidate columns in LDS and gives every output entry to a lane that walks A's row in order and
+ * bisects the rows of B; it needs strictly ascending rows of B, so any other B sends every row to the fallback.  Every
+ * other row (and every row with spgemm_row_cap = 0) takes the fallback: whole rows in batches of at most spgemm_batch
+ * products (option; default 2^26; a longer row is a batch of its own), expanded, sorted by a stable 64-bit radix sort and
+ * summed run by run.  Its temporary memory grows with the batch, not with the total number of products.  Nothing is
+ * truncated or refused for its length.
+ * Blocking.  No floating-point atomics, no inter-workgroup waits: two calls give the same bits.
+ * BIS_ERR_INVALID: null arguments, n_cols(A) != n_rows(B), a row-range view.  n = 0 or no product at all: BIS_OK, a C
+ * without entries.  *C is written on success only.
+ * bis_spgemm_kernel: the path(s) that made C: "spgemm_row_kernel", "spgemm_sort_fallback" or
+ * "spgemm_row_kernel + spgemm_sort_fallback" (static string; "" for a C without entries and for any other matrix).
+ * bis_spgemm_limits (any pointer may be NULL): wave_cap = 256, row_cap = 4096 (the default of spgemm_row_cap),
+ * row_cap_max = 4096 (larger settings count as this), batch = 2^26 (the default of spgemm_batch).
+ *
+ * bis_mat_transpose: At = A^T with the values of A bit for bit.  Row c of At lists the entries of column c of A in
+ * ascending row order; repeats of a column inside one row of A stay adjacent, in that row's order.  Row pointers by the
+ * library's rule, no grid hint.  A stable sort places the entries: the result does not depend on the schedule.
+ * BIS_ERR_INVALID: null arguments, a row-range view.  *At is written on success only.  Blocking. */
+BIS_API bis_status bis_spgemm(bis_ctx *ctx, const bis_mat *A, const bis_mat *B, bis_mat **C);
+BIS_API bis_status bis_mat_transpose(bis_ctx *ctx, const bis_mat *A, bis_mat **At);
+BIS_API const char *bis_spgemm_kernel(const bis_mat *C);
+BIS_API bis_status bis_spgemm_limits(int *wave_cap, int *row_cap, int *row_cap_max, int64_t *batch);
+
 /* ---- aggregation multigrid (bis_mg.hip); no reference counterpart ------------------------------------------------------
  * Unsmoothed aggregation, one V(nu,nu) cycle with Jacobi-type smoothing as the preconditioner (or a W- or K-cycle of the same
  * hierarchy: bis_mg_set_cycle): SpMVs and streaming passes only, no dependency between rows, any row order.
@@ -514,6 +549,34 @@ BIS_API const bis_mat *bis_mg_level_matrix(const bis_mg *mg, int level);
 /* agg[0, n_l) of a level that is not the coarsest, and w[0, n_l) of any level, to host arrays.  Blocking. */
 BIS_API bis_status bis_mg_level_aggregates(bis_ctx *ctx, const bis_mg *mg, int level, int32_t *host);
 BIS_API bis_status bis_mg_level_weights(bis_ctx *ctx, const bis_mg *mg, int level, double *host);
+/* Smoothed aggregation: bis_mg_create with one Jacobi-smoothed prolongator per transition.  prolong_omega 0 means 4/3;
+ * otherwise it must lie in (0, 2) (else BIS_ERR_INVALID).  Everything bis_mg_create documents holds -- level rule, 0.8 rule,
+ * grid / MIS aggregates, weights, error table, the hint (cx, cy, cz, dof) on grid levels, blocking, reproducible bits --
+ * except the transfer operators and the Galerkin product of every transition, built from the level matrix A (n rows), its
+ * aggregates agg and n_c:
+ *   rho = max_i (s_i / |a_ii|), s_i = sum_j |a_ij| summed left to right from 0 (the sum of the l1 weights), a_ii the first
+ *   diagonal entry of row i, the quotient rounded: Gershgorin's bound on the spectral radius of D^-1 A.
+ *   omega_l = prolong_omega / rho (one division).
+ *   T: n x n_c with t_{i,agg[i]} = 1.  Q = A T by bis_spgemm's rule (the products a_ij 1 are exact).
+ *   P has Q's pattern, structural zeros kept: c_i = omega_l / a_ii, p_iJ = t_iJ - c_i q_iJ (the product rounded, then the
+ *   difference; t_iJ = 0 off the aggregate).  R = bis_mat_transpose(P).
+ *   A_c = bis_spgemm(R, bis_spgemm(A, P)), in that association.
+ * Entries that cancel stay in the pattern, so A_c is structurally symmetric whenever A is: MIS aggregates of the next
+ * level can be taken.
+ * The cycle is bis_mg_apply's with the two transfers replaced, every product and addition rounded separately:
+ *   r_c[I] = sum over row I of R of R_{I,t} (b - y)_{col t}: lane q of a wave of 64 sums the products at the positions
+ *   q, q + 64, ... of the row in that order from 0, and the 64 sums are added pairwise, lane q with lane q + 32, then
+ *   + 16, ..., + 1;
+ *   x_i = x_i + coarse_scale (sum over row i of P of P_{i,t} e_c[col t]), the row taken left to right, the first product
+ *   starting the sum.
+ * bis_mg_set_cycle and everything that takes BIS_PC_MG work on such a hierarchy unchanged.
+ * bis_mg_level_prolongator / _restrictor: P and R of the transition from `level`, owned by the hierarchy; NULL on the
+ * coarsest level, outside the hierarchy and on a hierarchy made by bis_mg_create.  bis_mg_level_prolong_omega: omega_l of
+ * such a transition (BIS_ERR_INVALID where the prolongator is NULL).  bis_mg_info's nnz counts the level operators only. */
+BIS_API bis_status bis_mg_create_smoothed(bis_ctx *ctx, const bis_mat *A, const bis_mg_params *params, double prolong_omega, bis_mg **out);
+BIS_API const bis_mat *bis_mg_level_prolongator(const bis_mg *mg, int level);
+BIS_API const bis_mat *bis_mg_level_restrictor(const bis_mg *mg, int level);
+BIS_API bis_status bis_mg_level_prolong_omega(const bis_mg *mg, int level, double *omega_l);
 
 /* ---- block Jacobi (bis_bjacobi.hip); no reference counterpart -------------------------------------------------------------
  * M^-1 = diag(B_0^-1, B_1^-1, ...): the dense diagonal blocks of A over blocks of consecutive rows, inverted once on the

@@ -16,6 +16,12 @@ the device).  Reported per input:
       first 1, 2, 3 and on all transitions (a count that covers all of them is run once, as "all") -- iterations and ms of
       the fused CG to 1e-10 r0, and one apply against the sum of its own SpMVs timed alone (the K-GCR legs are there for the
       apply's cost: its cycle is not symmetric, CG is not the method for it).  The cycle is set before the clock starts.
+  (e) smoothed aggregation (bis_mg_create_smoothed) against the unsmoothed hierarchy: ms of the whole setup of either, the
+      rows, non-zeros and SpMV form of every level of both, and of the first transition the two bis_spgemm calls (A P, then
+      R (A P)) and the transpose timed alone, with the path each product took;
+  (f) iterations and ms of the fused CG to 1e-10 r0 with the smoothed V-cycle against the unsmoothed V, W and K cycles and
+      none, sgs, ilu0it (inner 3) and fsai; "best_other" names the fastest leg that is not multigrid.
+(e) and (f) run only when --parts names them.
 --json writes the records (meant for profiles/)."""
 import json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -236,6 +242,93 @@ def run_input(spec, parts, rounds, max_iters):
         for v in [out] + xs + ys:
             v.free()
 
+    if "e" in parts or "f" in parts:
+        sm = ctx.mg(A, smooth=True)
+        sm_levels = [sm.level_matrix(l) for l in range(sm.levels)]
+        rec["smoothed_hierarchy"] = dict(levels=sm.levels, rows=sm.rows, nnz=sm.nnz, kinds=sm.kinds,
+                                         operator_complexity=sum(sm.nnz) / max(sm.nnz[0], 1),
+                                         prolong_omega=[sm.prolong_omega(l) for l in range(sm.levels - 1)],
+                                         nnz_P=[sm.prolongator(l).nnz for l in range(sm.levels - 1)],
+                                         spmv_forms=[[M.spmv_stream_info()[3], M.spmv_kernel()] for M in sm_levels])
+        print(f"{spec}: smoothed: {sm.levels} levels, rows {sm.rows}, nnz {sm.nnz}, operator complexity "
+              f"{rec['smoothed_hierarchy']['operator_complexity']:.3f}", flush=True)
+
+    if "e" in parts:
+        legs = [("unsmoothed", lambda: ctx.mg(A).free()), ("smoothed", lambda: ctx.mg(A, smooth=True).free())]
+        paths = {}
+        if sm.levels > 1:
+            P, R = sm.prolongator(0), sm.restrictor(0)
+            AP = ctx.spgemm(A, P)
+            paths["A P"] = AP.spgemm_kernel()
+
+            def ap_leg():
+                ctx.spgemm(A, P).free()
+
+            def rap_leg():
+                C_ = ctx.spgemm(R, AP)
+                paths["R (A P)"] = C_.spgemm_kernel()
+                C_.free()
+
+            legs += [("spgemm A P", ap_leg), ("spgemm R (A P)", rap_leg), ("transpose P", lambda: P.transpose().free())]
+        r = summary(timed(ctx, legs, rounds))
+        r["paths"] = paths
+        rec["smoothed_setup"] = r
+        print(f"{spec} (e) setup ms: " + ", ".join(f"{k} {v:.2f}" for k, v in r["median_ms"].items()) + f"; paths {paths}", flush=True)
+        if sm.levels > 1:
+            AP.free()
+
+    if "f" in parts:
+        Ls, Us, D, Dinv = ctx.split_strict(A)
+        iLs, iLD, iUs, iUD = ctx.ilu0(A)
+        iUinv = ctx.alloc(n)
+        ctx.elemwise_div_vectors(iUinv, iLD, iUD)
+        mgw, mgk = ctx.mg(A, cycle="w"), ctx.mg(A, cycle="k")
+        pcs = [("mg smoothed V", "mg", 0, dict(Ls=sm.operand)), ("mg V", "mg", 0, dict(Ls=mg.operand)), ("mg W", "mg", 0, dict(Ls=mgw.operand)),
+               ("mg K", "mg", 0, dict(Ls=mgk.operand)), ("none", None, 0, {}),
+               ("sgs", "sgs", 0, dict(Ls=Ls, Us=Us, A_D=D, A_D_inv=Dinv, L_D=D, U_D=D)),
+               ("ilu0it", "ilu0it", 3, dict(Ls=iLs, Us=iUs, A_D=iLD, A_D_inv=iUinv, L_D=iLD, U_D=iUD))]
+        try:
+            G, Gt, _ = ctx.fsai(A)
+            pcs.append(("fsai", "fsai", 0, dict(Ls=G, Us=Gt)))
+        except Exception as e:  # (rows longer than FSAI's limit)
+            rec["fsai_refused"] = str(e)
+        handles, legs, got = [], [], {}
+
+        def solve_leg_f(s, key):
+            def f():
+                ctx.init_vector(x, 0.0)
+                s.init(TOL)
+                done = 0
+                while done < max_iters:
+                    s.iterate(CHUNK)
+                    done += CHUNK
+                    it, conv, hist = s.status()
+                    if conv or it < done:
+                        break
+                got[key] = dict(iters=it, converged=conv, last_over_r0=float(hist[-1] / hist[0]) if len(hist) else 0.0)
+            return f
+
+        for key, pc, inner, kw in pcs:
+            s = ctx.cg(A, b, x)
+            if pc:
+                s.set_preconditioner(pc, inner=inner, **kw)
+            handles.append(s)
+            legs.append((key, solve_leg_f(s, key)))
+        r = summary(timed(ctx, legs, rounds))
+        r["result"] = got
+        others = [k for k, *_ in pcs if not k.startswith("mg") and got[k]["converged"]]
+        r["best_other"] = min(others, key=lambda k: r["median_ms"][k]) if others else None
+        rec["smoothed_solve_cg"] = r
+        print(f"{spec} (f) -cg to {TOL:g} r0: " + ", ".join(
+            f"{k} {got[k]['iters']} it {'conv' if got[k]['converged'] else 'NOT conv'} {r['median_ms'][k]:.1f} ms" for k, *_ in pcs) +
+            f"; best non-mg: {r['best_other']}", flush=True)
+        for s in handles:
+            s.free()
+        mgw.free()
+        mgk.free()
+
+    if "e" in parts or "f" in parts:
+        sm.free()
     info = ctx.device_info()
     mg.free()
     mg15.free()
