@@ -296,19 +296,23 @@ class Context:
         self.check(self.lib.bis_spgemm(self.h, A.h, B.h, C.byref(h)))
         return Mat(self, h)
 
-    def mg(self, A, cycle=None, cycle_levels=0, smooth=False, prolong_omega=0.0, **params):
+    def mg(self, A, cycle=None, cycle_levels=0, smooth=False, prolong_omega=0.0, smoother=None, degree=2, ratio=None, est_steps=10,
+           safety=1.1, **params):
         """The aggregation multigrid hierarchy of A (bis_mg_create): an MG object.  Parameters: max_levels, coarse_limit,
         coarsening (0 / "auto", 1 / "grid", 2 / "mis"), nu, coarse_sweeps, omega, coarse_scale.  `cycle` (0 / "v", 1 / "w",
         2 / "k", 3 / "kgcr") and `cycle_levels` go to MG.set_cycle after creation; without `cycle` the hierarchy stays V.
         `smooth` builds smoothed aggregation (bis_mg_create_smoothed) with the factor `prolong_omega` (0: 4/3).
-        Preconditioner "mg" takes Ls=MG.operand."""
+        `smoother` (0 / "jacobi", 1 / "cheb") with `degree`, `ratio`, `est_steps`, `safety` goes to MG.set_smoother; without it
+        the hierarchy relaxes with its weights, as before.  Preconditioner "mg" takes Ls=MG.operand."""
         m = MG(self, A, smooth=smooth, prolong_omega=prolong_omega, **params)
-        if cycle is not None:
-            try:
+        try:
+            if cycle is not None:
                 m.set_cycle(cycle, cycle_levels)
-            except Exception:
-                m.free()
-                raise
+            if smoother is not None:
+                m.set_smoother(smoother, degree=degree, ratio=ratio, est_steps=est_steps, safety=safety)
+        except Exception:
+            m.free()
+            raise
         return m
 
     def bjacobi(self, A, block_size=None, block_ptr=None, symmetrize=False):
@@ -657,12 +661,21 @@ class MGParams(C.Structure):
                 ("coarse_sweeps", C.c_int), ("omega", C.c_double), ("coarse_scale", C.c_double)]
 
 
+class MGSmoother(C.Structure):
+    """bis_mg_smoother."""
+    _fields_ = [("kind", C.c_int), ("degree", C.c_int), ("ratio", C.c_double), ("est_steps", C.c_int), ("safety", C.c_double)]
+
+
 class MG:
     """bis_mg: an aggregation multigrid hierarchy of A; one cycle of it (V unless set_cycle chose W or K) is the
     preconditioner "mg" (pass `.operand` as Ls)."""
 
     COARSENING = dict(auto=0, grid=1, mis=2)
     CYCLE = dict(v=0, w=1, k=2, kgcr=3)
+    SMOOTHER = dict(jacobi=0, cheb=1)
+    # lambda_max / lambda_min of the Chebyshev smoother: the fewest CG iterations in total over HPCG 16^3 and 32^3 and the
+    # unstructured 8^3 input, plain and smoothed, degree 2 and 3, among 4, 10, 20 and 30 (docs/EXPERIMENTS.md)
+    DEFAULT_RATIO = 4.0
 
     def __init__(self, ctx, A, max_levels=10, coarse_limit=256, coarsening=0, nu=1, coarse_sweeps=4, omega=0.0, coarse_scale=1.0,
                  smooth=False, prolong_omega=0.0):
@@ -734,6 +747,40 @@ class MG:
         c, k = C.c_int(), C.c_int()
         self.ctx.check(self.ctx.lib.bis_mg_cycle(self.h, C.byref(c), C.byref(k)))
         return c.value, k.value
+
+    def set_smoother(self, kind, degree=2, ratio=None, est_steps=10, safety=1.1):
+        """The smoother of this hierarchy (bis_mg_set_smoother; blocking): 0 / "jacobi", or 1 / "cheb": one Chebyshev
+        polynomial of `degree` (1..8) in W A per sweep, built for [lambda_max / ratio, lambda_max] (ratio None:
+        DEFAULT_RATIO), lambda_max from the row-sum bound, tightened by `est_steps` (0..100) steps of a power iteration
+        times `safety`."""
+        if isinstance(kind, str):
+            if kind not in self.SMOOTHER:
+                raise BisError(f"MG.set_smoother: kind {kind!r} is none of {sorted(self.SMOOTHER)}")
+            kind = self.SMOOTHER[kind]
+        s = MGSmoother(int(kind), int(degree), float(self.DEFAULT_RATIO if ratio is None else ratio), int(est_steps), float(safety))
+        self.ctx.check(self.ctx.lib.bis_mg_set_smoother(self.ctx.h, self.h, C.byref(s)))
+
+    def smoother(self):
+        """dict(kind, degree, ratio, est_steps, safety) as set (bis_mg_smoother_info); a Jacobi hierarchy reports zeros."""
+        s = MGSmoother()
+        self.ctx.check(self.ctx.lib.bis_mg_smoother_info(self.h, C.byref(s)))
+        return dict(kind=s.kind, degree=s.degree, ratio=s.ratio, est_steps=s.est_steps, safety=s.safety)
+
+    def spectrum(self, l):
+        """dict(bound, estimate, lambda_max, lambda_min) of level l under the Chebyshev smoother (bis_mg_level_spectrum);
+        None on a Jacobi hierarchy and outside the hierarchy."""
+        v = [C.c_double() for _ in range(4)]
+        if self.ctx.lib.bis_mg_level_spectrum(self.h, C.c_int(int(l)), *[C.byref(x) for x in v]) != 0:
+            return None
+        return dict(zip(("bound", "estimate", "lambda_max", "lambda_min"), (x.value for x in v)))
+
+    def cheb_coeffs(self, l):
+        """(c1, c2) of level l, numpy arrays of `degree` (bis_mg_level_cheb_coeffs); None where spectrum is."""
+        k = self.smoother()["degree"]
+        c1, c2 = np.zeros(max(k, 1)), np.zeros(max(k, 1))
+        if self.ctx.lib.bis_mg_level_cheb_coeffs(self.h, C.c_int(int(l)), c1.ctypes, c2.ctypes) != 0:
+            return None
+        return c1[:k], c2[:k]
 
     def apply(self, out, inp):
         """out = M^-1 inp: one cycle (bis_mg_apply); out may alias inp."""

@@ -23,12 +23,22 @@
 // streaming kernels: r = a - s b with s on the device, the multi-dot pass (2 or 3 sums over 3 or 4 operands in one read, the last
 // workgroup to arrive sums the partials in index order and computes the step's coefficients into the transition's own device
 // scalars) and the combine x = c1 x + c2 d.  The launch sequence is fixed, nothing is read back.
+//
+// Chebyshev smoother (bis_mg_set_smoother, blocking, allocates one more vector d per level): every sweep becomes one polynomial
+// of degree m in W A for [lambda_max / ratio, lambda_max] -- m SpMVs and m streaming steps d = c1 d + c2 w o (b - y), x += d,
+// the first step of a level visit from x = 0 without its SpMV.  lambda_max per level: the row-sum bound max_i w_i sum_j |a_ij|
+// (one kernel and a one-workgroup maximum), optionally tightened by a power iteration run with the public single-vector calls;
+// the coefficients are computed on the host and travel as kernel arguments.  A hierarchy that never saw the call launches what
+// it always did.
 #include "bis_internal.hpp"
 
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
+
+constexpr int kMgMaxDegree = 8;
 
 struct bis_mg_level {
     const bis_mat *A = nullptr; // level 0: the caller's matrix; otherwise `owned`
@@ -46,6 +56,12 @@ struct bis_mg_level {
     // a smoothed hierarchy only (bis_mg_create_smoothed): the transfer operators towards the next level and their omega_l
     bis_mat *P = nullptr, *R = nullptr;
     double pomega = 0.0;
+    // the Chebyshev smoother only (bis_mg_set_smoother): cd = the polynomial's direction d, live inside one smoothing call;
+    // cheb_degree > 0 is what switches this level's sweeps over
+    double *cd = nullptr;
+    int cheb_degree = 0;
+    double cheb_c1[kMgMaxDegree] = {0}, cheb_c2[kMgMaxDegree] = {0};
+    double sp_bound = 0.0, sp_estimate = 0.0, sp_lmax = 0.0, sp_lmin = 0.0;
 };
 
 struct bis_mg {
@@ -56,6 +72,7 @@ struct bis_mg {
     bis_mat *operand = nullptr;
     double *b0 = nullptr; // level 0: the copy of the right-hand side when out aliases in
     int cycle = BIS_MG_CYCLE_V, cycle_levels = 0;
+    bis_mg_smoother sm = {BIS_MG_SMOOTH_JACOBI, 0, 0.0, 0, 0.0};
     // W and K transitions (allocated by the first bis_mg_set_cycle that leaves V)
     double *ksc = nullptr;       // device scalars: [0, 4) = {1, 1, 0, 1}: W's constants; transition t: [kMgScBase + kMgScPer t, ...), MG_SC_*
     double *kpartials = nullptr; // [3 kMaxReduceBlocks] the multi-dot pass' per-workgroup sums
@@ -833,7 +850,7 @@ bis_status smoothed_transition(bis_ctx *ctx, double prolong_omega, bis_mg_level 
 
 void free_level(bis_ctx *ctx, bis_mg_level &L) {
     hipFree(L.w); hipFree(L.agg); hipFree(L.agg_ptr); hipFree(L.agg_idx); hipFree(L.x); hipFree(L.b); hipFree(L.y);
-    hipFree(L.kr); hipFree(L.kd); hipFree(L.kv);
+    hipFree(L.kr); hipFree(L.kd); hipFree(L.kv); hipFree(L.cd);
     if (L.owned) bis_mat_destroy(ctx, L.owned);
     if (L.P) bis_mat_destroy(ctx, L.P);
     if (L.R) bis_mat_destroy(ctx, L.R);
@@ -925,9 +942,122 @@ bis_status mg_build(bis_ctx *ctx, const bis_mat *A, bis_mg *mg) {
     return BIS_OK;
 }
 
-// `sweeps` further sweeps x += w o (b - A x)
+// ---- the Chebyshev smoother's kernels (after everything the plain cycle launches: those keep their place in the code object) ----
+// The Chebyshev smoother's steps (bis_mg_set_smoother).  From x = 0: d = c2 (w b), x = d.  The inputs are read once:
+// non-temporal loads; x and d are stored plainly -- the next SpMV and the next step read them.
+template <bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_cheb0_kernel(double *x, double *d, const double *w, const double *b, double c2, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *x2 = reinterpret_cast<mg_v2d *>(x), *d2 = reinterpret_cast<mg_v2d *>(d);
+        const mg_v2d *w2 = reinterpret_cast<const mg_v2d *>(w), *b2 = reinterpret_cast<const mg_v2d *>(b);
+        for (; i < n2; i += stride) {
+            const mg_v2d wv = __builtin_nontemporal_load(w2 + i), bv = __builtin_nontemporal_load(b2 + i);
+            mg_v2d r;
+            r.x = __dmul_rn(c2, __dmul_rn(wv.x, bv.x));
+            r.y = __dmul_rn(c2, __dmul_rn(wv.y, bv.y));
+            d2[i] = r;
+            x2[i] = r;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = d[n - 1] = __dmul_rn(c2, __dmul_rn(w[n - 1], b[n - 1]));
+    } else {
+        for (; i < n; i += stride) x[i] = d[i] = __dmul_rn(c2, __dmul_rn(__builtin_nontemporal_load(w + i), __builtin_nontemporal_load(b + i)));
+    }
+}
+
+// The general step with y = A x: t = b - y, u = w t, d = (c1 d) + (c2 u), x = x + d, each rounded.  FIRST (step 0 of a
+// polynomial): d = c2 u -- the d of the polynomial before is neither read nor multiplied.
+template <bool FIRST>
+__device__ __forceinline__ double mg_cheb1(double d, double w, double b, double y, double c1, double c2) {
+    // (bis_mul_sep: a product that feeds a sum -- here, or x + d in the caller -- would otherwise be contracted into it)
+    const double cu = bis_mul_sep(c2, __dmul_rn(w, __dsub_rn(b, y)));
+    return FIRST ? cu : __dadd_rn(bis_mul_sep(c1, d), cu);
+}
+
+template <bool FIRST, bool VEC>
+__global__ __launch_bounds__(kMgT) void mg_cheb_kernel(double *x, double *d, const double *w, const double *b, const double *y, double c1,
+                                                       double c2, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        mg_v2d *x2 = reinterpret_cast<mg_v2d *>(x), *d2 = reinterpret_cast<mg_v2d *>(d);
+        const mg_v2d *w2 = reinterpret_cast<const mg_v2d *>(w), *b2 = reinterpret_cast<const mg_v2d *>(b),
+                     *y2 = reinterpret_cast<const mg_v2d *>(y);
+        for (; i < n2; i += stride) {
+            const mg_v2d wv = __builtin_nontemporal_load(w2 + i), bv = __builtin_nontemporal_load(b2 + i),
+                         yv = __builtin_nontemporal_load(y2 + i), xv = x2[i];
+            mg_v2d dv = xv; // (FIRST: any value, not used)
+            if (!FIRST) dv = d2[i];
+            mg_v2d dn, xn;
+            dn.x = mg_cheb1<FIRST>(dv.x, wv.x, bv.x, yv.x, c1, c2);
+            dn.y = mg_cheb1<FIRST>(dv.y, wv.y, bv.y, yv.y, c1, c2);
+            xn.x = __dadd_rn(xv.x, dn.x);
+            xn.y = __dadd_rn(xv.y, dn.y);
+            d2[i] = dn;
+            x2[i] = xn;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            const int64_t j = n - 1;
+            const double dn = mg_cheb1<FIRST>(FIRST ? 0.0 : d[j], w[j], b[j], y[j], c1, c2);
+            d[j] = dn;
+            x[j] = __dadd_rn(x[j], dn);
+        }
+    } else {
+        for (; i < n; i += stride) {
+            const double dn = mg_cheb1<FIRST>(FIRST ? 0.0 : d[i], __builtin_nontemporal_load(w + i), __builtin_nontemporal_load(b + i),
+                                              __builtin_nontemporal_load(y + i), c1, c2);
+            d[i] = dn;
+            x[i] = __dadd_rn(x[i], dn);
+        }
+    }
+}
+
+bis_status launch_cheb0(bis_ctx *ctx, double *x, double *d, const double *w, const double *b, double c2, int64_t n) {
+    const bool vec = aligned16(x) && aligned16(d) && aligned16(w) && aligned16(b) && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+    if (vec) hipLaunchKernelGGL((mg_cheb0_kernel<true>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, d, w, b, c2, n);
+    else hipLaunchKernelGGL((mg_cheb0_kernel<false>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, d, w, b, c2, n);
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+bis_status launch_cheb(bis_ctx *ctx, bool first, double *x, double *d, const double *w, const double *b, const double *y, double c1, double c2,
+                       int64_t n) {
+    const bool vec = aligned16(x) && aligned16(d) && aligned16(w) && aligned16(b) && aligned16(y) && n >= 2;
+    const int grid = mg_grid(vec ? n >> 1 : n);
+#define MG_CHEB(F, V) hipLaunchKernelGGL((mg_cheb_kernel<F, V>), dim3(grid), dim3(kMgT), 0, ctx->stream, x, d, w, b, y, c1, c2, n)
+    if (first) { if (vec) MG_CHEB(true, true); else MG_CHEB(true, false); }
+    else { if (vec) MG_CHEB(false, true); else MG_CHEB(false, false); }
+#undef MG_CHEB
+    BIS_HIP_CHECK(ctx, hipGetLastError());
+    return BIS_OK;
+}
+
+// steps [from, degree) of one Chebyshev polynomial on x
+bis_status cheb_steps(bis_ctx *ctx, const bis_mg_level &L, double *x, const double *b, int from) {
+    for (int k = from; k < L.cheb_degree; ++k) {
+        if (bis_status st = bis_spmv_launch(ctx, L.A, x, L.y, nullptr, nullptr)) return st;
+        if (bis_status st = launch_cheb(ctx, k == 0, x, L.cd, L.w, b, L.y, L.cheb_c1[k], L.cheb_c2[k], L.n)) return st;
+    }
+    return BIS_OK;
+}
+
+// the first sweep of a level visit, from x = 0: x = w o b, or the polynomial without its first SpMV
+bis_status smooth0(bis_ctx *ctx, const bis_mg_level &L, double *x, const double *b) {
+    if (!L.cheb_degree) return launch_relax0(ctx, x, L.w, b, L.n);
+    if (bis_status st = launch_cheb0(ctx, x, L.cd, L.w, b, L.cheb_c2[0], L.n)) return st;
+    return cheb_steps(ctx, L, x, b, 1);
+}
+
+// `sweeps` further sweeps x += w o (b - A x), or as many polynomials
 bis_status smooth(bis_ctx *ctx, const bis_mg_level &L, double *x, const double *b, int sweeps) {
     for (int s = 0; s < sweeps; ++s) {
+        if (L.cheb_degree) {
+            if (bis_status st = cheb_steps(ctx, L, x, b, 0)) return st;
+            continue;
+        }
         if (bis_status st = bis_spmv_launch(ctx, L.A, x, L.y, nullptr, nullptr)) return st;
         if (bis_status st = launch_relax(ctx, x, L.w, b, L.y, L.n)) return st;
     }
@@ -966,7 +1096,7 @@ bis_status coarse_solve(bis_ctx *ctx, const bis_mg *mg, size_t l) {
 
 bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const double *b) {
     const bis_mg_level &L = mg->lv[l];
-    if (bis_status st = launch_relax0(ctx, x, L.w, b, L.n)) return st;
+    if (bis_status st = smooth0(ctx, L, x, b)) return st;
     if (l + 1 == mg->lv.size()) return smooth(ctx, L, x, b, mg->p.coarse_sweeps - 1);
     if (bis_status st = smooth(ctx, L, x, b, mg->p.nu - 1)) return st;
     const bis_mg_level &N = mg->lv[l + 1];
@@ -985,6 +1115,146 @@ bis_status cycle(bis_ctx *ctx, const bis_mg *mg, size_t l, double *x, const doub
     } else if (bis_status st = launch_prolong(ctx, x, L.agg, N.x, mg->p.coarse_scale, L.n)) return st;
     return smooth(ctx, L, x, b, mg->p.nu);
 }
+
+// ---- the Chebyshev smoother's setup (bis_mg_set_smoother) ---------------------------------------------------------------
+// the Chebyshev smoother's bound on the spectrum of W A: per workgroup the maximum of w_i (sum_j |a_ij|, left to right from 0),
+// the product rounded; mg_max_kernel (one workgroup) then takes the maximum of those.  A maximum does not depend on the order.
+__device__ __forceinline__ double mg_block_max(double m, double *lds) {
+    lds[threadIdx.x] = m;
+    __syncthreads();
+    for (int off = kMgT / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) lds[threadIdx.x] = fmax(lds[threadIdx.x], lds[threadIdx.x + off]);
+        __syncthreads();
+    }
+    return lds[0];
+}
+template <typename RP>
+__global__ __launch_bounds__(kMgT) void mg_bound_kernel(const RP *__restrict__ rp, const double *__restrict__ val, const double *__restrict__ w,
+                                                        int64_t n, double *partial) {
+    __shared__ double lds[kMgT];
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    double m = -DBL_MAX;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) {
+        double sum = 0.0;
+        for (int64_t k = (int64_t)rp[i], e = (int64_t)rp[i + 1]; k < e; ++k) sum = __dadd_rn(sum, fabs(val[k]));
+        m = fmax(m, __dmul_rn(w[i], sum));
+    }
+    m = mg_block_max(m, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+__global__ __launch_bounds__(kMgT) void mg_max_kernel(const double *__restrict__ partial, int count, double *out) {
+    __shared__ double lds[kMgT];
+    double m = -DBL_MAX;
+    for (int k = threadIdx.x; k < count; k += kMgT) m = fmax(m, partial[k]);
+    m = mg_block_max(m, lds);
+    if (threadIdx.x == 0) out[0] = m;
+}
+// the power iteration's start: v_i = hash32(i) / 2^32 - 0.5 (exact)
+__global__ __launch_bounds__(kMgT) void mg_hash_vector_kernel(double *v, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kMgT;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) v[i] = (double)mg_hash32((uint32_t)i) * 0x1p-32 - 0.5;
+}
+#define MG_SM_CHECK(call)                                                                                              \
+    do {                                                                                                               \
+        hipError_t e_ = (call);                                                                                        \
+        if (e_ != hipSuccess) { ctx->err = std::string("bis_mg_set_smoother: " #call ": ") + hipGetErrorString(e_); return BIS_ERR_HIP; } \
+    } while (0)
+
+bis_status level_bound(bis_ctx *ctx, const bis_mg_level &L, double *bound) {
+    const int grid = mg_grid(L.n);
+    DevBuf partial, out;
+    MG_SM_CHECK(partial.alloc(sizeof(double) * (size_t)grid));
+    MG_SM_CHECK(out.alloc(sizeof(double)));
+    if (L.A->rp64)
+        hipLaunchKernelGGL(mg_bound_kernel<int64_t>, dim3(grid), dim3(kMgT), 0, ctx->stream, (const int64_t *)L.A->row_ptr, L.A->val, L.w, L.n,
+                           partial.as<double>());
+    else
+        hipLaunchKernelGGL(mg_bound_kernel<int32_t>, dim3(grid), dim3(kMgT), 0, ctx->stream, (const int32_t *)L.A->row_ptr, L.A->val, L.w, L.n,
+                           partial.as<double>());
+    hipLaunchKernelGGL(mg_max_kernel, dim3(1), dim3(kMgT), 0, ctx->stream, partial.as<double>(), grid, out.as<double>());
+    MG_SM_CHECK(hipGetLastError());
+    MG_SM_CHECK(hipMemcpyAsync(bound, out.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MG_SM_CHECK(hipStreamSynchronize(ctx->stream));
+    return BIS_OK;
+}
+
+// lambda_steps of the power iteration on W A in the W^-1 inner product, by the blocking single-vector calls
+bis_status level_estimate(bis_ctx *ctx, const bis_mg_level &L, int steps, double *estimate) {
+    const int64_t n = L.n;
+    DevBuf v, y, t;
+    const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(n, 2);
+    MG_SM_CHECK(v.alloc(bytes));
+    MG_SM_CHECK(y.alloc(bytes));
+    MG_SM_CHECK(t.alloc(bytes));
+    hipLaunchKernelGGL(mg_hash_vector_kernel, dim3(mg_grid(n)), dim3(kMgT), 0, ctx->stream, v.as<double>(), n);
+    MG_SM_CHECK(hipGetLastError());
+    double lambda = 0.0;
+    for (int k = 0; k < steps; ++k) {
+        double num = 0.0, den = 0.0, nn = 0.0;
+        if (bis_status st = bis_spmv(ctx, L.A, v.as<double>(), y.as<double>())) return st;
+        if (bis_status st = bis_dot(ctx, v.as<double>(), y.as<double>(), n, &num)) return st;
+        if (bis_status st = bis_elemwise_div_vectors(ctx, t.as<double>(), v.as<double>(), L.w, n, 1.0)) return st;
+        if (bis_status st = bis_dot(ctx, v.as<double>(), t.as<double>(), n, &den)) return st;
+        lambda = num / den;
+        if (bis_status st = bis_elemwise_mult_vectors(ctx, v.as<double>(), L.w, y.as<double>(), n, 1.0)) return st;
+        if (bis_status st = bis_dot(ctx, v.as<double>(), v.as<double>(), n, &nn)) return st;
+        if (bis_status st = bis_scale(ctx, v.as<double>(), v.as<double>(), 1.0 / std::sqrt(nn), n)) return st;
+    }
+    MG_SM_CHECK(hipStreamSynchronize(ctx->stream)); // (the temporaries go out of scope)
+    *estimate = lambda;
+    return BIS_OK;
+}
+
+// the header's recurrence, every operation its own rounded step (hipcc contracts host code by default)
+void cheb_coefficients(double lmax, double lmin, int degree, double *c1, double *c2) {
+#pragma clang fp contract(off)
+    const double theta = (lmax + lmin) / 2.0;
+    const double delta = (lmax - lmin) / 2.0;
+    const double sigma = theta / delta;
+    double rho = 1.0 / sigma;
+    c1[0] = 0.0;
+    c2[0] = 1.0 / theta;
+    for (int k = 1; k < degree; ++k) {
+        const double two_sigma = 2.0 * sigma;
+        const double rho_new = 1.0 / (two_sigma - rho);
+        c1[k] = rho_new * rho;
+        const double two_rho = 2.0 * rho_new;
+        c2[k] = two_rho / delta;
+        rho = rho_new;
+    }
+}
+
+void smoother_to_jacobi(bis_mg *mg) {
+    for (bis_mg_level &L : mg->lv) {
+        hipFree(L.cd);
+        L.cd = nullptr;
+        L.cheb_degree = 0;
+    }
+    mg->sm = bis_mg_smoother{BIS_MG_SMOOTH_JACOBI, 0, 0.0, 0, 0.0};
+}
+
+bis_status smoother_setup(bis_ctx *ctx, bis_mg *mg, const bis_mg_smoother &s) {
+    for (bis_mg_level &L : mg->lv) {
+        if (L.n == 0) continue;
+        double bound = 0.0, lambda = 0.0;
+        if (bis_status st = level_bound(ctx, L, &bound)) return st;
+        if (!(bound > 0.0) || !(bound <= DBL_MAX)) {
+            ctx->err = "bis_mg_set_smoother: the bound on the spectrum of W A is not a positive finite number";
+            return BIS_ERR_INVALID;
+        }
+        if (s.est_steps > 0)
+            if (bis_status st = level_estimate(ctx, L, s.est_steps, &lambda)) return st;
+        const double estimate = (lambda > 0.0 && lambda <= DBL_MAX) ? lambda : 0.0;
+        L.sp_bound = bound;
+        L.sp_estimate = estimate;
+        L.sp_lmax = estimate == 0.0 ? bound : std::min(bound, s.safety * estimate);
+        L.sp_lmin = L.sp_lmax / s.ratio;
+        cheb_coefficients(L.sp_lmax, L.sp_lmin, s.degree, L.cheb_c1, L.cheb_c2);
+        MG_SM_CHECK(hipMalloc(&L.cd, sizeof(double) * (size_t)std::max<int64_t>(L.n, 2)));
+    }
+    return BIS_OK;
+}
+#undef MG_SM_CHECK
 
 } // namespace
 
@@ -1090,6 +1360,55 @@ bis_status bis_mg_cycle(const bis_mg *mg, int *cycle, int *cycle_levels) {
     if (!mg) return BIS_ERR_INVALID;
     if (cycle) *cycle = mg->cycle;
     if (cycle_levels) *cycle_levels = mg->cycle_levels;
+    return BIS_OK;
+}
+
+bis_status bis_mg_set_smoother(bis_ctx *ctx, bis_mg *mg, const bis_mg_smoother *smoother) {
+    BIS_CTX_OK(ctx);
+    BIS_REQUIRE(ctx, mg && smoother, "bis_mg_set_smoother: bad arguments");
+    const bis_mg_smoother s = *smoother;
+    BIS_REQUIRE(ctx, s.kind == BIS_MG_SMOOTH_JACOBI || s.kind == BIS_MG_SMOOTH_CHEBYSHEV, "bis_mg_set_smoother: kind 0 (Jacobi) or 1 (Chebyshev)");
+    if (s.kind == BIS_MG_SMOOTH_CHEBYSHEV)
+        BIS_REQUIRE(ctx, s.degree >= 1 && s.degree <= kMgMaxDegree && s.ratio > 1.0 && s.ratio <= DBL_MAX && s.est_steps >= 0 && s.est_steps <= 100 &&
+                             s.safety >= 1.0 && s.safety <= DBL_MAX,
+                    "bis_mg_set_smoother: degree 1..8, ratio > 1 and finite, est_steps 0..100, safety >= 1 and finite");
+    hipError_t e = hipStreamSynchronize(ctx->stream); // applies in flight read the scratch that may go
+    if (e != hipSuccess) { ctx->err = std::string("bis_mg_set_smoother: ") + hipGetErrorString(e); return BIS_ERR_HIP; }
+    smoother_to_jacobi(mg); // (what holds if something below fails)
+    if (s.kind == BIS_MG_SMOOTH_JACOBI) return BIS_OK;
+    if (bis_status st = smoother_setup(ctx, mg, s)) {
+        hipStreamSynchronize(ctx->stream);
+        smoother_to_jacobi(mg);
+        return st;
+    }
+    for (bis_mg_level &L : mg->lv) L.cheb_degree = L.n ? s.degree : 0;
+    mg->sm = s;
+    return BIS_OK;
+}
+
+bis_status bis_mg_smoother_info(const bis_mg *mg, bis_mg_smoother *out) {
+    if (!mg || !out) return BIS_ERR_INVALID;
+    *out = mg->sm;
+    return BIS_OK;
+}
+
+bis_status bis_mg_level_spectrum(const bis_mg *mg, int level, double *bound, double *estimate, double *lambda_max, double *lambda_min) {
+    if (!mg || mg->sm.kind != BIS_MG_SMOOTH_CHEBYSHEV || level < 0 || (size_t)level >= mg->lv.size()) return BIS_ERR_INVALID;
+    const bis_mg_level &L = mg->lv[(size_t)level];
+    if (bound) *bound = L.sp_bound;
+    if (estimate) *estimate = L.sp_estimate;
+    if (lambda_max) *lambda_max = L.sp_lmax;
+    if (lambda_min) *lambda_min = L.sp_lmin;
+    return BIS_OK;
+}
+
+bis_status bis_mg_level_cheb_coeffs(const bis_mg *mg, int level, double *c1, double *c2) {
+    if (!mg || mg->sm.kind != BIS_MG_SMOOTH_CHEBYSHEV || level < 0 || (size_t)level >= mg->lv.size()) return BIS_ERR_INVALID;
+    const bis_mg_level &L = mg->lv[(size_t)level];
+    for (int k = 0; k < mg->sm.degree; ++k) {
+        if (c1) c1[k] = L.cheb_c1[k];
+        if (c2) c2[k] = L.cheb_c2[k];
+    }
     return BIS_OK;
 }
 

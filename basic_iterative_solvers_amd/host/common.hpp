@@ -70,6 +70,9 @@ inline MGCycle &precond_mg_cycle() { static MGCycle c; return c; }
 // -mg smooth=1[,pomega=X]: smoothed aggregation (bis_mg_create_smoothed) with the prolongator's factor X in (0, 2); 0: the library's 4/3
 struct MGSmooth { bool smooth = false; double pomega = 0.0; };
 inline MGSmooth &precond_mg_smooth() { static MGSmooth s; return s; }
+// -mg smoother=jacobi|cheb[,degree=N,ratio=X,est=S,safety=X]: the smoother of -p mg (bis_mg_set_smoother); ratio 4 is the
+// default the CPU table of docs/EXPERIMENTS.md chose; without smoother=cheb nothing is called
+inline bis_mg_smoother &precond_mg_smoother() { static bis_mg_smoother s = {BIS_MG_SMOOTH_JACOBI, 2, 4.0, 10, 1.1}; return s; }
 // -bs N: rows per block of -p bj (bis_bj_params.block_size); 0: not given, the dof of the matrix' grid hint where that is above 1
 inline int &precond_block_size() { static int b = 0; return b; }
 // -fill K: level-of-fill of -p ilu0 / -p ilu0it (bis_mat_iluk); 0, the default, is ILU(0) as it always ran

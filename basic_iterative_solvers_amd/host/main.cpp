@@ -1,7 +1,7 @@
 // main.cpp -- CLI driver of the MI355X build; same command line and the same
 // stdout (residual table, summary, timer tree) as the reference's main.cpp.
 //   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-idr [-ids S]|-bi>
-//        [-p j|gs|bgs|sgs|2st|s2st|ilu0|ilu0it|fsai|mg|bj] [-mg KEY=VALUE,... (nu, cs, limit, levels, scale, omega, coarsening, cycle=v|w|k|kgcr, klev, smooth=0|1, pomega)] [-bs N] [-fill K (level-of-fill of ilu0 / ilu0it, 0..16)] [-inner K] [-pprec 32|64] [-scale 0|1] [-rl N] [-unfused] [-dev K]
+//        [-p j|gs|bgs|sgs|2st|s2st|ilu0|ilu0it|fsai|mg|bj] [-mg KEY=VALUE,... (nu, cs, limit, levels, scale, omega, coarsening, cycle=v|w|k|kgcr, klev, smooth=0|1, pomega, smoother=jacobi|cheb, degree, ratio, est, safety)] [-bs N] [-fill K (level-of-fill of ilu0 / ilu0it, 0..16)] [-inner K] [-pprec 32|64] [-scale 0|1] [-rl N] [-unfused] [-dev K]
 #include <chrono>
 
 #include "common.hpp"

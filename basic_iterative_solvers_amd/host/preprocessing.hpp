@@ -147,6 +147,20 @@ inline void factor_LU(Solver *s) {
             else std::cout << "none (the hierarchy has fewer than three levels: the V-cycle)";
             std::cout << std::endl;
         }
+        const bis_mg_smoother &smo = precond_mg_smoother();
+        if (smo.kind == BIS_MG_SMOOTH_CHEBYSHEV) { // (a command line without smoother=cheb prints and computes what it always did)
+            const bis_status sst = bis_mg_set_smoother(bis::ctx(), s->mg, &smo);
+            if (sst == BIS_ERR_INVALID) { fprintf(stderr, "%s\n", bis_last_error(bis::ctx())); exit(EXIT_FAILURE); }
+            bis::check(sst, "bis_mg_set_smoother");
+            std::cout << "multigrid smoother: Chebyshev, degree " << smo.degree << ", ratio " << smo.ratio << ", est " << smo.est_steps << ", safety "
+                      << smo.safety << ", lambda_max";
+            for (int l = 0; l < levels; ++l) {
+                double lmax = 0.0;
+                bis_mg_level_spectrum(s->mg, l, nullptr, nullptr, &lmax, nullptr);
+                std::cout << (l ? " / " : " ") << lmax;
+            }
+            std::cout << std::endl;
+        }
     }
     if (s->preconditioner == PrecondType::BlockJacobi) factor_block_jacobi(s);
 }

@@ -71,7 +71,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                                 "\n-p s2st (Symmetric 2 Stage Gauss-Seidel)\n-p ilu0 (Incomplete LU with 0 fill-in)"
                                 "\n-p ilu0it (Incomplete LU with 0 fill-in, -inner K Jacobi-Richardson steps per triangular solve)"
                                 "\n-p fsai (Factorized sparse approximate inverse on the pattern of tril(A))"
-                                "\n-p mg (Aggregation multigrid cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=0,smooth=0|1,pomega=X)"
+                                "\n-p mg (Aggregation multigrid cycle, -mg nu=1,cs=4,limit=256,levels=10,scale=1,omega=0,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=0,smooth=0|1,pomega=X,smoother=jacobi|cheb,degree=2,ratio=4,est=10,safety=1.1)"
                                 "\n-p bj (Block Jacobi on blocks of -bs N consecutive rows, N = 1..32; default: the dof of the grid hint)\n");
                 exit(EXIT_FAILURE);
             }
@@ -127,8 +127,9 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else if (arg == "-mg" && i + 1 < argc) {
             bis_mg_params &p = precond_mg_params();
             std::stringstream ss(argv[++i]);
-            std::string item, pomega_item;
-            const char *mg_keys = "ERROR: -mg nu=K,cs=K,limit=N,levels=K,scale=S,omega=W,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=N,smooth=0|1,pomega=X (0 < X < 2, with smooth=1): cannot read \"%s\"\n";
+            std::string item, pomega_item, cheb_item;
+            const char *mg_keys = "ERROR: -mg nu=K,cs=K,limit=N,levels=K,scale=S,omega=W,coarsening=auto|grid|mis,cycle=v|w|k|kgcr,klev=N,smooth=0|1,pomega=X (0 < X < 2, with smooth=1),smoother=jacobi|cheb,degree=N (1..8),ratio=X (> 1),est=S (0..100),safety=X (>= 1) (the last four with smoother=cheb): cannot read \"%s\"\n";
+            const auto digits = [](const std::string &t) { return t.find_first_not_of("0123456789") == std::string::npos; };
             while (std::getline(ss, item, ',')) {
                 const size_t eq = item.find('=');
                 const std::string k = item.substr(0, eq), v = eq == std::string::npos ? "" : item.substr(eq + 1);
@@ -145,11 +146,21 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 else if (k == "klev" && v.find_first_not_of("0123456789") == std::string::npos) precond_mg_cycle().levels = atoi(v.c_str());
                 else if (k == "smooth" && (v == "0" || v == "1")) precond_mg_smooth().smooth = v == "1";
                 else if (k == "pomega" && atof(v.c_str()) > 0.0 && atof(v.c_str()) < 2.0) { precond_mg_smooth().pomega = atof(v.c_str()); pomega_item = item; }
+                else if (k == "smoother" && (v == "jacobi" || v == "cheb"))
+                    precond_mg_smoother().kind = v == "cheb" ? BIS_MG_SMOOTH_CHEBYSHEV : BIS_MG_SMOOTH_JACOBI;
+                else if (k == "degree" && digits(v) && atoi(v.c_str()) >= 1 && atoi(v.c_str()) <= 8) { precond_mg_smoother().degree = atoi(v.c_str()); cheb_item = item; }
+                else if (k == "ratio" && atof(v.c_str()) > 1.0 && std::isfinite(atof(v.c_str()))) { precond_mg_smoother().ratio = atof(v.c_str()); cheb_item = item; }
+                else if (k == "est" && digits(v) && atoi(v.c_str()) <= 100) { precond_mg_smoother().est_steps = atoi(v.c_str()); cheb_item = item; }
+                else if (k == "safety" && atof(v.c_str()) >= 1.0 && std::isfinite(atof(v.c_str()))) { precond_mg_smoother().safety = atof(v.c_str()); cheb_item = item; }
                 else ok = false;
                 if (!ok) {
                     fprintf(stderr, mg_keys, item.c_str());
                     exit(EXIT_FAILURE);
                 }
+            }
+            if (!cheb_item.empty() && precond_mg_smoother().kind != BIS_MG_SMOOTH_CHEBYSHEV) { // a key of a smoother that is not chosen
+                fprintf(stderr, mg_keys, cheb_item.c_str());
+                exit(EXIT_FAILURE);
             }
             if (!pomega_item.empty() && !precond_mg_smooth().smooth) { // the factor of a prolongator that is not smoothed
                 fprintf(stderr, mg_keys, pomega_item.c_str());

@@ -577,6 +577,54 @@ BIS_API bis_status bis_mg_create_smoothed(bis_ctx *ctx, const bis_mat *A, const 
 BIS_API const bis_mat *bis_mg_level_prolongator(const bis_mg *mg, int level);
 BIS_API const bis_mat *bis_mg_level_restrictor(const bis_mg *mg, int level);
 BIS_API bis_status bis_mg_level_prolong_omega(const bis_mg *mg, int level, double *omega_l);
+/* The smoother of an existing hierarchy (a fresh one relaxes with its weights w: BIS_MG_SMOOTH_JACOBI, the sweeps above).
+ * BIS_MG_SMOOTH_CHEBYSHEV replaces every "sweep" above -- in nu, nu - 1, coarse_sweeps - 1 and the first one from x = 0 -- by
+ * one Chebyshev polynomial of degree `degree` in W A, W = diag(w), built for the interval [lambda_max / ratio, lambda_max]
+ * of every level: as many SpMVs and streaming passes as `degree` Jacobi sweeps, no dependency between rows, and the V- and
+ * W-cycle stay fixed, symmetric positive definite operators.  max_levels = 1 makes the cycle a polynomial preconditioner.
+ *
+ * Spectrum of level l (operator A, weights w, n rows):
+ *   bound = max_i w_i s_i, s_i = sum_j |a_ij| summed left to right in CRS order from 0 (the sum w_i was made from where
+ *   omega = 0), the product rounded.  Gershgorin's bound on the spectrum of W A; per-workgroup maxima, then one pass: exact
+ *   whatever the order.  A bound that is not positive and finite: BIS_ERR_INVALID.
+ *   estimate = 0 for est_steps = 0; otherwise lambda_{est_steps} of the power iteration on W A in the W^-1 inner product, run
+ *   with bis_spmv, bis_dot, bis_elemwise_div_vectors / _mult_vectors (scale 1) and bis_scale: v_i = hash32(i) / 2^32 - 0.5
+ *   (hash32 as above), then per step y = A v;  lambda_k = (v, y) / (v, v / w);  v = w o y;  v = v (1 / sqrt((v, v))).
+ *   A Rayleigh quotient: for SPD A it never exceeds lambda_max(W A).  Not finite or not positive: it counts as 0.
+ *   lambda_max = bound if estimate = 0, otherwise min(bound, safety estimate);  lambda_min = lambda_max / ratio.
+ * Coefficients of level l, on the host in fp64, every operation its own rounded step:
+ *   theta = (lambda_max + lambda_min) / 2, delta = (lambda_max - lambda_min) / 2, sigma = theta / delta, rho_0 = 1 / sigma;
+ *   c1[0] = 0, c2[0] = 1 / theta;  k = 1 .. degree - 1: rho_k = 1 / (2 sigma - rho_{k-1}), c1[k] = rho_k rho_{k-1},
+ *   c2[k] = (2 rho_k) / delta.
+ * One polynomial on the current x, every product, difference and sum rounded separately (no fused multiply-add):
+ *   k = 0 .. degree - 1:  y = A x by bis_spmv;  per row t = b - y, u = w t, d = (c1[k] d) + (c2[k] u), x = x + d;
+ *   at k = 0, d = c2[0] u: the d of an earlier polynomial is not read.
+ *   From x = 0 (the first sweep of every level visit) step 0 needs no SpMV: d = c2[0] (w b), x = d.
+ * The coefficients are fixed when bis_mg_set_smoother returns and travel as kernel arguments.
+ *
+ * bis_mg_set_smoother blocks (it synchronises the stream first), computes the spectrum and the coefficients of every level
+ * and allocates one more vector (d) per level, so bis_mg_apply still allocates nothing and never blocks.  d is live inside
+ * one smoothing call only: the second visit of a level in a W or K transition reuses it.  It composes with bis_mg_set_cycle
+ * in either order, on plain and smoothed hierarchies.  Setting JACOBI frees d and restores Jacobi's bits; for JACOBI the
+ * other fields are ignored.  A failure leaves the hierarchy on Jacobi.
+ * BIS_ERR_INVALID, nothing changed: null arguments, kind outside 0..1, degree outside 1..8, ratio not finite or <= 1,
+ * est_steps outside 0..100, safety not finite or < 1.
+ * bis_mg_smoother_info: what is set (a Jacobi hierarchy reports {0, 0, 0, 0, 0}).  bis_mg_level_spectrum (any pointer may be
+ * NULL) and bis_mg_level_cheb_coeffs (arrays of `degree`; either may be NULL): BIS_ERR_INVALID on a Jacobi hierarchy and
+ * on a level outside the hierarchy. */
+enum { BIS_MG_SMOOTH_JACOBI = 0, BIS_MG_SMOOTH_CHEBYSHEV = 1 };
+typedef struct {
+    int kind;
+    int degree;
+    double ratio;
+    int est_steps;
+    double safety;
+} bis_mg_smoother;
+BIS_API bis_status bis_mg_set_smoother(bis_ctx *ctx, bis_mg *mg, const bis_mg_smoother *smoother);
+BIS_API bis_status bis_mg_smoother_info(const bis_mg *mg, bis_mg_smoother *out);
+BIS_API bis_status bis_mg_level_spectrum(const bis_mg *mg, int level, double *bound, double *estimate, double *lambda_max,
+                                         double *lambda_min);
+BIS_API bis_status bis_mg_level_cheb_coeffs(const bis_mg *mg, int level, double *c1, double *c2);
 
 /* ---- block Jacobi (bis_bjacobi.hip); no reference counterpart -------------------------------------------------------------
  * M^-1 = diag(B_0^-1, B_1^-1, ...): the dense diagonal blocks of A over blocks of consecutive rows, inverted once on the

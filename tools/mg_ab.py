@@ -21,7 +21,11 @@ the device).  Reported per input:
       R (A P)) and the transpose timed alone, with the path each product took;
   (f) iterations and ms of the fused CG to 1e-10 r0 with the smoothed V-cycle against the unsmoothed V, W and K cycles and
       none, sgs, ilu0it (inner 3) and fsai; "best_other" names the fastest leg that is not multigrid.
-(e) and (f) run only when --parts names them.
+  (g) the Chebyshev smoother (bis_mg_set_smoother) at equal SpMVs per cycle: l1-Jacobi at nu = m against one polynomial of degree
+      m at nu = 1, m = 2, 3, with est_steps 10 and 0, on the plain and the smoothed hierarchy (and Jacobi nu = 1 beside them) --
+      iterations and ms of the fused CG to 1e-10 r0, ms of one cycle (median, min and max over the rounds: the spread a
+      comparison with another build has to stay inside), lambda_max per level, and ms of bis_mg_set_smoother itself.
+(e), (f) and (g) run only when --parts names them.  INPUT@rcm solves the reverse Cuthill-McKee reordering of INPUT.
 --json writes the records (meant for profiles/)."""
 import json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,9 +39,15 @@ APPLIES = 10
 
 
 def generate(ctx, spec):
+    spec, _, order = spec.partition("@")
     kind, dims = spec.split(":")
     nums = [int(v) for v in dims.split(",") if "=" not in v]
-    return dict(hpcg=ctx.gen_hpcg, anderson=ctx.gen_anderson, fem=ctx.gen_fem, unstr=ctx.gen_unstr)[kind](*nums)
+    A = dict(hpcg=ctx.gen_hpcg, anderson=ctx.gen_anderson, fem=ctx.gen_fem, unstr=ctx.gen_unstr)[kind](*nums)
+    if order == "rcm":  # what the CLI's -perm rcm solves: the permuted matrix has no grid hint
+        B = ctx.permute(A, ctx.bfs_order(A, rcm=True))
+        A.free()
+        return B
+    return A
 
 
 def timed(ctx, legs, rounds):
@@ -326,6 +336,70 @@ def run_input(spec, parts, rounds, max_iters):
             s.free()
         mgw.free()
         mgk.free()
+
+    if "g" in parts:
+        rec["chebyshev"] = {}
+        out = ctx.alloc(n)
+        for hier, smooth in (("plain", False), ("smoothed", True)):
+            # one hierarchy per nu; the nu = 1 one carries every Chebyshev setting in turn (set before the clock starts)
+            hs = {nu: ctx.mg(A, smooth=smooth, nu=nu) for nu in (1, 2, 3)}
+            solvers = {}
+            for nu, h in hs.items():
+                solvers[nu] = ctx.cg(A, b, x)
+                solvers[nu].set_preconditioner("mg", Ls=h.operand)
+            got, lmax = {}, {}
+
+            def set_jacobi():
+                if hs[1].smoother()["kind"]:
+                    hs[1].set_smoother("jacobi")
+
+            def set_cheb(m, est):
+                def f():
+                    hs[1].set_smoother("cheb", degree=m, est_steps=est)
+                    lmax[f"cheb degree={m} est={est}"] = [hs[1].spectrum(l)["lambda_max"] for l in range(hs[1].levels)]
+                return f
+
+            def solve_leg_g(s, key):
+                def f():
+                    ctx.init_vector(x, 0.0)
+                    s.init(TOL)
+                    done = 0
+                    while done < max_iters:
+                        s.iterate(CHUNK)
+                        done += CHUNK
+                        it, conv, hist = s.status()
+                        if conv or it < done:
+                            break
+                    got[key] = dict(iters=it, converged=conv, last_over_r0=float(hist[-1] / hist[0]) if len(hist) else 0.0)
+                return f
+
+            def apply_leg_g(h):
+                def f():
+                    for _ in range(APPLIES):
+                        h.apply(out, b)
+                return f
+
+            settings = [("jacobi nu=1", 1, set_jacobi)]
+            for m in (2, 3):
+                settings.append((f"jacobi nu={m}", m, None))
+                for est in (10, 0):
+                    settings.append((f"cheb degree={m} est={est}", 1, set_cheb(m, est)))
+            r = summary(timed(ctx, [(k, solve_leg_g(solvers[nu], k), prep) for k, nu, prep in settings], rounds))
+            a = summary(timed(ctx, [(k, apply_leg_g(hs[nu]), prep) for k, nu, prep in settings], rounds), per=APPLIES)
+            setup = summary(timed(ctx, [("set_smoother est=10", lambda: hs[1].set_smoother("cheb", degree=2, est_steps=10)),
+                                        ("set_smoother est=0", lambda: hs[1].set_smoother("cheb", degree=2, est_steps=0))], rounds))
+            rec["chebyshev"][hier] = dict(rows=hs[1].rows, nnz=hs[1].nnz, solve_cg=dict(r, result=got), apply=a, lambda_max=lmax,
+                                          set_smoother=setup)
+            for k, _, _ in settings:
+                print(f"{spec} (g) {hier} {k}: -cg {got[k]['iters']} it {'conv' if got[k]['converged'] else 'NOT conv'} "
+                      f"{r['median_ms'][k]:.2f} ms (min {r['min_ms'][k]:.2f}); one cycle {a['median_ms'][k]:.3f} ms (min {a['min_ms'][k]:.3f}, max "
+                      f"{max(a['rounds'][k]) / APPLIES:.3f})" + (f"; lambda_max {['%.4f' % v for v in lmax[k]]}" if k in lmax else ""), flush=True)
+            print(f"{spec} (g) {hier} set_smoother ms: " + ", ".join(f"{k} {v:.2f}" for k, v in setup["median_ms"].items()), flush=True)
+            for s in solvers.values():
+                s.free()
+            for h in hs.values():
+                h.free()
+        out.free()
 
     if "e" in parts or "f" in parts:
         sm.free()
