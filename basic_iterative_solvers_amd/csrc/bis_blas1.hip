@@ -22,7 +22,6 @@
 namespace {
 
 constexpr int kEwThreads = 256;
-constexpr int kMaxEwBlocks = 16384; // elementwise kernels (no partial sums: the grid is free)
 
 // grid of a reduction (its partials are indexed by block: at most kMaxDotBlocks of them)
 inline int ew_grid(int64_t n_items) {
@@ -46,8 +45,6 @@ __device__ __forceinline__ double2 ld_stream(const double2 *p) {
     return make_double2(v.x, v.y);
 }
 __device__ __forceinline__ double ld_stream(const double *p) { return __builtin_nontemporal_load(p); }
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 enum { OP_SUB, OP_SUM, OP_MUL, OP_DIV };
 

@@ -19,7 +19,7 @@
 // host only enqueues iterations and reads the status when it wants to.  Once
 // the stop test fires, the remaining enqueued passes are no-ops, so the result
 // is exactly the state at the reference's stopping iteration.
-#include "bis_pc.hpp"
+#include "bis_solver.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -33,7 +33,7 @@ int64_t bis_dist_n_local(const bis_dist *d);
 int64_t bis_dist_n_ext(const bis_dist *d);
 bis_status bis_dist_allreduce(bis_ctx *ctx, bis_dist *d, double *buf_dev, int count);
 
-struct bis_cg {
+struct bis_cg : bis_solver_core {
     bis_dist *dist = nullptr;    // non-null: row-partitioned operator
     const bis_mat *A = nullptr;
     const double *A_D = nullptr; // nullptr: no preconditioner
@@ -43,20 +43,16 @@ struct bis_cg {
     double *p = nullptr, *r = nullptr, *z = nullptr, *tmp = nullptr;
     double *sc = nullptr;   // device scalars, see enum below
     double *pap_stage = nullptr; // [kPapBlocks] stage-1 sums of the SpMV's fused partials
-    int *flags = nullptr;   // device: [0] iters, [1] done, [2] converged, [3] iteration at which the stop test fired
-    double *hist = nullptr; // device residual history
-    int hist_cap = 0;
-    int enqueued = 0;
-    bool initialised = false; // bis_cg_init has run: p0 and (r,z) were made with the preconditioner set at that time
-    unsigned *counters = nullptr; // device: arrival tickets of the last-arriver reductions ([0] pap, [1] pass B, [4...] pass B's per-group counters)
-    bis_pc_binding pc; // general preconditioner (bis_cg_set_preconditioner), once set: z = M^-1 r through bis_pc_apply; its tmp is the handle's
+    // flags: [0] iters, [1] done, [2] converged, [3] iteration at which the stop test fired
+    // initialised: p0 and (r,z) were made with the preconditioner set at that time
+    // counters: one set in a layout of its own: [0] pap, [1] pass B, [4...] pass B's per-group counters
+    // pc: the general preconditioner, once set: z = M^-1 r through bis_pc_apply; its tmp is the handle's
 };
 
 namespace {
 
 enum { S_RZ = 0, S_PAP, S_RZ_NEW, S_RR, S_ALPHA, S_BETA, S_STOP, S_COUNT = 8 }; // S_RZ_NEW,S_RR adjacent
-constexpr int kT = 256;
-constexpr int kMaxIters = 1 << 20;
+constexpr int kT = kSolverT;
 
 // (the last-arriver reductions -- publish, fetch, arrive_last, arrive_last2 -- live in bis_internal.hpp: bis_mcg.hip shares them)
 
@@ -228,13 +224,6 @@ __global__ __launch_bounds__(kT) void cg_p_update_kernel(int64_t n, const double
     }
 }
 
-inline int grid_for(int64_t n) {
-    int64_t g = ((n >> 1) + kT - 1) / kT;
-    if (g < 1) g = 1;
-    if (g > kMaxReduceBlocks) g = kMaxReduceBlocks;
-    return (int)g;
-}
-
 } // namespace
 
 extern "C" {
@@ -249,16 +238,13 @@ static bis_status cg_create_common(bis_ctx *ctx, bis_dist *dist, const bis_mat *
     cg->x = x;
     cg->n = dist ? bis_dist_n_local(dist) : A->n_rows;
     const int64_t n_ext = dist ? bis_dist_n_ext(dist) : cg->n; // p is the SpMV input: needs the halo tail
-    cg->hist_cap = 1 << 16;
     bis_status st = bis_vec_alloc(ctx, n_ext, &cg->p);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, cg->n, &cg->r);
     if (st == BIS_OK && A_D) st = bis_vec_alloc(ctx, cg->n, &cg->z);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, cg->n, &cg->tmp);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, S_COUNT, &cg->sc);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, kPapBlocks, &cg->pap_stage);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, cg->hist_cap, &cg->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &cg->flags, 4);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &cg->counters, 4 + kArriveSubs);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, cg, 4, 1, 1, 4 + kArriveSubs);
     if (st != BIS_OK) { bis_cg_destroy(ctx, cg); return st; }
     cg->pc.tmp = cg->tmp; // lent: the binding owns only its work vector
     if (!A_D) cg->z = cg->r; // z aliases r without a preconditioner
@@ -286,7 +272,7 @@ bis_status bis_cg_set_preconditioner(bis_ctx *ctx, bis_cg *cg, int precond_type,
                                      int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (!cg) return bis_pc_no_handle(ctx, "bis_cg", 0, precond_type);
-    return bis_pc_bind(ctx, &cg->pc, {"bis_cg", cg->n, cg->n, 0, cg->initialised || cg->enqueued != 0, cg->dist ? 2 : 1},
+    return bis_pc_bind(ctx, &cg->pc, {"bis_cg", cg->n, cg->n, 0, bis_solver_live(*cg), cg->dist ? 2 : 1},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
                        {{&cg->z, cg->n, cg->z == cg->r}}); // z aliased r (no preconditioner at creation): it needs its own storage now
 }
@@ -301,10 +287,7 @@ bis_status bis_cg_destroy(bis_ctx *ctx, bis_cg *cg) {
     hipFree(cg->tmp);
     hipFree(cg->sc);
     hipFree(cg->pap_stage);
-    hipFree(cg->hist);
-    hipFree(cg->flags);
-    hipFree(cg->counters);
-    bis_pc_release(cg->pc);
+    bis_solver_core_free(cg);
     delete cg;
     return BIS_OK;
 }
@@ -397,13 +380,12 @@ bis_status bis_cg_iterate(bis_ctx *ctx, bis_cg *cg, int n_iters) {
                 "bis_cg_iterate: bad arguments");
     const int64_t n = cg->n;
     if (n == 0) return BIS_OK;
-    const int g = grid_for(n);
+    const int g = bis_pair_grid(n, kMaxReduceBlocks);
     const size_t need = std::max((size_t)2 * kMaxReduceBlocks, // the fused dot's partials, whichever form the SpMV takes
                                  cg->dist ? bis_dist_partials_need(cg->dist) : bis_spmv_partials_bound(cg->A));
     bis_status st = bis_ensure_partials(ctx, need);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = cg->flags;
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, cg->flags);
     // (replaying a captured iteration as a hipGraph was measured and removed: no gain on ROCm 7.2 --
     // HPCG-32/64/128/256: 2.33/4.83/40.6/607 ms of plain launches against 2.66/5.73/42.8/588 ms of replays)
     for (int done = 0; done < n_iters; ++done) {
@@ -420,18 +402,10 @@ bis_status bis_cg_status(bis_ctx *ctx, bis_cg *cg, int *iters, int *converged, d
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, cg, "bis_cg_status: null handle");
     int flags[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, cg->flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *cg, 0, 4, flags)) return st;
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
-    if (hist_host && hist_cap > 0) {
-        int cnt = flags[0] + 1;
-        if (cnt > hist_cap) cnt = hist_cap;
-        if (cnt > cg->hist_cap) cnt = cg->hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, cg->hist, sizeof(double) * (size_t)cnt,
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0) return bis_solver_copy_hist(ctx, *cg, 0, std::min(flags[0] + 1, hist_cap), hist_host);
     return BIS_OK;
 }
 

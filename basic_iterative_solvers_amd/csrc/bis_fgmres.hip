@@ -30,13 +30,10 @@
 // Elementwise and reduction traffic at position n, per row: pass 0 reads W, V_0 (16 B), each of the n middle passes reads W,
 // V_{i-1}, V_i and writes W (32 B), the last reads W, V_n and writes W (24 B), the scale reads W and writes V_{n+1} (16 B):
 // 56 + 32 n bytes, as bis_mgmres_* per column.
-#include "bis_pc.hpp"
+#include "bis_gmres_state.hpp"
+#include "bis_solver.hpp"
 
-#include <algorithm>
-#include <cfloat>
-#include <cmath>
-
-struct bis_fgmres {
+struct bis_fgmres : bis_solver_core { // flags: F_*
     const bis_mat *A = nullptr;
     const double *b = nullptr;
     double *x = nullptr;
@@ -45,116 +42,26 @@ struct bis_fgmres {
     double *V = nullptr;    // m + 1 blocks
     double *Z = nullptr;    // m blocks (null without a preconditioner: Z_n is V_n)
     double *W = nullptr;
-    double *st = nullptr;   // the Givens / least-squares state (fgm_layout)
-    int *flags = nullptr;   // F_*
-    double *hist = nullptr;
-    int hist_cap = 0;
-    int enqueued = 0;
-    unsigned *counters = nullptr; // last-arriver counter sets: Gram-Schmidt passes, residual pass, combine
-    bool initialised = false;
-    bis_pc_binding pc;
+    double *st = nullptr;   // the Givens / least-squares state (gmres_layout)
+    // counters: three last-arriver counter sets: Gram-Schmidt passes, residual pass, combine
 };
 
 namespace {
 
-constexpr int kT = 256;
-constexpr int kMaxRestart = 64;
-constexpr int kMaxIters = 1 << 20;
-constexpr int kMaxEwBlocks = 16384; // bis_blas1.hip's elementwise limit
-constexpr unsigned kCounterSet = 4 + kMaxDotBlocks / kArriveGroup; // top counter, padding, a sub counter per 16 workgroups
+constexpr int kT = kSolverT;
+constexpr unsigned kCounterSet = bis_counter_set_words(kMaxDotBlocks); // every pass that arrives runs on bis_pair_grid(n, kMaxDotBlocks)
 
 // flags: iterations, stopped, converged, the iteration of the stop; x awaits its combine, the steps of that combine, history
 // entries written, steps done in the current cycle
 enum { F_ITERS = 0, F_DONE, F_CONV, F_STOP_IT, F_PENDING, F_STEPS, F_NHIST, F_POS, F_COUNT };
 
-// the state, in doubles: h (m + 1: the current Hessenberg column, then rotated in place), cs (m), sn (m), g (m + 1), y (m),
-// the y of bis_fgmres_solution (m), 1 / norm for the scale, beta, threshold, the rotated triangle (m x m, entry (r, c) at c m + r)
-struct fgm_layout {
-    int m;
-    __host__ __device__ int h() const { return 0; }
-    __host__ __device__ int cs() const { return m + 1; }
-    __host__ __device__ int sn() const { return 2 * m + 1; }
-    __host__ __device__ int g() const { return 3 * m + 1; }
-    __host__ __device__ int y() const { return 4 * m + 2; }
-    __host__ __device__ int ysol() const { return 5 * m + 2; }
-    __host__ __device__ int inv() const { return 6 * m + 2; }
-    __host__ __device__ int beta() const { return 6 * m + 3; }
-    __host__ __device__ int stop() const { return 6 * m + 4; }
-    __host__ __device__ int rt() const { return 6 * m + 5; }
-    __host__ __device__ int size() const { return 6 * m + 5 + m * m; }
-};
-
-// y_r = (g_r - sum_{c > r} R_rc y_c) / R_rr for r = steps - 1 .. 0
-__device__ void fgm_backsub(const fgm_layout L, const double *s, int steps, double *y) {
-    const double *rt = s + L.rt(), *g = s + L.g();
-    for (int r = steps - 1; r >= 0; --r) {
-        double sum = 0.0;
-        for (int c = r + 1; c < steps; ++c) sum = fma(rt[c * L.m + r], y[c], sum);
-        y[r] = (g[r] - sum) / rt[r * L.m + r];
-    }
-}
-
-// the bookkeeping after the sum-of-squares pass of position n: bis_mgmres.hip's mgm_book on the one column
-__device__ void fgm_book(const fgm_layout L, double ss, int n, double *s, int *flags, double *hist, int hist_cap) {
-    double *h = s + L.h(), *cs = s + L.cs(), *sn = s + L.sn(), *g = s + L.g(), *rt = s + L.rt();
-    const int m = L.m;
-    const double hn1 = sqrt(ss);
-    s[L.inv()] = 1.0 / hn1;
-    h[n + 1] = hn1;
-    for (int i = 0; i < n; ++i) { // the stored rotations on the new column
-        const double a = h[i], b = h[i + 1];
-        h[i] = cs[i] * a + sn[i] * b;
-        h[i + 1] = cs[i] * b - sn[i] * a;
-    }
-    const double a = h[n], b = h[n + 1];
-    const double den = sqrt(a * a + b * b);
-    const double c_n = a / den, s_n = b / den;
-    cs[n] = c_n;
-    sn[n] = s_n;
-    for (int i = 0; i < n; ++i) rt[n * m + i] = h[i];
-    rt[n * m + n] = c_n * a + s_n * b;
-    const double gn = g[n];
-    g[n + 1] = -s_n * gn;
-    g[n] = c_n * gn;
-    const double est = fabs(g[n + 1]);
-    const int it = flags[F_ITERS] + 1;
-    flags[F_ITERS] = it;
-    const int nh = flags[F_NHIST];
-    if (nh < hist_cap) hist[nh] = est;
-    flags[F_NHIST] = nh + 1;
-    flags[F_POS] = n + 1;
-    const bool conv = est < s[L.stop()];
-    const bool diverged = est > DBL_MAX || est != est;
-    if (conv || diverged) { flags[F_DONE] = 1; flags[F_CONV] = conv ? 1 : 0; flags[F_STOP_IT] = it; }
-    if (conv || diverged || n + 1 == m) {
-        fgm_backsub(L, s, n + 1, s + L.y());
-        flags[F_STEPS] = n + 1;
-        flags[F_PENDING] = 1;
-    }
-}
-
-// The workgroup's sum goes to partials[blockIdx.x]; returns (in every lane) whether this workgroup arrived last -- its
-// thread 0 then holds, in *total, the sum of all partials: lane t adds the workgroups t, t + 256, ... in index order, the
-// lanes are folded in the fixed order of block_sum.
-__device__ __forceinline__ bool fgm_reduce(double acc, double *lds /*[kT / 64]*/, double *partials, unsigned *counter, double *total) {
-    __shared__ bool last;
-    const double s = block_sum<kT>(acc, lds);
-    if (threadIdx.x == 0) {
-        publish(partials + blockIdx.x, s);
-        last = arrive_last2(counter, counter + 4, blockIdx.x, gridDim.x);
-    }
-    __syncthreads();
-    if (!last) return false;
-    double a = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kT) a += fetch(partials + i);
-    *total = block_sum<kT>(a, lds);
-    return true;
-}
+// gmres_book's words: the column's four are the first four flags, its extra four follow
+static_assert(F_PENDING == 4 + X_PENDING && F_STEPS == 4 + X_STEPS && F_NHIST == 4 + X_NHIST && F_POS == 4 + X_POS, "flag layout");
 
 // One Gram-Schmidt pass at position pos.  MODE 0: h_0 = (W, V_0) (Vnext = V_0).  MODE 1: W -= h_ci Vprev, h_{ci+1} = (W, Vnext).
 // MODE 2: W -= h_ci Vprev, (W, W), and the last workgroup does the bookkeeping (ci = pos).
 template <int MODE>
-__global__ __launch_bounds__(kT) void fgm_gs_kernel(int64_t n, fgm_layout L, int pos, int ci, double *st, int *flags,
+__global__ __launch_bounds__(kT) void fgm_gs_kernel(int64_t n, gmres_layout L, int pos, int ci, double *st, int *flags,
                                                     double *__restrict__ W, const double *__restrict__ Vprev,
                                                     const double *__restrict__ Vnext, double *partials, unsigned *counter,
                                                     double *hist, int hist_cap) {
@@ -191,19 +98,20 @@ __global__ __launch_bounds__(kT) void fgm_gs_kernel(int64_t n, fgm_layout L, int
         }
         acc = fma(w, MODE == 2 ? w : Vnext[n - 1], acc);
     }
-    double total = 0.0;
-    if (!fgm_reduce(acc, lds, partials, counter, &total)) return;
+    const double sums[1] = {acc};
+    double total[1];
+    if (!reduce_last<1>(sums, lds, partials, counter, total)) return;
     // every other workgroup has read its coefficient and the flags before it arrived: they may change now
     if (threadIdx.x != 0) return;
-    if (MODE == 2) fgm_book(L, total, pos, st, flags, hist, hist_cap);
-    else st[L.h() + (MODE == 0 ? 0 : ci + 1)] = total;
+    if (MODE == 2) gmres_book(L, total[0], pos, st, flags, flags + 4, hist, hist_cap);
+    else st[L.h() + (MODE == 0 ? 0 : ci + 1)] = total[0];
 }
 
 // Start of the solve (INIT) and of every later cycle: W = b - W (W holds A x), (W, W), and the last workgroup's
 // bookkeeping -- INIT: the state and the flags cleared, history entry 0, the threshold; both: beta, g, 1 / beta; a restart: the
 // extra history entry and the stop test on beta.
 template <bool INIT>
-__global__ __launch_bounds__(kT) void fgm_resid_kernel(int64_t n, fgm_layout L, double tol, double *st, int *flags,
+__global__ __launch_bounds__(kT) void fgm_resid_kernel(int64_t n, gmres_layout L, double tol, double *st, int *flags,
                                                        const double *__restrict__ b, double *__restrict__ W, double *partials,
                                                        unsigned *counter, double *hist, int hist_cap) {
     __shared__ double lds[kT / 64];
@@ -226,10 +134,11 @@ __global__ __launch_bounds__(kT) void fgm_resid_kernel(int64_t n, fgm_layout L, 
         W[n - 1] = r;
         acc = fma(r, r, acc);
     }
-    double total = 0.0;
-    if (!fgm_reduce(acc, lds, partials, counter, &total)) return;
+    const double sums[1] = {acc};
+    double total[1];
+    if (!reduce_last<1>(sums, lds, partials, counter, total)) return;
     if (threadIdx.x != 0) return;
-    const double norm = sqrt(total);
+    const double norm = sqrt(total[0]);
     if (INIT) {
         for (int q = 0; q < L.size(); ++q) st[q] = 0.0;
         for (int q = 0; q < F_COUNT; ++q) flags[q] = 0;
@@ -252,7 +161,7 @@ __global__ __launch_bounds__(kT) void fgm_resid_kernel(int64_t n, fgm_layout L, 
 }
 
 // Vdst = W (1 / norm)
-__global__ __launch_bounds__(kT) void fgm_scale_kernel(int64_t n, fgm_layout L, const double *__restrict__ st,
+__global__ __launch_bounds__(kT) void fgm_scale_kernel(int64_t n, gmres_layout L, const double *__restrict__ st,
                                                        const int *__restrict__ flags, const double *__restrict__ W,
                                                        double *__restrict__ Vdst) {
     if (flags[F_DONE]) return;
@@ -273,7 +182,7 @@ __global__ __launch_bounds__(kT) void fgm_scale_kernel(int64_t n, fgm_layout L, 
 // the last workgroup clears the pending flag.  SOL: OUT = X + the sum over the steps of the current cycle with the y of
 // fgm_ysol_kernel while the solve is live, OUT = X once it has stopped; nothing of the handle changes.
 template <bool SOL>
-__global__ __launch_bounds__(kT) void fgm_combine_kernel(int64_t n, int64_t ld, fgm_layout L, const double *st, int *flags,
+__global__ __launch_bounds__(kT) void fgm_combine_kernel(int64_t n, int64_t ld, gmres_layout L, const double *st, int *flags,
                                                          const double *__restrict__ Z, const double *X, double *OUT,
                                                          unsigned *counter) {
     __shared__ double ys[kMaxRestart];
@@ -303,22 +212,14 @@ __global__ __launch_bounds__(kT) void fgm_combine_kernel(int64_t n, int64_t ld, 
     }
     if (SOL) return;
     // every workgroup has read the pending flag, the steps and the y before it arrives
-    if (threadIdx.x == 0 && arrive_last2(counter, counter + 4, blockIdx.x, gridDim.x)) flags[F_PENDING] = 0;
+    if (threadIdx.x == 0 && arrive_last_set(counter, blockIdx.x, gridDim.x)) flags[F_PENDING] = 0;
 }
 
 // the y of a live solve at its current position, for bis_fgmres_solution: into the state's ysol
-__global__ void fgm_ysol_kernel(fgm_layout L, double *st, const int *flags) {
+__global__ void fgm_ysol_kernel(gmres_layout L, double *st, const int *flags) {
     if (threadIdx.x != 0 || flags[F_DONE]) return;
-    fgm_backsub(L, st, flags[F_POS], st + L.ysol());
+    gmres_backsub(L, st, flags[F_POS], st + L.ysol());
 }
-
-// one lane per 16 bytes; a reduction's partials are indexed by workgroup
-inline int fgm_grid(int64_t n, int cap) {
-    const int64_t g = ((n >> 1) + kT - 1) / kT;
-    return (int)std::min<int64_t>(std::max<int64_t>(g, 1), cap);
-}
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 } // namespace
 
@@ -335,14 +236,11 @@ bis_status bis_fgmres_create(bis_ctx *ctx, const bis_mat *A, const double *b, do
     s->n = A->n_rows;
     s->ld = (s->n + 1) & ~(int64_t)1;
     s->m = restart_len;
-    s->hist_cap = 1 << 16;
-    const fgm_layout L{restart_len};
+    const gmres_layout L{restart_len};
     bis_status st = bis_vec_alloc(ctx, s->ld * (restart_len + 1), &s->V);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, s->ld, &s->W);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, L.size(), &s->st);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, s->hist_cap, &s->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->flags, F_COUNT);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->counters, 3 * kCounterSet);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, s, F_COUNT, 1, 3, kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) { bis_fgmres_destroy(ctx, s); return st; }
     *out = s;
@@ -354,7 +252,7 @@ bis_status bis_fgmres_set_preconditioner(bis_ctx *ctx, bis_fgmres *s, int precon
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (!s) return bis_pc_no_handle(ctx, "bis_fgmres", 0, precond_type);
-    return bis_pc_bind(ctx, &s->pc, {"bis_fgmres", s->n, s->ld, 0, s->initialised || s->enqueued != 0, 0},
+    return bis_pc_bind(ctx, &s->pc, {"bis_fgmres", s->n, s->ld, 0, bis_solver_live(*s), 0},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
                        {{&s->Z, s->ld * s->m, precond_type != BIS_PC_NONE && !s->Z}});
 }
@@ -363,10 +261,8 @@ bis_status bis_fgmres_destroy(bis_ctx *ctx, bis_fgmres *s) {
     BIS_CTX_OK(ctx);
     if (!s) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *v : {s->V, s->Z, s->W, s->st, s->hist}) hipFree(v);
-    bis_pc_release(s->pc);
-    hipFree(s->flags);
-    hipFree(s->counters);
+    for (double *v : {s->V, s->Z, s->W, s->st}) hipFree(v);
+    bis_solver_core_free(s);
     delete s;
     return BIS_OK;
 }
@@ -374,8 +270,8 @@ bis_status bis_fgmres_destroy(bis_ctx *ctx, bis_fgmres *s) {
 // W holds A x: the residual, its norm and the bookkeeping, then V_0
 static void fgm_start_cycle(bis_ctx *ctx, bis_fgmres *s, bool restart, double tol) {
     const int64_t n = s->n;
-    const fgm_layout L{s->m};
-    const int g = fgm_grid(n, kMaxDotBlocks);
+    const gmres_layout L{s->m};
+    const int g = bis_pair_grid(n, kMaxDotBlocks);
     unsigned *counter = s->counters + kCounterSet;
     if (restart)
         hipLaunchKernelGGL((fgm_resid_kernel<false>), dim3(g), dim3(kT), 0, ctx->stream, n, L, tol, s->st, s->flags, s->b, s->W,
@@ -383,7 +279,7 @@ static void fgm_start_cycle(bis_ctx *ctx, bis_fgmres *s, bool restart, double to
     else
         hipLaunchKernelGGL((fgm_resid_kernel<true>), dim3(g), dim3(kT), 0, ctx->stream, n, L, tol, s->st, s->flags, s->b, s->W,
                            ctx->partials, counter, s->hist, s->hist_cap);
-    hipLaunchKernelGGL(fgm_scale_kernel, dim3(fgm_grid(n, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, n, L, (const double *)s->st,
+    hipLaunchKernelGGL(fgm_scale_kernel, dim3(bis_pair_grid(n, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, n, L, (const double *)s->st,
                        (const int *)s->flags, (const double *)s->W, s->V);
 }
 
@@ -415,13 +311,12 @@ bis_status bis_fgmres_iterate(bis_ctx *ctx, bis_fgmres *s, int n_iters) {
     const int len = s->m;
     if (n == 0) return BIS_OK;
     BIS_REQUIRE(ctx, s->initialised, "bis_fgmres_iterate: call bis_fgmres_init first");
-    const int g = fgm_grid(n, kMaxDotBlocks), g_wide = fgm_grid(n, kMaxEwBlocks);
-    const fgm_layout L{len};
+    const int g = bis_pair_grid(n, kMaxDotBlocks), g_wide = bis_pair_grid(n, kMaxEwBlocks);
+    const gmres_layout L{len};
     const bool pc = s->pc.type != BIS_PC_NONE;
     bis_status st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = s->flags; // the SpMV returns at once when the solve has stopped
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, s->flags); // the SpMV returns at once when the solve has stopped
 #define BIS_FGM_GS(MODE, CI, VPREV, VNEXT)                                                                                     \
     hipLaunchKernelGGL((fgm_gs_kernel<MODE>), dim3(g), dim3(kT), 0, ctx->stream, n, L, pos, CI, s->st, s->flags, s->W,        \
                        (const double *)(VPREV), (const double *)(VNEXT), ctx->partials, s->counters, s->hist, s->hist_cap)
@@ -472,9 +367,9 @@ bis_status bis_fgmres_solution(bis_ctx *ctx, bis_fgmres *s, double *x_out) {
     if (s->n == 0) return BIS_OK;
     BIS_REQUIRE(ctx, aligned16(x_out), "bis_fgmres_solution: x_out must be 16-byte aligned");
     BIS_REQUIRE(ctx, s->initialised, "bis_fgmres_solution: call bis_fgmres_init first");
-    const fgm_layout L{s->m};
+    const gmres_layout L{s->m};
     hipLaunchKernelGGL(fgm_ysol_kernel, dim3(1), dim3(64), 0, ctx->stream, L, s->st, (const int *)s->flags);
-    hipLaunchKernelGGL((fgm_combine_kernel<true>), dim3(fgm_grid(s->n, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, s->n, s->ld, L,
+    hipLaunchKernelGGL((fgm_combine_kernel<true>), dim3(bis_pair_grid(s->n, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, s->n, s->ld, L,
                        (const double *)s->st, s->flags, (const double *)(s->pc.type != BIS_PC_NONE ? s->Z : s->V), (const double *)s->x,
                        x_out, (unsigned *)nullptr);
     BIS_HIP_CHECK(ctx, hipGetLastError());
@@ -486,17 +381,12 @@ bis_status bis_fgmres_status(bis_ctx *ctx, bis_fgmres *s, int *iters, int *conve
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, s, "bis_fgmres_status: null handle");
     int flags[F_COUNT] = {0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, s->flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
-    int cnt = flags[F_NHIST] < s->hist_cap ? flags[F_NHIST] : s->hist_cap;
+    if (bis_status st = bis_solver_read_flags(ctx, *s, 0, F_COUNT, flags)) return st;
+    const int cnt = std::min(flags[F_NHIST], s->hist_cap);
     if (iters) *iters = flags[F_ITERS];
     if (converged) *converged = flags[F_CONV];
     if (n_hist) *n_hist = cnt;
-    if (hist_host && hist_cap > 0) {
-        if (cnt > hist_cap) cnt = hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, s->hist, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0) return bis_solver_copy_hist(ctx, *s, 0, std::min(cnt, hist_cap), hist_host);
     return BIS_OK;
 }
 

@@ -30,13 +30,13 @@
 // nothing reads their results.)
 // Memory: r, v, t and the column blocks P, G, U = (3 s + 3) n doubles (n rounded up to even: every column starts on 16
 // bytes and is an SpMV operand), 96 doubles of state, the history (65536 doubles), plus the preconditioner's scratch.
-#include "bis_pc.hpp"
+#include "bis_solver.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
-struct bis_idr {
+struct bis_idr : bis_solver_core { // flags: [0] iterations, [1] stopped, [2] converged
     const bis_mat *A = nullptr;
     const double *b = nullptr;
     double *x = nullptr;
@@ -45,22 +45,14 @@ struct bis_idr {
     double *r = nullptr, *v = nullptr, *t = nullptr;
     double *P = nullptr, *G = nullptr, *U = nullptr; // s columns of ld doubles each
     double *sc = nullptr; // device state (S_*)
-    int *flags = nullptr; // [0] iterations, [1] stopped, [2] converged
-    double *hist = nullptr;
-    int hist_cap = 0;
-    int enqueued = 0;
-    unsigned *counters = nullptr; // one last-arriver counter set; the reducing passes follow each other on the stream
-    bool initialised = false;
-    bis_pc_binding pc;
+    // counters: one last-arriver counter set; the reducing passes follow each other on the stream
 };
 
 namespace {
 
-constexpr int kT = 256;
+constexpr int kT = kSolverT;
 constexpr int kMaxS = 8;
-constexpr int kMaxIters = 1 << 20;
-constexpr int kMaxEwBlocks = 16384; // bis_blas1.hip's elementwise limit
-constexpr unsigned kCounterSet = 4 + kArriveSubs; // top counter, padding, a sub counter per 16 workgroups
+constexpr unsigned kCounterSet = bis_counter_set_words(kMaxReduceBlocks); // every reducing pass runs on bis_pair_grid(n, kMaxReduceBlocks)
 
 // state: scalars, then c, alpha, f (kMaxS each) and the lower triangle M, row i at S_M + kMaxS i
 enum { S_OMEGA = 0, S_NORM /* || r || */, S_STOP, S_BETA, S_C = 8, S_ALPHA = 16, S_F = 24, S_M = 32, S_COUNT = 96 };
@@ -79,30 +71,6 @@ __global__ __launch_bounds__(kT) void idr_shadow_kernel(double *P, int64_t n, in
         const uint32_t h = idr_hash32(idr_hash32((uint32_t)i) ^ ((uint32_t)(j + 1) * 0x9e3779b9u));
         P[idx] = i < n ? ((double)h + 0.5) * 0x1p-31 - 1.0 : 0.0;
     }
-}
-
-// NV sums at once: the workgroup's sums go to partials[v * gridDim.x + blockIdx.x]; returns (in every lane) whether this
-// workgroup arrived last -- its thread 0 then holds in total[v] the sum of all partials of v: lane t adds the workgroups
-// t, t + 256, ... in index order, the lanes are folded in the fixed order of block_sum.
-template <int NV>
-__device__ __forceinline__ bool idr_reduce(const double (&acc)[NV], double *lds /*[NV * kT / 64]*/, double *partials,
-                                           unsigned *counter, double (&total)[NV]) {
-    __shared__ bool last;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const double sum = block_sum<kT>(acc[v], lds + v * (kT / 64));
-        if (threadIdx.x == 0) publish(partials + (size_t)v * gridDim.x + blockIdx.x, sum);
-    }
-    if (threadIdx.x == 0) last = arrive_last2(counter, counter + 4, blockIdx.x, gridDim.x);
-    __syncthreads();
-    if (!last) return false;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double a = 0.0;
-        for (int i = threadIdx.x; i < (int)gridDim.x; i += kT) a += fetch(partials + (size_t)v * gridDim.x + i);
-        total[v] = block_sum<kT>(a, lds + v * (kT / 64));
-    }
-    return true;
 }
 
 // ---- the small algebra: one lane, every operation rounded on its own ------------------------------------------------
@@ -263,7 +231,7 @@ __global__ __launch_bounds__(kT) void idr_dots_kernel(int64_t n, int64_t ld, dou
         for (int j = 0; j < S; ++j) acc[j] = fma(P[n - 1 + j * ld], g[n - 1], acc[j]);
     }
     double q[S];
-    if (!idr_reduce<S>(acc, lds, partials, counter, q)) return;
+    if (!reduce_last<S>(acc, lds, partials, counter, q)) return;
     if (threadIdx.x != 0) return;
     if (k >= 0) {
         idr_book_q(q, sc, k, S);
@@ -340,7 +308,7 @@ __global__ __launch_bounds__(kT) void idr_w_kernel(int64_t n, int64_t ld, double
         acc[0] = fma(rv, rv, acc[0]);
     }
     double rr[1];
-    if (!idr_reduce<1>(acc, lds, partials, counter, rr)) return;
+    if (!reduce_last<1>(acc, lds, partials, counter, rr)) return;
     // every other workgroup has read its scalars and the stop flag before it arrived: they may change now
     if (threadIdx.x != 0) return;
     idr_book_norm(rr[0], sc, flags, hist, hist_cap);
@@ -367,7 +335,7 @@ __global__ __launch_bounds__(kT) void idr_tt_kernel(int64_t n, double *sc, const
         acc[1] = fma(t[n - 1], r[n - 1], acc[1]);
     }
     double d[2];
-    if (!idr_reduce<2>(acc, lds, partials, counter, d)) return;
+    if (!reduce_last<2>(acc, lds, partials, counter, d)) return;
     if (threadIdx.x != 0) return;
     {
 #pragma clang fp contract(off)
@@ -425,20 +393,12 @@ __global__ __launch_bounds__(kT) void idr_o_kernel(int64_t n, int64_t ld, double
         acc[S] = fma(rv, rv, acc[S]);
     }
     double d[S + 1];
-    if (!idr_reduce<S + 1>(acc, lds, partials, counter, d)) return;
+    if (!reduce_last<S + 1>(acc, lds, partials, counter, d)) return;
     if (threadIdx.x != 0) return;
     idr_book_norm(d[S], sc, flags, hist, hist_cap);
     for (int j = 0; j < S; ++j) sc[S_F + j] = d[j];
     idr_solve_c(sc, 0, S);
 }
-
-// one lane per 16 bytes; a reduction's partials are indexed by workgroup
-inline int idr_grid(int64_t n, int cap) {
-    const int64_t g = ((n >> 1) + kT - 1) / kT;
-    return (int)std::min<int64_t>(std::max<int64_t>(g, 1), cap);
-}
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // LAUNCH(N) with the runtime N as a constant: 1 .. 8 (column counts, s), 0 .. 7 (k)
 #define BIS_IDR_CASES_1_7(LAUNCH)                                                                                              \
@@ -483,19 +443,16 @@ bis_status bis_idr_create(bis_ctx *ctx, const bis_mat *A, const double *b, doubl
     h->n = A->n_rows;
     h->ld = (h->n + 1) & ~(int64_t)1;
     h->s = s;
-    h->hist_cap = 1 << 16;
     bis_status st = BIS_OK;
     for (double **p : {&h->r, &h->v, &h->t})
         if (st == BIS_OK) st = bis_vec_alloc(ctx, h->ld, p);
     for (double **p : {&h->P, &h->G, &h->U})
         if (st == BIS_OK) st = bis_vec_alloc(ctx, h->ld * s, p);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, S_COUNT, &h->sc);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, h->hist_cap, &h->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &h->flags, 4);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &h->counters, kCounterSet);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, h, 4, 1, 1, kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, (size_t)(kMaxS + 1) * kMaxReduceBlocks);
     if (st == BIS_OK && h->n > 0) {
-        hipLaunchKernelGGL(idr_shadow_kernel, dim3(idr_grid(2 * h->ld * s, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, h->P, h->n, h->ld, s);
+        hipLaunchKernelGGL(idr_shadow_kernel, dim3(bis_pair_grid(2 * h->ld * s, kMaxEwBlocks)), dim3(kT), 0, ctx->stream, h->P, h->n, h->ld, s);
         if (hipGetLastError() != hipSuccess) st = BIS_ERR_HIP;
     }
     if (st != BIS_OK) { bis_idr_destroy(ctx, h); return st; }
@@ -508,14 +465,14 @@ bis_status bis_idr_set_preconditioner(bis_ctx *ctx, bis_idr *h, int precond_type
                                       const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (!h) return bis_pc_no_handle(ctx, "bis_idr", 0, precond_type);
-    return bis_pc_bind(ctx, &h->pc, {"bis_idr", h->n, h->ld, 0, h->initialised || h->enqueued != 0, 0},
+    return bis_pc_bind(ctx, &h->pc, {"bis_idr", h->n, h->ld, 0, bis_solver_live(*h), 0},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters}, {});
 }
 
 bis_status bis_idr_set_shadow(bis_ctx *ctx, bis_idr *h, const double *P_host) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, h && (P_host || h->n == 0), "bis_idr_set_shadow: bad arguments");
-    BIS_REQUIRE(ctx, !(h->initialised || h->enqueued != 0), "bis_idr_set_shadow: call it before bis_idr_init / bis_idr_iterate");
+    BIS_REQUIRE(ctx, !bis_solver_live(*h), "bis_idr_set_shadow: call it before bis_idr_init / bis_idr_iterate");
     if (h->n == 0) return BIS_OK;
     BIS_HIP_CHECK(ctx, hipMemcpy2DAsync(h->P, sizeof(double) * (size_t)h->ld, P_host, sizeof(double) * (size_t)h->n,
                                         sizeof(double) * (size_t)h->n, (size_t)h->s, hipMemcpyHostToDevice, ctx->stream));
@@ -527,10 +484,8 @@ bis_status bis_idr_destroy(bis_ctx *ctx, bis_idr *h) {
     BIS_CTX_OK(ctx);
     if (!h) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *p : {h->r, h->v, h->t, h->P, h->G, h->U, h->sc, h->hist}) hipFree(p);
-    bis_pc_release(h->pc);
-    hipFree(h->flags);
-    hipFree(h->counters);
+    for (double *p : {h->r, h->v, h->t, h->P, h->G, h->U, h->sc}) hipFree(p);
+    bis_solver_core_free(h);
     delete h;
     return BIS_OK;
 }
@@ -562,7 +517,7 @@ bis_status bis_idr_init(bis_ctx *ctx, bis_idr *h, double tol, double *r0_norm_ho
     BIS_HIP_CHECK(ctx, hipMemcpyAsync(h->sc, sc, sizeof sc, hipMemcpyHostToDevice, ctx->stream));
     BIS_HIP_CHECK(ctx, hipMemcpyAsync(h->flags, flags, sizeof flags, hipMemcpyHostToDevice, ctx->stream));
     BIS_HIP_CHECK(ctx, hipMemcpyAsync(h->hist, &r0, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    idr_launch_dots(ctx, h, -1, h->r, idr_grid(n, kMaxReduceBlocks)); // f = P^T r, c = f (M = I)
+    idr_launch_dots(ctx, h, -1, h->r, bis_pair_grid(n, kMaxReduceBlocks)); // f = P^T r, c = f (M = I)
     BIS_HIP_CHECK(ctx, hipGetLastError());
     BIS_SYNC_CHECK(ctx);
     h->initialised = true;
@@ -576,12 +531,11 @@ bis_status bis_idr_iterate(bis_ctx *ctx, bis_idr *h, int n_iters) {
     const int64_t n = h->n, ld = h->ld;
     if (n == 0) return BIS_OK;
     BIS_REQUIRE(ctx, h->initialised, "bis_idr_iterate: call bis_idr_init first");
-    const int s = h->s, g = idr_grid(n, kMaxReduceBlocks), g_wide = idr_grid(n, kMaxEwBlocks);
+    const int s = h->s, g = bis_pair_grid(n, kMaxReduceBlocks), g_wide = bis_pair_grid(n, kMaxEwBlocks);
     const bool pc = h->pc.type != BIS_PC_NONE;
     bis_status st = bis_ensure_partials(ctx, (size_t)(kMaxS + 1) * kMaxReduceBlocks);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = h->flags; // the SpMV returns at once when the solve has stopped
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, h->flags); // the SpMV returns at once when the solve has stopped
     const int *flags = h->flags;
     const double *sc = h->sc;
     for (int done = 0; done < n_iters; ++done) {
@@ -644,17 +598,10 @@ bis_status bis_idr_status(bis_ctx *ctx, bis_idr *h, int *iters, int *converged, 
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, h, "bis_idr_status: null handle");
     int flags[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, h->flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *h, 0, 4, flags)) return st;
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
-    if (hist_host && hist_cap > 0 && h->initialised) {
-        int cnt = flags[0] + 1;
-        if (cnt > hist_cap) cnt = hist_cap;
-        if (cnt > h->hist_cap) cnt = h->hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, h->hist, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0 && h->initialised) return bis_solver_copy_hist(ctx, *h, 0, std::min(flags[0] + 1, hist_cap), hist_host);
     return BIS_OK;
 }
 

@@ -61,8 +61,9 @@ struct bis_ctx {
 
     std::map<std::string, bis_named_kernel> kernels; // named-kernel registry (SMAX protocol)
 
-    // set by bis_cg_iterate around its launches: the fused-dot SpMV returns at once when
-    // flags[1] (the solver's stop flag) is set, like the other passes of a stopped iteration
+    // set by every solver handle's *_iterate around its launches (bis_stop_guard, bis_solver.hpp): the SpMV, the SpMM, the
+    // sweeps and the diagonal applies return at once when spmv_stop[1] (the solve's stop flag) is set, like the other
+    // passes of a stopped iteration
     const int *spmv_stop = nullptr;
 
     // profiling
@@ -144,6 +145,8 @@ constexpr int kMaxReduceBlocks = 2048;
 // residual norm: 16 N bytes of two non-temporal read streams move 5.9 TB/s from a grid of 2048, 6.3 from 4096, 6.4 from 8192
 // (tools/blas1_bench.hip).  One constant for all of them: kernels that promise the bits of "ew3 then dot" share the index map.
 constexpr int kMaxDotBlocks = 8192;
+constexpr int kMaxEwBlocks = 16384; // elementwise kernels (no partial sums: the grid is free)
+constexpr int kMaxIters = 1 << 20;  // iterations one solver handle may enqueue between two *_init calls
 constexpr int kWinMaxTiles = 128; // x window: at most 128 tiles of 16 columns (16 KiB of LDS)
 constexpr int kWinTile = 16;
 constexpr int kWinTileLog = 4;
@@ -267,6 +270,9 @@ bis_status bis_fault_check(bis_ctx *ctx);
     do {                                                                       \
         if (!(ctx)) return BIS_ERR_NO_DEVICE;                                  \
     } while (0)
+
+// operands that a kernel loads 16 bytes per lane
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // `count` device words, zeroed on the stream: a handle's flags and arrival counters
 template <class T>

@@ -52,8 +52,6 @@ __global__ __launch_bounds__(kItThreads) void itrsv_epilogue_kernel(double *x, c
     }
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 bis_status launch_epilogue(bis_ctx *ctx, double *x, const double *b, const double *D_inv, int64_t n) {
     const bool vec = aligned16(x) && aligned16(b) && aligned16(D_inv) && n >= 2;
     const int64_t items = vec ? n >> 1 : n;

@@ -5,16 +5,16 @@
 // depend on (n, k, its own data) only.
 #pragma once
 
-#include "bis_internal.hpp"
+#include "bis_solver.hpp"
 
 #include <algorithm>
 
 namespace bis_lockstep {
 
-constexpr int kT = 256;
+constexpr int kT = kSolverT;
 constexpr int kMaxK = 8;
-constexpr int kMaxIters = 1 << 20;
-constexpr unsigned kCounterSet = 4 + kArriveSubs; // one last-arriver counter set (top counter, padding, the sub counters) per reduction
+// one last-arriver counter set per reduction; every reducing pass is launched with lockstep_grid, capped at kMaxReduceBlocks
+constexpr unsigned kCounterSet = bis_counter_set_words(kMaxReduceBlocks);
 
 // per-column sums of a workgroup: lane t < act holds a partial of column t % k; thread 0 publishes the k (or 2 k) sums and
 // takes the ticket.  Returns (in every lane) whether this workgroup arrived last.
@@ -36,7 +36,7 @@ __device__ __forceinline__ bool fold_and_arrive(const double (&v)[NV], int k, in
     __syncthreads();
     if (t == 0) {
         for (int i = 0; i < NV * k; ++i) publish(partials + (size_t)i * stride + blockIdx.x, sums[i]);
-        last = arrive_last2(counter, counter + 3, blockIdx.x, gridDim.x);
+        last = arrive_last_set(counter, blockIdx.x, gridDim.x);
     }
     __syncthreads();
     return last;

@@ -23,12 +23,11 @@
 // breakdown (rho, d1 or d3 reaching 0) gives a non-finite norm, which the divergence test turns into "stopped, not
 // converged" for that column alone.  No kernel here waits for another workgroup: there is the arrive ticket and nothing else.
 #include "bis_lockstep.hpp"
-#include "bis_pc.hpp"
 
 #include <cfloat>
 #include <cmath>
 
-struct bis_mbicgstab {
+struct bis_mbicgstab : bis_solver_core {
     const bis_mat *A = nullptr;
     const double *B = nullptr;
     double *X = nullptr;
@@ -37,14 +36,9 @@ struct bis_mbicgstab {
     // n x k blocks.  Y and St exist with a preconditioner only (without one Y is P and St is S = R's storage)
     double *R = nullptr, *R0 = nullptr, *P = nullptr, *V = nullptr, *Z = nullptr, *Y = nullptr, *St = nullptr;
     double *sc = nullptr;   // [k][B_COUNT]
-    int *flags = nullptr;   // bis_mcg's layout: [1] every column has stopped, [3] the iteration at which the last one did;
-                            // then per column [4 + 4 j ...]: iters, done, converged, iteration at which its stop test fired
-    double *hist = nullptr; // [k][hist_cap]
-    int hist_cap = 0;
-    int enqueued = 0;
-    unsigned *counters = nullptr; // one last-arriver counter set per reduction: passes 1, 3, 4
-    bool initialised = false;
-    bis_pc_binding pc; // its scratch: n x k blocks
+    // flags: bis_mcg's layout: [1] every column has stopped, [3] the iteration at which the last one did; then per column
+    // [4 + 4 j ...]: iters, done, converged, iteration at which its stop test fired.  hist: [k][hist_cap]
+    // counters: one last-arriver counter set per reduction: passes 1, 3, 4.  pc's scratch: n x k blocks
 };
 
 namespace {
@@ -246,16 +240,12 @@ bis_status bis_mbicgstab_create(bis_ctx *ctx, const bis_mat *A, const double *B,
     m->A = A; m->B = B; m->X = X;
     m->n = A->n_rows;
     m->k = n_rhs;
-    m->hist_cap = 1 << 16;
     const int64_t nk = m->n * n_rhs;
-    const size_t n_flags = 4 + 4 * (size_t)n_rhs;
     bis_status st = BIS_OK;
     for (double **v : {&m->R, &m->R0, &m->P, &m->V, &m->Z})
         if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, v);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)B_COUNT * n_rhs, &m->sc);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->flags, n_flags);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->counters, 3 * kCounterSet);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, m, 4 + 4 * (size_t)n_rhs, n_rhs, 3, kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) { bis_mbicgstab_destroy(ctx, m); return st; }
     *out = m;
@@ -269,7 +259,7 @@ bis_status bis_mbicgstab_set_preconditioner(bis_ctx *ctx, bis_mbicgstab *m, int 
     if (!m) return bis_pc_no_handle(ctx, "bis_mbicgstab", 1, precond_type);
     const int64_t nk = m->n * m->k;
     const bool need_blocks = precond_type != BIS_PC_NONE;
-    return bis_pc_bind(ctx, &m->pc, {"bis_mbicgstab", m->n, m->n, m->k, m->initialised || m->enqueued != 0, 0},
+    return bis_pc_bind(ctx, &m->pc, {"bis_mbicgstab", m->n, m->n, m->k, bis_solver_live(*m), 0},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
                        {{&m->Y, nk, need_blocks && !m->Y}, {&m->St, nk, need_blocks && !m->St}});
 }
@@ -278,10 +268,8 @@ bis_status bis_mbicgstab_destroy(bis_ctx *ctx, bis_mbicgstab *m) {
     BIS_CTX_OK(ctx);
     if (!m) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *v : {m->R, m->R0, m->P, m->V, m->Z, m->Y, m->St, m->sc, m->hist}) hipFree(v);
-    bis_pc_release(m->pc);
-    hipFree(m->flags);
-    hipFree(m->counters);
+    for (double *v : {m->R, m->R0, m->P, m->V, m->Z, m->Y, m->St, m->sc}) hipFree(v);
+    bis_solver_core_free(m);
     delete m;
     return BIS_OK;
 }
@@ -336,8 +324,7 @@ bis_status bis_mbicgstab_iterate(bis_ctx *ctx, bis_mbicgstab *m, int n_iters) {
     double *Y = pc ? m->Y : m->P, *St = pc ? m->St : m->R;
     bis_status st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = m->flags; // the SpMM and the sweeps return at once when every column has stopped
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, m->flags); // the SpMM and the sweeps return at once when every column has stopped
     for (int done = 0; done < n_iters; ++done) {
         if (pc) st = bis_pc_apply(ctx, m->pc, n, k, m->Y, m->P);
         if (st == BIS_OK) st = bis_spmm_launch(ctx, m->A, Y, m->V, k);
@@ -367,18 +354,10 @@ bis_status bis_mbicgstab_status(bis_ctx *ctx, bis_mbicgstab *m, int j, int *iter
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, m && j >= 0 && j < m->k, "bis_mbicgstab_status: bad arguments");
     int flags[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, m->flags + 4 + 4 * j, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *m, 4 + 4 * j, 4, flags)) return st;
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
-    if (hist_host && hist_cap > 0) {
-        int cnt = flags[0] + 1;
-        if (cnt > hist_cap) cnt = hist_cap;
-        if (cnt > m->hist_cap) cnt = m->hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, m->hist + (size_t)j * m->hist_cap, sizeof(double) * (size_t)cnt,
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0) return bis_solver_copy_hist(ctx, *m, j, std::min(flags[0] + 1, hist_cap), hist_host);
     return BIS_OK;
 }
 

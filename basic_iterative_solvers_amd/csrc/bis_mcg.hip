@@ -21,13 +21,12 @@
 // pass C.  The sweeps and the elementwise kernels of the apply may still compute a frozen column's z: nothing of that
 // column is read afterwards.  Without the call, the None / Jacobi schedule above is launched exactly as before.
 #include "bis_lockstep.hpp"
-#include "bis_pc.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
-struct bis_mcg {
+struct bis_mcg : bis_solver_core {
     const bis_mat *A = nullptr;
     const double *A_D = nullptr; // nullptr: no preconditioner
     const double *B = nullptr;
@@ -36,14 +35,10 @@ struct bis_mcg {
     int k = 0;
     double *P = nullptr, *R = nullptr, *Z = nullptr, *T = nullptr; // n x k; Z aliases R without a preconditioner
     double *sc = nullptr;   // [k][M_COUNT]
-    int *flags = nullptr;   // [0..3]: [1] every column has stopped, [3] the iteration at which the last one did;
-                            // then per column [4 + 4 j ...]: iters, done, converged, iteration at which its stop test fired
-    double *hist = nullptr; // [k][hist_cap]
-    int hist_cap = 0;
-    int enqueued = 0;
-    unsigned *counters = nullptr; // three last-arriver counter sets (pass A', pass B, the (r,z) pass of a general preconditioner)
-    bool initialised = false;     // bis_mcg_init has run
-    bis_pc_binding pc; // general preconditioner (bis_mcg_set_preconditioner), once set: Z = M^-1 R through bis_pc_apply; its scratch: n x k blocks
+    // flags: [0..3]: [1] every column has stopped, [3] the iteration at which the last one did; then per column
+    // [4 + 4 j ...]: iters, done, converged, iteration at which its stop test fired.  hist: [k][hist_cap]
+    // counters: three last-arriver counter sets (pass A', pass B, the (r,z) pass of a general preconditioner)
+    // pc: the general preconditioner, once set: Z = M^-1 R through bis_pc_apply; its scratch: n x k blocks
 };
 
 namespace {
@@ -280,17 +275,13 @@ bis_status bis_mcg_create(bis_ctx *ctx, const bis_mat *A, const double *A_D, con
     m->A = A; m->A_D = A_D; m->B = B; m->X = X;
     m->n = A->n_rows;
     m->k = n_rhs;
-    m->hist_cap = 1 << 16;
     const int64_t nk = m->n * n_rhs;
-    const size_t n_flags = 4 + 4 * (size_t)n_rhs;
     bis_status st = bis_vec_alloc(ctx, nk, &m->P);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, &m->R);
     if (st == BIS_OK && A_D) st = bis_vec_alloc(ctx, nk, &m->Z);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, &m->T);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)M_COUNT * n_rhs, &m->sc);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->flags, n_flags);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->counters, 3 * kCounterSet);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, m, 4 + 4 * (size_t)n_rhs, n_rhs, 3, kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, (size_t)2 * kMaxK * kMaxReduceBlocks);
     if (st != BIS_OK) { bis_mcg_destroy(ctx, m); return st; }
     if (!A_D) m->Z = m->R; // z aliases r without a preconditioner
@@ -303,7 +294,7 @@ bis_status bis_mcg_set_preconditioner(bis_ctx *ctx, bis_mcg *m, int precond_type
                                       int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (!m) return bis_pc_no_handle(ctx, "bis_mcg", 1, precond_type);
-    return bis_pc_bind(ctx, &m->pc, {"bis_mcg", m->n, m->n, m->k, m->initialised || m->enqueued != 0, 0},
+    return bis_pc_bind(ctx, &m->pc, {"bis_mcg", m->n, m->n, m->k, bis_solver_live(*m), 0},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters},
                        {{&m->Z, m->n * m->k, m->Z == m->R}}); // z aliased r (no preconditioner at creation): it needs its own storage now
 }
@@ -317,10 +308,7 @@ bis_status bis_mcg_destroy(bis_ctx *ctx, bis_mcg *m) {
     if (m->Z != m->R) hipFree(m->Z);
     hipFree(m->T);
     hipFree(m->sc);
-    hipFree(m->hist);
-    hipFree(m->flags);
-    hipFree(m->counters);
-    bis_pc_release(m->pc);
+    bis_solver_core_free(m);
     delete m;
     return BIS_OK;
 }
@@ -373,8 +361,7 @@ bis_status bis_mcg_iterate(bis_ctx *ctx, bis_mcg *m, int n_iters) {
     const int g = lockstep_grid(n, k);
     bis_status st = bis_ensure_partials(ctx, (size_t)2 * kMaxK * kMaxReduceBlocks);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = m->flags; // the SpMM (k == 1: the SpMV) returns at once when every column has stopped
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, m->flags); // the SpMM (k == 1: the SpMV) returns at once when every column has stopped
     for (int done = 0; done < n_iters; ++done) {
         const int it = m->enqueued + done + 1;
         st = bis_spmm_launch(ctx, m->A, m->P, m->T, k);
@@ -407,18 +394,10 @@ bis_status bis_mcg_status(bis_ctx *ctx, bis_mcg *m, int j, int *iters, int *conv
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, m && j >= 0 && j < m->k, "bis_mcg_status: bad arguments");
     int flags[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, m->flags + 4 + 4 * j, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *m, 4 + 4 * j, 4, flags)) return st;
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
-    if (hist_host && hist_cap > 0) {
-        int cnt = flags[0] + 1;
-        if (cnt > hist_cap) cnt = hist_cap;
-        if (cnt > m->hist_cap) cnt = m->hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, m->hist + (size_t)j * m->hist_cap, sizeof(double) * (size_t)cnt,
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0) return bis_solver_copy_hist(ctx, *m, j, std::min(flags[0] + 1, hist_cap), hist_host);
     return BIS_OK;
 }
 

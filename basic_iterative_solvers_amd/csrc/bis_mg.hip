@@ -82,7 +82,7 @@ struct bis_mg {
 namespace {
 
 constexpr int kMgT = 256;
-constexpr int kMgMaxBlocks = 16384; // elementwise passes: the wide grid of bis_blas1.hip's kernels
+constexpr int kMgMaxBlocks = kMaxEwBlocks; // elementwise passes: the wide grid of bis_blas1.hip's kernels
 constexpr int kMgMaxLevels = 16;
 // a transition's device scalars: c1, c2 and the "e_c = 0" flag are adjacent (the combine kernel reads the three)
 enum { MG_SC_C1 = 0, MG_SC_C2, MG_SC_ZERO, MG_SC_S1, MG_SC_RHO1, MG_SC_COUNT };
@@ -91,7 +91,6 @@ constexpr int kMgScBase = 8, kMgScPer = 8;
 typedef double mg_v2d __attribute__((ext_vector_type(2)));
 typedef int mg_v2i __attribute__((ext_vector_type(2)));
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int mg_grid(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + kMgT - 1) / kMgT, kMgMaxBlocks)); }
 
 // ---- the cycle's kernels -----------------------------------------------------------------------------------------------

@@ -27,13 +27,10 @@
 // Elementwise and reduction traffic at position n, per row and column: pass 0 reads W, V_0 (16 B), each of the n middle
 // passes reads W, V_{i-1}, V_i and writes W (32 B), the last reads W, V_n and writes W (24 B), the scale reads W and
 // writes V_{n+1} (16 B): 56 + 32 n bytes.
+#include "bis_gmres_state.hpp"
 #include "bis_lockstep.hpp"
-#include "bis_pc.hpp"
 
-#include <cfloat>
-#include <cmath>
-
-struct bis_mgmres {
+struct bis_mgmres : bis_solver_core {
     const bis_mat *A = nullptr;
     const double *B = nullptr;
     double *X = nullptr;
@@ -41,97 +38,22 @@ struct bis_mgmres {
     int k = 0, m = 0;
     double *V = nullptr;    // m + 1 blocks of n x k
     double *W = nullptr;    // n x k
-    double *st = nullptr;   // [k][state_size(m)]: the per-column Givens / least-squares state (mgm_layout)
-    int *flags = nullptr;   // bis_mcg's layout in the first 4 + 4 k ints; then per column [4 + 4 k + 4 j ...]: pending, steps
-                            // of the pending combine, history entries written, steps done in the current cycle
-    double *hist = nullptr; // [k][hist_cap]
-    int hist_cap = 0;
-    int enqueued = 0;
-    unsigned *counters = nullptr; // last-arriver counter sets: Gram-Schmidt passes, residual / norm passes, combine
-    bool initialised = false;
-    bis_pc_binding pc; // its scratch: n x k blocks
+    double *st = nullptr;   // [k][state_size(m)]: the per-column Givens / least-squares state (gmres_layout)
+    // flags: bis_mcg's layout in the first 4 + 4 k ints; then per column [4 + 4 k + 4 j ...] the X_* words: pending, steps of
+    // the pending combine, history entries written, steps done in the current cycle.  hist: [k][hist_cap].  counters: three
+    // last-arriver counter sets: Gram-Schmidt passes, residual / norm passes, combine.  pc's scratch: n x k blocks
 };
 
 namespace {
 
 using namespace bis_lockstep;
 
-constexpr int kMaxRestart = 64; // bis_multi_axpy's limit
-
-// per-column state, in doubles: h (m + 1: the current Hessenberg column, then rotated in place), cs (m), sn (m), g (m + 1),
-// y (m), the y of bis_mgmres_solution (m), 1 / norm for the scale, beta, threshold, the rotated triangle (m x m, entry
-// (r, c) at c m + r)
-struct mgm_layout {
-    int m;
-    __host__ __device__ int h() const { return 0; }
-    __host__ __device__ int cs() const { return m + 1; }
-    __host__ __device__ int sn() const { return 2 * m + 1; }
-    __host__ __device__ int g() const { return 3 * m + 1; }
-    __host__ __device__ int y() const { return 4 * m + 2; }
-    __host__ __device__ int ysol() const { return 5 * m + 2; }
-    __host__ __device__ int inv() const { return 6 * m + 2; }
-    __host__ __device__ int beta() const { return 6 * m + 3; }
-    __host__ __device__ int stop() const { return 6 * m + 4; }
-    __host__ __device__ int rt() const { return 6 * m + 5; }
-    __host__ __device__ int size() const { return 6 * m + 5 + m * m; }
-};
-
-enum { X_PENDING = 0, X_STEPS, X_NHIST, X_POS };
 enum { BK_INIT0 = 1, BK_BETA = 2, BK_RESTART = 4 };
 
 __device__ __forceinline__ unsigned frozen_mask(const int *flags, int k) {
     unsigned frozen = 0;
     for (int c = 0; c < k; ++c) frozen |= flags[4 + 4 * c + 1] ? 1u << c : 0u;
     return frozen;
-}
-
-// y_r = (g_r - sum_{c > r} R_rc y_c) / R_rr for r = steps - 1 .. 0 (get_explicit_x, gmres.hpp: y[steps] counts as 0)
-__device__ void mgm_backsub(const mgm_layout L, const double *s, int steps, double *y) {
-    const double *rt = s + L.rt(), *g = s + L.g();
-    for (int r = steps - 1; r >= 0; --r) {
-        double sum = 0.0;
-        for (int c = r + 1; c < steps; ++c) sum = fma(rt[c * L.m + r], y[c], sum);
-        y[r] = (g[r] - sum) / rt[r * L.m + r];
-    }
-}
-
-// one column's bookkeeping after the sum-of-squares pass of position n (least_squares, update_g, check_restart)
-__device__ void mgm_book(const mgm_layout L, double ss, int n, double *s, int *fc, int *xc, double *hist, int hist_cap) {
-    double *h = s + L.h(), *cs = s + L.cs(), *sn = s + L.sn(), *g = s + L.g(), *rt = s + L.rt();
-    const int m = L.m;
-    const double hn1 = sqrt(ss);
-    s[L.inv()] = 1.0 / hn1;
-    h[n + 1] = hn1;
-    for (int i = 0; i < n; ++i) { // the stored rotations on the new column
-        const double a = h[i], b = h[i + 1];
-        h[i] = cs[i] * a + sn[i] * b;
-        h[i + 1] = cs[i] * b - sn[i] * a;
-    }
-    const double a = h[n], b = h[n + 1];
-    const double den = sqrt(a * a + b * b);
-    const double c_n = a / den, s_n = b / den;
-    cs[n] = c_n;
-    sn[n] = s_n;
-    for (int i = 0; i < n; ++i) rt[n * m + i] = h[i];
-    rt[n * m + n] = c_n * a + s_n * b;
-    const double gn = g[n];
-    g[n + 1] = -s_n * gn;
-    g[n] = c_n * gn;
-    const double est = fabs(g[n + 1]);
-    const int it = fc[0] + 1;
-    fc[0] = it;
-    const int nh = xc[X_NHIST];
-    if (nh < hist_cap) hist[nh] = est;
-    xc[X_NHIST] = nh + 1;
-    xc[X_POS] = n + 1;
-    const bool conv = est < s[L.stop()];
-    const bool diverged = est > DBL_MAX || est != est;
-    if (conv || diverged) { fc[1] = 1; fc[2] = conv ? 1 : 0; fc[3] = it; }
-    if (conv || diverged || n + 1 == m) {
-        mgm_backsub(L, s, n + 1, s + L.y());
-        xc[X_STEPS] = n + 1;
-        xc[X_PENDING] = 1;
-    }
 }
 
 // flags[1] / flags[3] when the last column has stopped (thread 0 of the last workgroup, after the lanes' bookkeeping)
@@ -148,7 +70,7 @@ __device__ __forceinline__ void mgm_all_stopped(int *flags, int k, const int *sd
 // One Gram-Schmidt pass at position n.  MODE 0: h_0 = (W, V_0) (Vnext = V_0).  MODE 1: W -= h_{ci} Vprev, h_{ci+1} = (W, Vnext).
 // MODE 2: W -= h_{ci} Vprev, (W, W), and the last workgroup does the columns' bookkeeping (ci = n).
 template <int MODE>
-__global__ __launch_bounds__(kT) void mgm_gs_kernel(int64_t n, int k, mgm_layout L, int pos, int ci, double *st, int *flags,
+__global__ __launch_bounds__(kT) void mgm_gs_kernel(int64_t n, int k, gmres_layout L, int pos, int ci, double *st, int *flags,
                                                     double *__restrict__ W, const double *__restrict__ Vprev,
                                                     const double *__restrict__ Vnext, double *partials, size_t stride,
                                                     unsigned *counter, double *hist, int hist_cap) {
@@ -183,7 +105,7 @@ __global__ __launch_bounds__(kT) void mgm_gs_kernel(int64_t n, int k, mgm_layout
         double *s = st + (size_t)t * L.size();
         if (!(frozen >> t & 1u)) {
             if (MODE == 2)
-                mgm_book(L, colsum[t], pos, s, flags + 4 + 4 * t, flags + 4 + 4 * k + 4 * t, hist + (size_t)t * hist_cap, hist_cap);
+                gmres_book(L, colsum[t], pos, s, flags + 4 + 4 * t, flags + 4 + 4 * k + 4 * t, hist + (size_t)t * hist_cap, hist_cap);
             else
                 s[L.h() + (MODE == 0 ? 0 : ci + 1)] = colsum[t];
         }
@@ -198,7 +120,7 @@ __global__ __launch_bounds__(kT) void mgm_gs_kernel(int64_t n, int k, mgm_layout
 // last workgroup's bookkeeping -- BK_INIT0: history entry 0, the threshold, the flags; BK_BETA: beta_j, g_j, 1 / beta_j;
 // BK_RESTART: the extra history entry and the stop test on beta_j.
 template <bool RESID, bool REDUCE>
-__global__ __launch_bounds__(kT) void mgm_resid_kernel(int64_t n, int k, mgm_layout L, int book, double tol, double *st, int *flags,
+__global__ __launch_bounds__(kT) void mgm_resid_kernel(int64_t n, int k, gmres_layout L, int book, double tol, double *st, int *flags,
                                                        const double *__restrict__ Bv, double *__restrict__ W, double *partials,
                                                        size_t stride, unsigned *counter, double *hist, int hist_cap) {
     __shared__ double lds[kT];
@@ -263,7 +185,7 @@ __global__ __launch_bounds__(kT) void mgm_resid_kernel(int64_t n, int k, mgm_lay
 }
 
 // Vdst = W * (1 / norm_j) for the columns that go on (scale, gmres.hpp:44-46)
-__global__ __launch_bounds__(kT) void mgm_scale_kernel(int64_t n, int k, mgm_layout L, const double *__restrict__ st,
+__global__ __launch_bounds__(kT) void mgm_scale_kernel(int64_t n, int k, gmres_layout L, const double *__restrict__ st,
                                                        const int *__restrict__ flags, const double *__restrict__ W,
                                                        double *__restrict__ Vdst) {
     if (flags[1]) return;
@@ -278,7 +200,7 @@ __global__ __launch_bounds__(kT) void mgm_scale_kernel(int64_t n, int k, mgm_lay
 // workgroup clears the pending flags.  SOL: OUT_j = X_j + sum over the steps of the current cycle with the y of
 // mgm_ysol_kernel for a live column, OUT_j = X_j for a stopped one; nothing of the handle changes.
 template <bool SOL>
-__global__ __launch_bounds__(kT) void mgm_combine_kernel(int64_t n, int k, mgm_layout L, const double *st, int *flags,
+__global__ __launch_bounds__(kT) void mgm_combine_kernel(int64_t n, int k, gmres_layout L, const double *st, int *flags,
                                                          const double *__restrict__ V, const double *X, double *OUT,
                                                          unsigned *counter) {
     __shared__ double ys[kMaxK * kMaxRestart];
@@ -314,16 +236,16 @@ __global__ __launch_bounds__(kT) void mgm_combine_kernel(int64_t n, int k, mgm_l
     }
     if (SOL) return;
     // every workgroup has read the pending flags and the y it needs before it arrives
-    if (t == 0 && arrive_last2(counter, counter + 3, blockIdx.x, gridDim.x))
+    if (t == 0 && arrive_last_set(counter, blockIdx.x, gridDim.x))
         for (int c = 0; c < k; ++c) xc[4 * c + X_PENDING] = 0;
 }
 
 // the y of a live column at its current position, for bis_mgmres_solution: lane j, column j, into the state's ysol
-__global__ void mgm_ysol_kernel(int k, mgm_layout L, double *st, const int *flags) {
+__global__ void mgm_ysol_kernel(int k, gmres_layout L, double *st, const int *flags) {
     const int t = threadIdx.x;
     if (t >= k || flags[4 + 4 * t + 1]) return;
     double *s = st + (size_t)t * L.size();
-    mgm_backsub(L, s, flags[4 + 4 * k + 4 * t + X_POS], s + L.ysol());
+    gmres_backsub(L, s, flags[4 + 4 * k + 4 * t + X_POS], s + L.ysol());
 }
 
 constexpr size_t kPartials = (size_t)kMaxK * kMaxReduceBlocks;
@@ -333,7 +255,7 @@ constexpr size_t kStride = (size_t)kMaxReduceBlocks;
 bis_status mgm_start_cycle(bis_ctx *ctx, bis_mgmres *m, bool restart, double tol) {
     const int64_t n = m->n;
     const int k = m->k, g = lockstep_grid(n, k);
-    const mgm_layout L{m->m};
+    const gmres_layout L{m->m};
     const bool pc = m->pc.type != BIS_PC_NONE;
     const int first = restart ? 0 : BK_INIT0, beta = BK_BETA | (restart ? BK_RESTART : 0);
     unsigned *counter = m->counters + kCounterSet;
@@ -369,16 +291,12 @@ bis_status bis_mgmres_create(bis_ctx *ctx, const bis_mat *A, const double *B, do
     m->n = A->n_rows;
     m->k = n_rhs;
     m->m = restart_len;
-    m->hist_cap = 1 << 16;
     const int64_t nk = m->n * n_rhs;
-    const size_t n_flags = 4 + 8 * (size_t)n_rhs;
-    const mgm_layout L{restart_len};
+    const gmres_layout L{restart_len};
     bis_status st = bis_vec_alloc(ctx, nk * (restart_len + 1), &m->V);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, nk, &m->W);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)L.size() * n_rhs, &m->st);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, (int64_t)m->hist_cap * n_rhs, &m->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->flags, n_flags);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &m->counters, 3 * kCounterSet);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, m, 4 + 8 * (size_t)n_rhs, n_rhs, 3, kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) { bis_mgmres_destroy(ctx, m); return st; }
     *out = m;
@@ -390,7 +308,7 @@ bis_status bis_mgmres_set_preconditioner(bis_ctx *ctx, bis_mgmres *m, int precon
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (!m) return bis_pc_no_handle(ctx, "bis_mgmres", 1, precond_type);
-    return bis_pc_bind(ctx, &m->pc, {"bis_mgmres", m->n, m->n, m->k, m->initialised || m->enqueued != 0, 0},
+    return bis_pc_bind(ctx, &m->pc, {"bis_mgmres", m->n, m->n, m->k, bis_solver_live(*m), 0},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters}, {});
 }
 
@@ -398,10 +316,8 @@ bis_status bis_mgmres_destroy(bis_ctx *ctx, bis_mgmres *m) {
     BIS_CTX_OK(ctx);
     if (!m) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *v : {m->V, m->W, m->st, m->hist}) hipFree(v);
-    bis_pc_release(m->pc);
-    hipFree(m->flags);
-    hipFree(m->counters);
+    for (double *v : {m->V, m->W, m->st}) hipFree(v);
+    bis_solver_core_free(m);
     delete m;
     return BIS_OK;
 }
@@ -438,13 +354,12 @@ bis_status bis_mgmres_iterate(bis_ctx *ctx, bis_mgmres *m, int n_iters) {
     if (n == 0) return BIS_OK;
     BIS_REQUIRE(ctx, m->initialised, "bis_mgmres_iterate: call bis_mgmres_init first");
     const int g = lockstep_grid(n, k);
-    const mgm_layout L{len};
+    const gmres_layout L{len};
     const int64_t blk = n * k;
     const bool pc = m->pc.type != BIS_PC_NONE;
     bis_status st = bis_ensure_partials(ctx, kPartials);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = m->flags; // the SpMM and the sweeps return at once when every column has stopped
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, m->flags); // the SpMM and the sweeps return at once when every column has stopped
 #define BIS_MGM_GS(MODE, CI, VPREV, VNEXT)                                                                                     \
     hipLaunchKernelGGL((mgm_gs_kernel<MODE>), dim3(g), dim3(kT), 0, ctx->stream, n, k, L, pos, CI, m->st, m->flags, m->W,     \
                        (const double *)(VPREV), (const double *)(VNEXT), ctx->partials, kStride, m->counters, m->hist, m->hist_cap)
@@ -485,7 +400,7 @@ bis_status bis_mgmres_solution(bis_ctx *ctx, bis_mgmres *m, double *X_out) {
     BIS_REQUIRE(ctx, X_out != m->X, "bis_mgmres_solution: X_out must not be the solve's X");
     if (m->n == 0) return BIS_OK;
     BIS_REQUIRE(ctx, m->initialised, "bis_mgmres_solution: call bis_mgmres_init first");
-    const mgm_layout L{m->m};
+    const gmres_layout L{m->m};
     hipLaunchKernelGGL(mgm_ysol_kernel, dim3(1), dim3(64), 0, ctx->stream, m->k, L, m->st, (const int *)m->flags);
     hipLaunchKernelGGL((mgm_combine_kernel<true>), dim3(lockstep_grid(m->n, m->k)), dim3(kT), 0, ctx->stream, m->n, m->k, L,
                        (const double *)m->st, m->flags, (const double *)m->V, (const double *)m->X, X_out, (unsigned *)nullptr);
@@ -499,19 +414,14 @@ bis_status bis_mgmres_status(bis_ctx *ctx, bis_mgmres *m, int j, int *iters, int
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, m && j >= 0 && j < m->k, "bis_mgmres_status: bad arguments");
     int flags[4] = {0, 0, 0, 0}, ext[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, m->flags + 4 + 4 * j, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(ext, m->flags + 4 + 4 * m->k + 4 * j, sizeof ext, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
-    int cnt = ext[X_NHIST] < m->hist_cap ? ext[X_NHIST] : m->hist_cap;
+    bis_status st = bis_solver_read_flags(ctx, *m, 4 + 4 * j, 4, flags);
+    if (st == BIS_OK) st = bis_solver_read_flags(ctx, *m, 4 + 4 * m->k + 4 * j, 4, ext);
+    if (st != BIS_OK) return st;
+    const int cnt = std::min(ext[X_NHIST], m->hist_cap);
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
     if (n_hist) *n_hist = cnt;
-    if (hist_host && hist_cap > 0) {
-        if (cnt > hist_cap) cnt = hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, m->hist + (size_t)j * m->hist_cap, sizeof(double) * (size_t)cnt,
-                                          hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0) return bis_solver_copy_hist(ctx, *m, j, std::min(cnt, hist_cap), hist_host);
     return BIS_OK;
 }
 

@@ -32,13 +32,13 @@
 // order.  No kernel waits for another workgroup; no floating-point atomics; two runs give the same bits.  After the stop
 // every launch of the schedule returns at once, except pass D of the stopping iteration: x is the iterate the last history
 // entry belongs to.  (Launches of a preconditioner queued behind the stop may still run; nothing reads their results.)
-#include "bis_pc.hpp"
+#include "bis_solver.hpp"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 
-struct bis_minres {
+struct bis_minres : bis_solver_core { // flags: [0] iterations, [1] stopped, [2] converged, [3] the iteration of the stop
     const bis_mat *A = nullptr;
     const double *b = nullptr;
     double *x = nullptr;
@@ -47,43 +47,17 @@ struct bis_minres {
     double *R[3] = {nullptr, nullptr, nullptr}; // r1, r2 and the SpMV's output / y, rotating
     double *W[3] = {nullptr, nullptr, nullptr}; // w1, w2, w, rotating
     double *sc = nullptr;   // device scalars (S_*)
-    int *flags = nullptr;   // [0] iterations, [1] stopped, [2] converged, [3] the iteration of the stop
-    double *hist = nullptr;
-    int hist_cap = 0;
-    int enqueued = 0;
-    unsigned *counters = nullptr; // two last-arriver counter sets: pass B, pass C
-    bool initialised = false;
-    bis_pc_binding pc;
+    // counters: two last-arriver counter sets: pass B, pass C
 };
 
 namespace {
 
-constexpr int kT = 256;
-constexpr int kMaxIters = 1 << 20;
-constexpr int kMaxEwBlocks = 16384; // bis_blas1.hip's elementwise limit
-constexpr unsigned kCounterSet = 4 + kMaxDotBlocks / kArriveGroup; // top counter, padding, a sub counter per 16 workgroups
+constexpr int kT = kSolverT;
+constexpr unsigned kCounterSet = bis_counter_set_words(kMaxDotBlocks); // passes B and C run on bis_pair_grid(n, kMaxDotBlocks)
 
 enum { S_BETA = 0, S_BOB /* beta / oldb */, S_ALPHA, S_AOB /* alpha / beta */, S_DBAR, S_EPSLN, S_PHIBAR, S_CS, S_SN, S_STOP,
        S_OLDEPS, S_DELTA, S_IGAMMA, S_PHI, S_IBETA, S_COUNT = 16 };
 enum { C_NONE = 0, C_JACOBI, C_UPDATE_ONLY, C_DOT_ONLY };
-
-// The workgroup's sum goes to partials[blockIdx.x]; returns (in every lane) whether this workgroup arrived last -- its
-// thread 0 then holds the sum of all partials in *total: lane t adds the workgroups t, t + 256, ... in index order, the
-// lanes are folded in the fixed order of block_sum.
-__device__ __forceinline__ bool mr_reduce(double acc, double *lds /*[kT / 64]*/, double *partials, unsigned *counter, double *total) {
-    __shared__ bool last;
-    const double s = block_sum<kT>(acc, lds);
-    if (threadIdx.x == 0) {
-        publish(partials + blockIdx.x, s);
-        last = arrive_last2(counter, counter + 4, blockIdx.x, gridDim.x);
-    }
-    __syncthreads();
-    if (!last) return false;
-    double a = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kT) a += fetch(partials + i);
-    *total = block_sum<kT>(a, lds);
-    return true;
-}
 
 // the scalar algebra of one iteration after (r2, y) is known: one lane
 __device__ void mr_book(double rzy, double *sc, int *flags, double *hist, int hist_cap) {
@@ -148,11 +122,12 @@ __global__ __launch_bounds__(kT) void mr_b_kernel(int64_t n, int has_r1, double 
         }
         acc0 = fma(v[n - 1], tv, acc0);
     }
-    double total = 0.0;
-    if (!mr_reduce(acc0 + acc1, lds, partials, counter, &total)) return;
+    const double acc[1] = {acc0 + acc1};
+    double total[1];
+    if (!reduce_last<1>(acc, lds, partials, counter, total)) return;
     if (threadIdx.x != 0) return;
-    sc[S_ALPHA] = total;
-    sc[S_AOB] = total / sc[S_BETA];
+    sc[S_ALPHA] = total[0];
+    sc[S_AOB] = total[0] / sc[S_BETA];
 }
 
 // pass C.  C_NONE: t -= (alpha / beta) r2, (t, t).  C_JACOBI: the same, y = t / (1.0 D), (t, y).  C_UPDATE_ONLY: the update
@@ -206,10 +181,11 @@ __global__ __launch_bounds__(kT) void mr_c_kernel(int64_t n, double *sc, int *fl
         }
     }
     if (MODE == C_UPDATE_ONLY) return;
-    double total = 0.0;
-    if (!mr_reduce(acc0 + acc1, lds, partials, counter, &total)) return;
+    const double acc[1] = {acc0 + acc1};
+    double total[1];
+    if (!reduce_last<1>(acc, lds, partials, counter, total)) return;
     // every other workgroup has read its scalars and the stop flag before it arrived: they may change now
-    if (threadIdx.x == 0) mr_book(total, sc, flags, hist, hist_cap);
+    if (threadIdx.x == 0) mr_book(total[0], sc, flags, hist, hist_cap);
 }
 
 // pass D: w = (v - oldeps w1 - delta w2) (1 / gamma); x += phi w; v = y (1 / beta).  `it` = the iteration this launch
@@ -247,14 +223,6 @@ __global__ __launch_bounds__(kT) void mr_d_kernel(int64_t n, const double *__res
     }
 }
 
-// one lane per 16 bytes; a reduction's partials are indexed by workgroup
-inline int mr_grid(int64_t n, int cap) {
-    const int64_t g = ((n >> 1) + kT - 1) / kT;
-    return (int)std::min<int64_t>(std::max<int64_t>(g, 1), cap);
-}
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // pass C reads D 16 bytes per lane: a diagonal off a 16-byte boundary takes the general path (the apply, then the dot pass)
 inline bool fused_jacobi(const bis_minres *s) { return s->pc.type == BIS_PC_JACOBI && s->pc.outer == 1 && aligned16(s->pc.AD); }
 
@@ -271,14 +239,11 @@ bis_status bis_minres_create(bis_ctx *ctx, const bis_mat *A, const double *b, do
     s->A = A; s->b = b; s->x = x;
     s->n = A->n_rows;
     s->ld = (s->n + 1) & ~(int64_t)1;
-    s->hist_cap = 1 << 16;
     bis_status st = bis_vec_alloc(ctx, s->ld, &s->v);
     for (int i = 0; i < 3 && st == BIS_OK; ++i) st = bis_vec_alloc(ctx, s->ld, &s->R[i]);
     for (int i = 0; i < 3 && st == BIS_OK; ++i) st = bis_vec_alloc(ctx, s->ld, &s->W[i]);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, S_COUNT, &s->sc);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, s->hist_cap, &s->hist);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->flags, 4);
-    if (st == BIS_OK) st = bis_alloc_zeroed(ctx, &s->counters, 2 * kCounterSet);
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, s, 4, 1, 2, kCounterSet);
     if (st == BIS_OK) st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) { bis_minres_destroy(ctx, s); return st; }
     *out = s;
@@ -290,7 +255,7 @@ bis_status bis_minres_set_preconditioner(bis_ctx *ctx, bis_minres *s, int precon
                                          const double *U_D, int outer_iters, int inner_iters) {
     BIS_CTX_OK(ctx);
     if (!s) return bis_pc_no_handle(ctx, "bis_minres", 0, precond_type);
-    return bis_pc_bind(ctx, &s->pc, {"bis_minres", s->n, s->ld, 0, s->initialised || s->enqueued != 0, 0},
+    return bis_pc_bind(ctx, &s->pc, {"bis_minres", s->n, s->ld, 0, bis_solver_live(*s), 0},
                        {precond_type, L_strict, U_strict, A_D, A_D_inv, L_D, U_D, outer_iters, inner_iters}, {});
 }
 
@@ -298,10 +263,8 @@ bis_status bis_minres_destroy(bis_ctx *ctx, bis_minres *s) {
     BIS_CTX_OK(ctx);
     if (!s) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    for (double *p : {s->v, s->R[0], s->R[1], s->R[2], s->W[0], s->W[1], s->W[2], s->sc, s->hist}) hipFree(p);
-    bis_pc_release(s->pc);
-    hipFree(s->flags);
-    hipFree(s->counters);
+    for (double *p : {s->v, s->R[0], s->R[1], s->R[2], s->W[0], s->W[1], s->W[2], s->sc}) hipFree(p);
+    bis_solver_core_free(s);
     delete s;
     return BIS_OK;
 }
@@ -348,11 +311,10 @@ bis_status bis_minres_iterate(bis_ctx *ctx, bis_minres *s, int n_iters) {
     const int64_t n = s->n;
     if (n == 0) return BIS_OK;
     BIS_REQUIRE(ctx, s->initialised, "bis_minres_iterate: call bis_minres_init first");
-    const int g = mr_grid(n, kMaxDotBlocks), g_wide = mr_grid(n, kMaxEwBlocks);
+    const int g = bis_pair_grid(n, kMaxDotBlocks), g_wide = bis_pair_grid(n, kMaxEwBlocks);
     bis_status st = bis_ensure_partials(ctx, kMaxDotBlocks);
     if (st != BIS_OK) return st;
-    ctx->spmv_stop = s->flags; // the SpMV returns at once when the solve has stopped
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, s->flags); // the SpMV returns at once when the solve has stopped
     unsigned *cnt_b = s->counters, *cnt_c = s->counters + kCounterSet;
 #define BIS_MR_C(MODE, Y)                                                                                                      \
     hipLaunchKernelGGL((mr_c_kernel<MODE>), dim3(g), dim3(kT), 0, ctx->stream, n, s->sc, s->flags, t, (const double *)r2,     \
@@ -391,17 +353,10 @@ bis_status bis_minres_status(bis_ctx *ctx, bis_minres *s, int *iters, int *conve
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, s, "bis_minres_status: null handle");
     int flags[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, s->flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *s, 0, 4, flags)) return st;
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
-    if (hist_host && hist_cap > 0 && s->initialised) {
-        int cnt = flags[0] + 1;
-        if (cnt > hist_cap) cnt = hist_cap;
-        if (cnt > s->hist_cap) cnt = s->hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, s->hist, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0 && s->initialised) return bis_solver_copy_hist(ctx, *s, 0, std::min(flags[0] + 1, hist_cap), hist_host);
     return BIS_OK;
 }
 

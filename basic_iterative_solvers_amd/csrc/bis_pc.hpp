@@ -1,5 +1,6 @@
 // bis_pc.hpp -- the preconditioner a solver handle keeps from its *_set_preconditioner call (bis_cg, bis_mcg, bis_mbicgstab,
-// bis_mgmres, bis_fgmres, bis_minres): one binding, one table of what a type reads, one check-and-bind, one apply, one
+// bis_mgmres, bis_fgmres, bis_minres, bis_idr -- every handle but bis_stat, which has none; the binding is a member of
+// bis_solver.hpp's bis_solver_core): one binding, one table of what a type reads, one check-and-bind, one apply, one
 // release.  Implemented in bis_precond.hip, next to the dispatcher the table describes.
 #pragma once
 

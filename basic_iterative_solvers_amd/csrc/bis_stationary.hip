@@ -18,12 +18,12 @@
 // Gauss-Seidel / symmetric Gauss-Seidel.  The reference's operations unchanged (tmp = U x; tmp = b -
 // tmp; x = (D+L)^-1 tmp; [the mirrored backward sweep]; tmp = A x; r = b - tmp; ||r||), stream-ordered,
 // with the norm and the stop test on the device instead of a blocking read per iteration.
-#include "bis_internal.hpp"
+#include "bis_solver.hpp"
 
 #include <cfloat>
 #include <cmath>
 
-struct bis_stat {
+struct bis_stat : bis_solver_core { // no counters, no preconditioner binding
     int kind = 0; // BIS_STAT_JACOBI / _GS / _SGS
     const bis_mat *A = nullptr, *L = nullptr, *U = nullptr;
     const double *D = nullptr, *b = nullptr;
@@ -33,11 +33,7 @@ struct bis_stat {
     double *r = nullptr;   // GS: b - A x
     int64_t n = 0;
     double *sc = nullptr;  // device: [0] stopping threshold, [1] sum of squares of the current sample
-    int *flags = nullptr;  // device: [0] iterations done, [1] stopped, [2] converged, [3] stopping iteration
-    double *hist = nullptr;
-    int hist_cap = 1 << 16;
-    int enqueued = 0;
-    bool initialised = false;
+    // flags: [0] iterations done, [1] stopped, [2] converged, [3] stopping iteration
 };
 
 namespace {
@@ -137,7 +133,8 @@ bis_status bis_stat_destroy(bis_ctx *ctx, bis_stat *s) {
     BIS_CTX_OK(ctx);
     if (!s) return BIS_OK;
     hipStreamSynchronize(ctx->stream);
-    hipFree(s->xb); hipFree(s->t); hipFree(s->r); hipFree(s->sc); hipFree(s->flags); hipFree(s->hist);
+    hipFree(s->xb); hipFree(s->t); hipFree(s->r); hipFree(s->sc);
+    bis_solver_core_free(s);
     delete s;
     return BIS_OK;
 }
@@ -158,8 +155,7 @@ bis_status bis_stat_create(bis_ctx *ctx, int kind, const bis_mat *A, const bis_m
     if (st == BIS_OK && kind == BIS_STAT_JACOBI) st = bis_vec_alloc(ctx, s->n, &s->xb);
     if (st == BIS_OK && kind != BIS_STAT_JACOBI) st = bis_vec_alloc(ctx, s->n, &s->r);
     if (st == BIS_OK) st = bis_vec_alloc(ctx, 8, &s->sc);
-    if (st == BIS_OK) st = bis_vec_alloc(ctx, s->hist_cap, &s->hist);
-    if (st == BIS_OK && hipMalloc(&s->flags, sizeof(int) * 4) != hipSuccess) st = BIS_ERR_HIP;
+    if (st == BIS_OK) st = bis_solver_core_alloc(ctx, s, 4, 1, 0, 0);
     if (st != BIS_OK) { bis_stat_destroy(ctx, s); return st; }
     *out = s;
     return BIS_OK;
@@ -195,8 +191,7 @@ bis_status bis_stat_iterate(bis_ctx *ctx, bis_stat *s, int n_iters) {
     BIS_REQUIRE(ctx, s && s->initialised && n_iters >= 0 && s->enqueued + n_iters < s->hist_cap, "bis_stat_iterate: bad arguments");
     const int64_t n = s->n;
     if (n == 0) return BIS_OK;
-    ctx->spmv_stop = s->flags;
-    struct StopGuard { bis_ctx *c; ~StopGuard() { c->spmv_stop = nullptr; } } stop_guard{ctx};
+    bis_stop_guard stop_guard(ctx, s->flags);
     bis_status st = BIS_OK;
     int done = 0;
     for (; done < n_iters && st == BIS_OK; ++done) {
@@ -245,17 +240,10 @@ bis_status bis_stat_status(bis_ctx *ctx, bis_stat *s, int *iters, int *converged
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, s, "bis_stat_status: null handle");
     int flags[4] = {0, 0, 0, 0};
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(flags, s->flags, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *s, 0, 4, flags)) return st;
     if (iters) *iters = flags[0];
     if (converged) *converged = flags[2];
-    if (hist_host && hist_cap > 0) {
-        int cnt = flags[0] + 1;
-        if (cnt > hist_cap) cnt = hist_cap;
-        if (cnt > s->hist_cap) cnt = s->hist_cap;
-        BIS_HIP_CHECK(ctx, hipMemcpyAsync(hist_host, s->hist, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-        BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (hist_host && hist_cap > 0) return bis_solver_copy_hist(ctx, *s, 0, std::min(flags[0] + 1, hist_cap), hist_host);
     return BIS_OK;
 }
 
@@ -264,8 +252,7 @@ bis_status bis_stat_solution(bis_ctx *ctx, bis_stat *s, double *x_out) {
     BIS_CTX_OK(ctx);
     BIS_REQUIRE(ctx, s && x_out, "bis_stat_solution: bad arguments");
     int it = 0;
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(&it, s->flags, sizeof it, hipMemcpyDeviceToHost, ctx->stream));
-    BIS_SYNC_CHECK(ctx);
+    if (bis_status st = bis_solver_read_flags(ctx, *s, 0, 1, &it)) return st;
     const double *src = s->x;
     if (s->kind == BIS_STAT_JACOBI && (it & 1)) src = s->xb; // x_k lives in buffer k mod 2
     if (src != x_out) return bis_copy_vector(ctx, x_out, src, s->n);

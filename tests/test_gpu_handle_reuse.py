@@ -1,5 +1,5 @@
-"""GPU: the solver handles on reuse -- bis_cg_*, bis_mcg_*, bis_mbicgstab_*, bis_mgmres_*, bis_fgmres_*, bis_minres_* and
-bis_stat_* share one life cycle (create, [set_preconditioner], init, iterate ..., status / solution, destroy), and every other
+"""GPU: the solver handles on reuse -- bis_cg_*, bis_mcg_*, bis_mbicgstab_*, bis_mgmres_*, bis_fgmres_*, bis_minres_*,
+bis_idr_* and bis_stat_* share one life cycle (create, [set_preconditioner], init, iterate ..., status / solution, destroy), and every other
 module builds a fresh handle per solve.  Here a handle is used again:
 
 A. `init` a second time on a handle that has converged, that was cut off inside a cycle after 7 iterations, or that was
@@ -9,7 +9,7 @@ A. `init` a second time on a handle that has converged, that was cut off inside 
    makes no other synchronisation of its own between the two.)  The fresh handle's correctness is each solver module's
    business; here one figure anchors the re-initialised run outside the library: the residual of the returned x, recomputed
    in np.longdouble from the host CRS, in the norm the handle's history records (bis_hip.h: the 2-norm of b - A x for
-   bis_cg, bis_mcg, bis_mbicgstab, bis_fgmres, bis_stat and every unpreconditioned handle; || M^-1 (b - A x) ||_2 for a
+   bis_cg, bis_mcg, bis_mbicgstab, bis_fgmres, bis_idr, bis_stat and every unpreconditioned handle; || M^-1 (b - A x) ||_2 for a
    preconditioned bis_mgmres; sqrt((r, M^-1 r)) for a preconditioned bis_minres, M^-1 r by the oracle's apply), is at most the
    last history entry + 1e-10 times entry 0 -- tests/test_gpu_fgmres.py's bound.
 B. Two live handles on one context, advanced one iteration at a time in turn, against the same solves made alone on another
@@ -27,12 +27,13 @@ pytestmark = pytest.mark.gpu
 
 K = 3            # columns of the lock-step handles
 M = 5            # restart length of both GMRES forms
-Q = 7            # the budget stop: odd, no multiple of 3 (MINRES' rotation), no multiple of M (inside a cycle)
+S = 4            # shadow vectors of IDR(s): a cycle of S + 1 positions
+Q = 7            # the budget stop: odd, no multiple of 3 (MINRES' rotation), no multiple of M or S + 1 (inside a cycle)
 BUDGET = 400
 PATTERN = (3, 4, BUDGET)  # the iterate calls of every second solve: call boundaries inside a cycle, then past the stop
 LOCKSTEP = ("mcg", "mbicgstab", "mgmres")
 HAS_SOLUTION = ("mgmres", "fgmres", "stat")
-NONSYMMETRIC = ("mbicgstab", "mgmres", "fgmres")
+NONSYMMETRIC = ("mbicgstab", "mgmres", "fgmres", "idr")
 CONFIGS = {
     "cg": ["none", "A_D", "sgs", "ilu0"],
     "mcg": ["none", "A_D", "sgs"],
@@ -40,14 +41,15 @@ CONFIGS = {
     "mgmres": ["none", "sgs"],
     "fgmres": ["none", "sgs", "sgs-outer2"],
     "minres": ["none", "j", "sgs"],
+    "idr": ["none", "sgs"],
     "stat": ["j", "gs", "sgs"],
 }
 CASES = [(kind, cfg) for kind, cfgs in CONFIGS.items() for cfg in cfgs]
 WIDE_CASES = [("cg", "sgs"), ("mcg", "A_D"), ("mbicgstab", "ilu0"), ("mgmres", "sgs"), ("fgmres", "sgs"), ("minres", "j"),
-              ("stat", "j")]
+              ("idr", "sgs"), ("stat", "j")]
 # b = 0 from x0 = 0: NaN at iteration 1, stopped, not converged -- pinned by tests/test_gpu_mcg.py (bis_cg and bis_mcg),
-# test_gpu_mgmres.py, test_gpu_fgmres.py and test_gpu_minres.py
-ZERO_RHS_PINNED = ("cg", "mcg", "mgmres", "fgmres", "minres")
+# test_gpu_mgmres.py, test_gpu_fgmres.py, test_gpu_minres.py and test_gpu_idr.py
+ZERO_RHS_PINNED = ("cg", "mcg", "mgmres", "fgmres", "minres", "idr")
 
 
 def tol_first(kind, cfg=None):
@@ -138,6 +140,8 @@ class Solve:
             self.h = ctx.fgmres(dA, db, dx, restart=M)
         elif kind == "minres":
             self.h = ctx.minres(dA, db, dx)
+        elif kind == "idr":
+            self.h = ctx.idr(dA, db, dx, s=S)
         else:
             self.h = ctx.stat(cfg, dA, e["D"], db, dx, e["Ls"] if cfg != "j" else None, e["Us"] if cfg != "j" else None)
             pc = None
