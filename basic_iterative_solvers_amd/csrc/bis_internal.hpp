@@ -116,7 +116,7 @@ struct bis_options {
     int trsv_tile_exp = -1;  // tiled sweep, timing experiments (bis_trsv_tiled.hip, TiledArgs::exp_flags); results are wrong with any bit set
     int trsv_tile_edge = -1; // grid-hinted matrices: tile extents in nodes, e (cubic) or ex | ey << 8 | ez << 16 (default by row length; 0 = interval tiles of the natural order)
     int force_rp64 = -1;   // 1: matrices created afterwards get 64-bit row pointers whatever their size (tests of the HPCG-512 code path)
-    int spmv_sellwin = -1; // dictionary SpMV with the block's x window in LDS and sliced-ELL codes (bis_spmv_sell.hip): 0 off (-1: on where the matrix qualifies)
+    int spmv_sellwin = -1; // dictionary SpMV with the block's x window in LDS and sliced-ELL codes (bis_spmv_sellwin.hip): 0 off (-1: on where the matrix qualifies)
     int spmv_sellwin_rows = -1; // rows per lane of the sliced-ELL form: 1 or 2 (blocks of 256 or 512 rows; -1: default 2)
     int spmv_sellwin_pairs = -1; // 0: never the one-byte (column - row, value) pair codes
     int spmv_sellwin_joint = -1; // 0: never the 16-bit joint (slot, value) codes
@@ -150,7 +150,7 @@ constexpr int kMaxIters = 1 << 20;  // iterations one solver handle may enqueue 
 constexpr int kWinMaxTiles = 128; // x window: at most 128 tiles of 16 columns (16 KiB of LDS)
 constexpr int kWinTile = 16;
 constexpr int kWinTileLog = 4;
-constexpr int kSwRows = 256; // window + sliced-ELL forms (bis_spmv_sell.hip): a block is kSwRows R rows, R rows per lane, R = 1, 2 or 4
+constexpr int kSwRows = 256; // window + sliced-ELL forms (bis_winplan.hpp): a block is kSwRows R rows, R rows per lane, R = 1, 2 or 4
 constexpr int kSwMaxR = 4;
 
 struct bis_mat {
@@ -202,18 +202,15 @@ struct bis_mat {
     int32_t *rm_seg = nullptr;  // [rm_blocks * 8]
     int64_t rm_base = 0;
     int rm_state = 0, rm_blocks = 0, rm_kind = 1; // rm_kind 1: 8 windows x 8192 columns per block, 3: 32 windows x 2048 columns
-    // x-window + sliced-ELL form of the dictionary kernel (bis_spmv_sell.hip); state as above
+    // x-window + sliced-ELL form of the dictionary kernel (bis_spmv_sellwin.hip); state as above
     struct bis_sellwin *sw = nullptr;
     int sw_state = 0;
-    // the same plan with the 8-byte values streamed (no dictionary needed): "win8", bis_spmv_sell.hip; state as above
-    struct bis_sellwin *sw8 = nullptr;
+    // the same plan with the values streamed (no dictionary needed), bis_spmv_win8.hip; state as above.  [0]: 8-byte values, "win8";
+    // [1]: 4-byte values, "win4", built only while f32_exact holds
+    struct { struct bis_win8 *p = nullptr; int state = 0; } w8[2];
     std::vector<bis_mat *> *colslabs = nullptr; // column slabs of a matrix without locality (bis_spmv_slab.hip); cs_state: 0 untried, 1 in use, -1 refused
     int cs_state = 0;
     double cs_trial_ms[2] = {0.0, 0.0};        // the build-time trial: one pass / the K passes
-    int sw8_state = 0;
-    // ... and with 4-byte values ("win4"), built only while f32_exact holds; state as above
-    struct bis_sellwin *sw4 = nullptr;
-    int sw4_state = 0;
     // every value of val is exactly representable in binary32: set by bis_mat_round_f32, cleared by bis_mat_scale_sym and
     // bis_mat_retune, inherited by row views (bis_mat_row_view) and by nothing else
     bool f32_exact = false;
@@ -422,7 +419,7 @@ bis_status bis_spmv_build_window(bis_ctx *ctx, bis_mat *A);
 void bis_spmv_drop_packed(bis_mat *A);
 void bis_spmv_drop_valdict(bis_mat *A); // after the values of A changed in place
 bis_status bis_spmv_try_valdict(bis_ctx *ctx, bis_mat *A, bool consecutive_ok);
-// x-window + sliced-ELL dictionary form (bis_spmv_sell.hip)
+// x-window + sliced-ELL dictionary form (bis_spmv_sellwin.hip)
 bis_status bis_spmv_sellwin_try(bis_ctx *ctx, bis_mat *A);
 int bis_spmv_sellwin_blocks(const bis_mat *A);
 int64_t bis_spmv_sellwin_bytes(const bis_mat *A);
@@ -431,8 +428,8 @@ int bis_spmv_sellwin_format(const bis_mat *A);
 bis_status bis_spmv_sellwin_launch(bis_ctx *ctx, const bis_mat *A, const double *x, double *y, int mode, const double *w,
                                    double *partials, const int *stop, int remap_arg, int grid);
 void bis_spmv_sellwin_drop(bis_mat *A);
-// window + sliced-ELL form with the 8-byte values streamed (bis_spmv_sell.hip, "win8")
-// vb: bytes per streamed value -- 8, or 4 for the stream of a matrix flagged f32_exact ("win4", A->sw4); one code path
+// window + sliced-ELL form with the 8-byte values streamed (bis_spmv_win8.hip, "win8")
+// vb: bytes per streamed value -- 8, or 4 for the stream of a matrix flagged f32_exact ("win4", A->w8[1]); one code path
 bis_status bis_spmv_win8_try(bis_ctx *ctx, bis_mat *A, int vb = 8);
 int bis_spmv_win8_blocks(const bis_mat *A, int vb = 8);
 int bis_spmv_win8_rows(const bis_mat *A, int vb = 8);

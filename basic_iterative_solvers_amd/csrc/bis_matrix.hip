@@ -718,9 +718,9 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
     // independent of where x and y lie; tools/win8_place2.py, profiles/r05_f_win8_placement.log): candidates are copies of the
     // stream in fresh allocations, the earlier ones held so that the next lands elsewhere; the search ends at the first
     // candidate of the fast level (bis_spmv_win8_fast; the library runs the same search by itself when it builds the
-    // stream -- bis_spmv_sell.hip w8_tune_placement -- so this normally finds the fast level in place).
+    // stream -- bis_spmv_win8.hip w8_tune_placement -- so this normally finds the fast level in place).
     // The 4-byte stream of a matrix flagged fp32-exact (form 8) is searched the same way, priced on its own bytes.
-    if (st == BIS_OK && (A->sw8_state == 1 || A->sw4_state == 1)) {
+    if (st == BIS_OK && (bis_spmv_win8_blocks(A, 8) > 0 || bis_spmv_win8_blocks(A, 4) > 0)) {
         int w8_form = 0;
         if (bis_mat_spmv_stream_info(ctx, A, nullptr, nullptr, nullptr, &w8_form) == BIS_OK && (w8_form == 6 || w8_form == 8) &&
             bis_spmv_win8_stream_bytes(A, w8_form == 8 ? 4 : 8) > 0) {

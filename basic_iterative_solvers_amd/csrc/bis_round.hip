@@ -4,7 +4,7 @@
 // bytes of their values; the outer Krylov method stays in fp64 and does not need 53 bits of them.  The rounding is the one
 // explicit, lossy step: every value becomes (double)(float)v -- IEEE round to nearest even, subnormals kept, -0.0 kept,
 // NaN / Inf unchanged.  Afterwards the matrix is flagged f32_exact and its SpMV may stream 4-byte values (form 8, "win4",
-// bis_spmv_sell.hip), which on such values is a LOSSLESS re-encoding like every other form: bit-identical y.
+// bis_spmv_win8.hip), which on such values is a LOSSLESS re-encoding like every other form: bit-identical y.
 // Two passes.  The census counts the values that are finite in fp64 and not after the rounding (|v| >= 2^128 - 2^103) and
 // finds max |v32 - v| / |v| over v != 0: per-workgroup partials in index order, then one workgroup -- no floating-point
 // atomics, the same result on every run (as the reductions of bis_blas1.hip).  Only a census without overflow is followed by

@@ -1308,7 +1308,7 @@ static bis_status ensure_packed(bis_ctx *ctx, const bis_mat *A_c, int t, SpmvArg
     return BIS_OK;
 }
 
-// the block map's kernel argument and grid for nb logical blocks (shared with the forms of bis_spmv_sell.hip)
+// the block map's kernel argument and grid for nb logical blocks (shared with the forms of bis_spmv_sellwin.hip and bis_spmv_win8.hip)
 int bis_spmv_remap_arg(int nb) { return remap_arg_for((nb + 7) & ~7); }
 int bis_spmv_grid(int nb) { return grid_for_map(nb, remap_arg_for((nb + 7) & ~7)); }
 

@@ -1,4 +1,4 @@
-"""GPU: single-precision preconditioner storage -- bis_mat_round_f32 and the SpMV form "win4" (bis_spmv_sell.hip, public
+"""GPU: single-precision preconditioner storage -- bis_mat_round_f32 and the SpMV form "win4" (bis_spmv_win8.hip, public
 form 8): win8's window + sliced-ELL plan with 4-byte values, only for a matrix the call has flagged fp32-exact.
 
 The rounding is held to numpy's float32 conversion bit for bit (ties, subnormals, signed zeros, the largest float, an

@@ -1163,7 +1163,7 @@ def _few_values_matrix(rng, n, n_values, empty_head=0):
 @pytest.fixture
 def no_sellwin(ctx):
     """The gather forms of the dictionary kernel (1-3) on their own: the x-window / sliced-ELL form (4-5,
-    bis_spmv_sell.hip), which takes precedence where a matrix qualifies, is switched off for the test."""
+    bis_spmv_sellwin.hip), which takes precedence where a matrix qualifies, is switched off for the test."""
     ctx.set_option("spmv_sellwin", 0)
     yield
     ctx.set_option("spmv_sellwin", -1)
@@ -1377,7 +1377,7 @@ def _banded_few_values(rng, n, n_values, offsets, max_len, ragged=4, empty_every
 @pytest.mark.parametrize("rp64,rows,joint,pairs,masks", [(0, 1, -1, -1, -1), (1, 2, -1, -1, -1), (0, 4, -1, -1, -1), (1, 4, -1, -1, -1), (0, 2, -1, -1, 0), (1, 1, -1, -1, 0), (0, 2, -1, 0, -1),
                                                          (1, 1, -1, 0, -1), (0, 2, 0, 0, -1), (1, 1, 0, 0, -1)])
 def test_spmv_sellwin_form_is_bit_identical(ctx, oracle, rp64, rows, joint, pairs, masks):
-    """Forms 4 / 5 of the dictionary SpMV (bis_spmv_sell.hip): the block's x entries in an LDS window, the codes per
+    """Forms 4 / 5 of the dictionary SpMV (bis_spmv_sellwin.hip): the block's x entries in an LDS window, the codes per
     64-row slice in lane order with neutral padding.  y is BIT-IDENTICAL to the kernel that streams the CRS values and
     within the kernel tolerance of the oracle (kernels.hpp:22-42): stencils, banded matrices with several column runs,
     ragged and empty rows, -0.0 / denormal / huge values and -0.0 row sums (the padding must not turn them into +0.0),
@@ -1500,7 +1500,7 @@ def _pair_matrix(rng, n, offsets, values, p_keep, sort=True, dup=False, empty_ev
 
 @pytest.mark.parametrize("rp64,rows", [(0, 1), (1, 2), (0, 4)])
 def test_spmv_row_mask_form_randomised(ctx, oracle, rp64, rows):
-    """The row-mask form (bis_spmv_sell.hip, spmv_sellmask_kernel: 32 bits per row over the matrix' <= 32 (column - row, value)
+    """The row-mask form (bis_spmv_sellwin.hip, spmv_sellmask_kernel: 32 bits per row over the matrix' <= 32 (column - row, value)
     pairs) on matrices that are NOT stencils of a grid: rows with random subsets of the pairs, empty rows, 1 .. 32 pairs (pair
     counts that are no multiple of the four pairs a step takes), two pairs with the same offset and different values, values
     -0.0 / denormal / huge / infinite; x with infinities and NaNs -- an entry a row does not have must not touch its sum

@@ -1,4 +1,4 @@
-"""GPU: the window + sliced-ELL SpMV with the 8-byte values streamed ("win8", bis_spmv_sell.hip; round 5): the kernel that
+"""GPU: the window + sliced-ELL SpMV with the 8-byte values streamed ("win8", bis_spmv_win8.hip; round 5): the kernel that
 serves matrices with ARBITRARY values (no dictionary) whose blocks read a few contiguous runs of x.  y is BIT-IDENTICAL to
 the row-block kernel on the CRS arrays (spmv_win8 = 0) and within 1e-13 of the oracle (kernels.hpp:22-42): stencils with
 random values, banded matrices with several column runs, ragged / empty rows, unsorted columns and duplicates, -0.0 row
@@ -169,7 +169,7 @@ def test_win8_in_fused_cg(ctx, oracle, rows):
 
 
 def test_win8_placement_search_and_its_record(ctx, oracle):
-    """A stream of >= 1 GiB is placement-searched when it is built (bis_spmv_sell.hip w8_tune_placement): the search keeps an
+    """A stream of >= 1 GiB is placement-searched when it is built (bis_spmv_win8.hip w8_tune_placement): the search keeps an
     allocation at least as fast as the first one, reports what it did (bis_mat_win8_tuning), can be switched off, and whichever
     allocation it keeps holds the same stream: y is bit-identical.  (HPCG-160: 4.1 M rows, 1.14 GiB of stream.)"""
     n1 = 160

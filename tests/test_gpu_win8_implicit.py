@@ -1,4 +1,4 @@
-"""GPU: win8 with implied window slots (option spmv_win8_implicit, bis_spmv_sell.hip).  Where all 64 rows of a slice have one
+"""GPU: win8 with implied window slots (option spmv_win8_implicit, bis_spmv_win8.hip).  Where all 64 rows of a slice have one
 length and their window slots differ only by 8 (row - block_row0) bytes, the stream holds only the chunk's values (2048 bytes)
 and a per-chunk descriptor of 4 slot bases; the other slices keep their 512 bytes of slots per chunk in a side array.  y must
 be BIT-IDENTICAL to the row-block kernel on the CRS arrays (spmv_win8 = 0) and to today's layout (spmv_win8_implicit = 0):
@@ -6,7 +6,8 @@ HPCG sizes whose blocks end mid-slice and whose last block is partial, 1 / 2 / 4
 that is only 8-byte aligned, an x holding -0.0 / inf / NaN (the padding entries must still read the -0.0 slot), stencils with
 a few perturbed rows (implicit and explicit slices in one block), and a matrix where nothing qualifies (today's layout and
 bytes).  bis_mat_spmv_stream_info keeps col_bytes 2 for both layouts (0 names the row-mask form); bis_mat_win8_layout tells
-them apart.  Also: the fused CG history, the placement search, the streamed-byte formula and the partitioned bench path."""
+them apart.  Also: the fused CG history, the placement search, the streamed-byte formula, the partitioned bench path and who
+owns a stream that bis_mat_win8_debug_stream redirected."""
 import json
 import os
 import subprocess
@@ -200,6 +201,72 @@ def test_implied_slots_placement_search_keeps_y(ctx, oracle):
     finally:
         _reset(ctx)
         x.free()
+
+
+def _row_block_product(ctx, dA, x):
+    """y = A x of dA's CRS arrays as they are now, by the row-block kernel (spmv_win8 = 0) on a second matrix"""
+    rp, col, val = dA.download()
+    ctx.set_option("spmv_win8", 0)
+    ref = ctx.matrix(CRS(dA.n_rows, rp, col, val, n_cols=dA.n_cols))
+    y = ctx.alloc(dA.n_rows)
+    ctx.spmv(ref, x, y)
+    assert ref.spmv_stream_info()[3] not in (6, 8)
+    out = y.to_host()
+    ref.free(); y.free()
+    ctx.set_option("spmv_win8", -1)
+    return out
+
+
+@pytest.mark.parametrize("gen,implied,rounded", [("hpcg", True, False), ("hpcg", True, True), ("fem", False, False), ("fem", False, True)])
+def test_redirected_stream_is_the_callers(ctx, gen, implied, rounded):
+    """bis_mat_win8_debug_stream: a stream redirected to the caller's memory is read from there (the same y, bit for bit), the
+    library's own buffer comes back on restore, and a matrix dropped while redirected (scale_sym changes the values) frees its own
+    buffer, never the caller's.  The 8-byte stream and, after round_f32, the 4-byte one; implied slots (hpcg 16: 4096 rows in
+    256-row blocks) and the explicit layout (fem 6)."""
+    import ctypes as C
+    from basic_iterative_solvers_amd import Vec
+
+    def stream(dA, to=None):
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        ctx.check(ctx.lib.bis_mat_win8_debug_stream(dA.h, C.byref(ptr), C.byref(nbytes), C.c_void_p(to) if to else None))
+        return ptr.value, nbytes.value
+
+    ctx.set_option("spmv_valdict", 0)
+    try:
+        dA = ctx.gen_hpcg(16) if gen == "hpcg" else ctx.gen_fem(6)
+        if rounded:
+            dA.round_f32()
+        form = 8 if rounded else 6
+        x = ctx.upload(np.random.default_rng(61).uniform(-1, 1, dA.n_cols))
+        y = ctx.alloc(dA.n_rows)
+        ref = _row_block_product(ctx, dA, x)
+        ctx.spmv(dA, x, y)  # 1: the stream exists
+        assert dA.spmv_stream_info()[3] == form and dA.win8_layout()[4] == implied, (dA.spmv_stream_info(), dA.win8_layout())
+        assert np.array_equal(y.to_host().view(np.uint64), ref.view(np.uint64))
+        own, nbytes = stream(dA)
+        assert own and nbytes > 0 and nbytes % 8 == 0
+        mine = ctx.alloc(nbytes // 8)  # 2: the caller's copy
+        ctx.copy_vector(mine, Vec(ctx, own, nbytes // 8, False))
+        held = mine.to_host()
+        stream(dA, to=mine.ptr)  # 3: read from the copy
+        ctx.init_vector(y, float("nan"))
+        ctx.spmv(dA, x, y)
+        assert np.array_equal(y.to_host().view(np.uint64), ref.view(np.uint64))
+        assert stream(dA) == (own, nbytes)  # 4: set = NULL restores; redirected or not, the report is the library's own buffer
+        assert stream(dA) == (own, nbytes)
+        stream(dA, to=mine.ptr)  # 5: dropped while redirected
+        s = ctx.scale_sym(dA)
+        assert np.array_equal(mine.to_host().view(np.uint64), held.view(np.uint64))  # 6
+        ref2 = _row_block_product(ctx, dA, x)
+        ctx.init_vector(y, float("nan"))
+        ctx.spmv(dA, x, y)  # 7: rebuilt (8-byte values: scale_sym clears the fp32 flag)
+        assert dA.spmv_stream_info()[3] == 6 and stream(dA)[0] != mine.ptr
+        assert np.array_equal(y.to_host().view(np.uint64), ref2.view(np.uint64))
+        assert not np.array_equal(ref, ref2)
+        mine.free()  # 8
+        dA.free(); x.free(); y.free(); s.free()
+    finally:
+        _reset(ctx)
 
 
 def test_implied_slots_partitioned_bench_path():

@@ -1,4 +1,4 @@
-"""GPU: the chunk ring of the window + sliced-ELL SpMV (win8 / win4, bis_spmv_sell.hip) with one and with two register sets.
+"""GPU: the chunk ring of the window + sliced-ELL SpMV (win8 / win4, bis_spmv_win8.hip) with one and with two register sets.
 
 A wave walks its n = C1 - C0 chunks in rounds of D (spmv_win8_depth); with two register sets (spmv_win8_sets = 2, depths 1-4) a
 loop trip is two whole rounds, then at most one whole round, then fewer than D steps that request nothing.  What can go wrong

@@ -2,6 +2,7 @@
 """Compare the device code of two builds of one source file, kernel by kernel.
    hipcc <build.FLAGS> --offload-device-only -S csrc/FILE.hip -o before.s   (at the parent commit; likewise after.s at the head)
    python tools/isa_compare.py before.s after.s
+(a file that was split, as bis_spmv_sell.hip into bis_spmv_sellwin.hip and bis_spmv_win8.hip: after.s = the parts' .s files, concatenated)
 A kernel is the text between its `.type NAME,@function` line and its `.Lfunc_end` label; comments and the numbering of the
 local labels are dropped, the kernel's own name is replaced.  Kernels are matched by mangled name; the value-type argument
 `d` (double) that `spmv_win8_kernel` and `w8_fill_kernel` gained with the 4-byte stream is dropped from the head's names, so the

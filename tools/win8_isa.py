@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What the compiler made of the chunk walk of every spmv_win8_kernel instance: VGPRs, scratch, and inside the walk's loop (the
 backward-branch region of the kernel with the most stream loads) the vmcnt waits, the number of v_mov and the loads.  Reads the gfx950 assembly
-that `hipcc --save-temps -c basic_iterative_solvers_amd/csrc/bis_spmv_sell.hip` leaves (no GPU needed).
-    python tools/win8_isa.py bis_spmv_sell-hip-amdgcn-amd-amdhsa-gfx950.s [filter]"""
+that `hipcc --save-temps -c basic_iterative_solvers_amd/csrc/bis_spmv_win8.hip` leaves (no GPU needed).
+    python tools/win8_isa.py bis_spmv_win8-hip-amdgcn-amd-amdhsa-gfx950.s [filter]"""
 import re
 import subprocess
 import sys
