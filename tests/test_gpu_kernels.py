@@ -8,6 +8,7 @@ import pytest
 from helpers import (GOLDEN, GOLDEN_MATS, check_history, crs_of, load_golden,
                      load_histories, parse_hist_key, random_spmv_case, relerr)
 from oracle.pyoracle import CRS
+from reorder_ref import queue_order as _queue_order
 
 pytestmark = pytest.mark.gpu
 
@@ -989,35 +990,6 @@ def test_tiled_sweep_grid_hint(ctx, oracle, capfd, monkeypatch):
         assert tiled is None or len(lines) == (2 if tiled else 0), (hint, lines)
     with pytest.raises(Exception):
         ctx.matrix(A).set_grid_hint(24, 24, 23, 1)  # extents must multiply to the row count
-
-
-def _queue_order(A, rcm):
-    """The sequential definition of the two orderings (host/utilities/permute.hpp bfs_like_permutation)."""
-    n = A.n_rows
-    adj = [set() for _ in range(n)]
-    for r in range(n):
-        for c in A.col[A.row_ptr[r]:A.row_ptr[r + 1]]:
-            if c != r:
-                adj[r].add(int(c)); adj[int(c)].add(r)
-    adj = [sorted(a) for a in adj]
-    deg = [len(a) for a in adj]
-    starts = sorted(range(n), key=lambda v: deg[v]) if rcm else list(range(n))
-    seen, perm = [False] * n, []
-    for s0 in starts:
-        if seen[s0]:
-            continue
-        seen[s0] = True
-        head = len(perm)
-        perm.append(s0)
-        while head < len(perm):
-            v = perm[head]; head += 1
-            nb = [w for w in adj[v] if not seen[w]]
-            for w in nb:
-                seen[w] = True
-            if rcm:
-                nb.sort(key=lambda w: deg[w])
-            perm += nb
-    return np.array(perm[::-1] if rcm else perm, dtype=np.int32)
 
 
 @pytest.mark.parametrize("rcm", [False, True])
