@@ -120,7 +120,7 @@ def hierarchy(A, grid, prolong_omega=0.0, product=None, **kw):
             agg, cgrid = base.grid_aggregates(n, grid)
             nc = int(np.prod(cgrid))
         else:
-            agg, _ = base.mis_aggregates(A)
+            agg, L["root"] = base.mis_aggregates(A)
             cgrid, nc = None, int(agg.max()) + 1
         if 5 * nc > 4 * n:
             break

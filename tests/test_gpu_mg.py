@@ -173,7 +173,8 @@ def galerkin_reference(A, agg, nc):
 
 
 def hierarchy_reference(A, grid, **kw):
-    """The levels of bis_mg_create: dicts of A, grid, w, agg (None on the coarsest level), kind."""
+    """The levels of bis_mg_create: dicts of A, grid, w, agg (None on the coarsest level), kind; where the MIS ran, root (the
+    flags of its roots) as well."""
     p = dict(DEFAULTS, **kw)
     levels = []
     while True:
@@ -187,7 +188,7 @@ def hierarchy_reference(A, grid, **kw):
             agg, cgrid = grid_aggregates(n, grid)
             nc = int(np.prod(cgrid))
         else:
-            agg, _ = mis_aggregates(A)
+            agg, L["root"] = mis_aggregates(A)
             cgrid, nc = None, int(agg.max()) + 1
         if 5 * nc > 4 * n:
             break
@@ -326,15 +327,16 @@ def test_aggregates_weights_and_galerkin_operators(built, name):
     compare_hierarchies(e["dev"], ref, name)
 
 
-@pytest.mark.parametrize("name", ["unstr666", "band600", "band600_isolated"])
-def test_mis_invariants(built, name):
-    e = built(name)
-    A, agg = e["A"], e["dev"][0]["agg"]
+def check_mis_invariants(A, agg, root_ref=None):
+    """The MIS invariants of the aggregates `agg` of A: the roots (root_ref: those of the restatement, computed here if not
+    given) are numbered by ascending row, independent and maximal, every member is adjacent to the root of its aggregate, and
+    a row without off-diagonal entries is a root.  Returns those rows."""
     n, nc = A.n_rows, int(agg.max()) + 1
     rows = rows_of(A)
     off = A.col != rows
     # the roots: aggregate I's root is the row that the ascending numbering points at
-    _, root_ref = mis_aggregates(A)
+    if root_ref is None:
+        _, root_ref = mis_aggregates(A)
     first = np.full(nc, -1)
     root_rows = np.flatnonzero(root_ref)
     assert len(root_rows) == nc
@@ -351,6 +353,13 @@ def test_mis_invariants(built, name):
     # a row without off-diagonal entries is a root
     lonely = np.flatnonzero(np.bincount(rows[off], minlength=n) == 0)
     assert np.all(is_root[lonely])
+    return lonely
+
+
+@pytest.mark.parametrize("name", ["unstr666", "band600", "band600_isolated"])
+def test_mis_invariants(built, name):
+    e = built(name)
+    lonely = check_mis_invariants(e["A"], e["dev"][0]["agg"])
     if name == "band600_isolated":
         assert len(lonely) == 3
 
