@@ -379,11 +379,9 @@ bis_status ilu0_t(bis_ctx *ctx, const bis_mat *A, double pivot_tol, double pivot
     }
     int has_dups = 0;
     if (n > 0) {
-        int *flag = (int *)ctx->counters + 38;
-        hipMemsetAsync(flag, 0, sizeof(int), ctx->stream);
-        hipLaunchKernelGGL(dup_check_kernel<RP>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rp, W->col, n, flag);
-        e = hipMemcpyAsync(&has_dups, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        bis_slot_io(ctx, kSlotDups, 1);
+        hipLaunchKernelGGL(dup_check_kernel<RP>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, rp, W->col, n, bis_slot_ptr(ctx, kSlotDups));
+        e = bis_slot_io(ctx, kSlotDups, 1, &has_dups);
         if (e != hipSuccess) { ctx->err = std::string("bis_mat_ilu0: ") + hipGetErrorString(e); return cleanup(BIS_ERR_HIP); }
     }
     st = bis_mat_finalize(ctx, W);

@@ -163,54 +163,25 @@ struct bis_mat {
     // SpMV row-block metadata: block k covers rows [blk_row[k], blk_row[k+1])
     int32_t *blk_row = nullptr;
     int64_t *blk_nnz = nullptr; // row_ptr[blk_row[k]] (saves a dependent load)
-    // x-window acceleration structure (bis_spmv.hip): per row block the sorted
-    // list of 16-column tiles of x it touches, and per non-zero a 16-bit offset
-    // into that window (replaces the 32-bit col in the SpMV stream)
-    uint16_t *loc = nullptr;    // [nnz_range + pad], index k - loc_base
-    int32_t *tiles = nullptr;   // [n_blocks * kWinMaxTiles]
-    int32_t *tile_cnt = nullptr; // [n_blocks]
-    int64_t loc_base = 0;
-    int max_tiles = 0;
-    bool win_ok = false;
     int n_blocks = 0;
-    // packed-column streams (bis_spmv.hip), one per row-block table (0 plain, 1
-    // fused): per non-zero a 16-bit code (segment:3 | offset:13) against 8 column
-    // bases per row block -- 10 instead of 12 streamed bytes per non-zero.  Built
-    // lazily at the first SpMV; state 0 = not tried, 1 = usable, -1 = not
-    // representable (some block needs more than 8 windows of 8192 columns).
-    uint16_t *pk[2] = {nullptr, nullptr};
-    int32_t *pk_seg[2] = {nullptr, nullptr}; // [n_blocks * 8]
-    int64_t pk_base[2] = {0, 0};
-    int pk_state[2] = {0, 0};
-    int pk_kind[2] = {0, 0};   // 1: 8 windows x 8192 columns, 3: 32 windows x 2048 columns
-    // value dictionary (bis_spmv.hip): a matrix with at most 256 distinct values (compared bit for bit) keeps them in a
-    // 256-entry table and streams one byte per non-zero instead of the 8-byte value.  Built lazily at the first SpMV;
-    // state 0 = not tried, 1 = usable, -1 = too many distinct values.  The CRS values stay authoritative.
-    uint8_t *vcode = nullptr;  // [nnz_range + pad], index k - vd_base
-    double *vdict = nullptr;   // [256], ascending bit patterns, unused entries 0
-    int64_t vd_base = 0;
-    int vd_state = 0, vd_n = 0;
-    // ... or all values EXCEPT the diagonal entries (col == row + view_row0) are at most 255: code 255 then stands for "this
-    // row's diagonal value", kept in a per-row array (Anderson: random diagonal, constant hopping).  Lane-per-row form only.
-    double *vdiag = nullptr;   // [n_rows] when vd_diag
-    bool vd_diag = false;
-    bool vd_rm_only = false;   // only the lane-per-row kernel can use this dictionary (vd_diag, or the row-block tables have no packed columns)
     int64_t view_row0 = 0;     // row views: first row of the view in the matrix it was cut from
-    // lane-per-row form of the dictionary kernel: blocks of 256 rows with their own packed column stream
-    int64_t *rm_nnz = nullptr;  // [rm_blocks + 1] row_ptr at every 256th row
-    uint16_t *rm_pk = nullptr;  // column codes against rm_seg's windows, index k - rm_base
-    int32_t *rm_seg = nullptr;  // [rm_blocks * 8]
-    int64_t rm_base = 0;
-    int rm_state = 0, rm_blocks = 0, rm_kind = 1; // rm_kind 1: 8 windows x 8192 columns per block, 3: 32 windows x 2048 columns
-    // x-window + sliced-ELL form of the dictionary kernel (bis_spmv_sellwin.hip); state as above
+    // The forms of the SpMV (table in bis_spmv.hip), each built lazily by spmv_resolve and owned by its unit: a pointer to the
+    // unit's struct and a state, 0 = not tried, 1 = usable, -1 = does not apply.  bis_mat_free_meta and bis_mat_values_changed
+    // say which of them a finalize and a value change drop.
+    struct bis_xwin *xw = nullptr; // x window (bis_spmv_xwin.hip), built by bis_mat_finalize where spmv_window asks: null = none
+    // packed-column streams (bis_spmv_colpack.hip), one per row-block table (0 plain, 1 fused): 10 instead of 12 streamed
+    // bytes per non-zero; -1 = some block needs more column windows than the format has
+    struct { struct bis_colpack *p = nullptr; int state = 0; } pk[2];
+    // value dictionary and its lane-per-row blocks (bis_spmv_valdict.hip); -1 = too many distinct values
+    struct { struct bis_valdict *p = nullptr; int state = 0; } vd;
+    // x-window + sliced-ELL form of the dictionary kernel (bis_spmv_sellwin.hip)
     struct bis_sellwin *sw = nullptr;
     int sw_state = 0;
-    // the same plan with the values streamed (no dictionary needed), bis_spmv_win8.hip; state as above.  [0]: 8-byte values, "win8";
+    // the same plan with the values streamed (no dictionary needed), bis_spmv_win8.hip.  [0]: 8-byte values, "win8";
     // [1]: 4-byte values, "win4", built only while f32_exact holds
     struct { struct bis_win8 *p = nullptr; int state = 0; } w8[2];
-    std::vector<bis_mat *> *colslabs = nullptr; // column slabs of a matrix without locality (bis_spmv_slab.hip); cs_state: 0 untried, 1 in use, -1 refused
-    int cs_state = 0;
-    double cs_trial_ms[2] = {0.0, 0.0};        // the build-time trial: one pass / the K passes
+    // column slabs of a matrix without locality (bis_spmv_slab.hip, colslab_try in bis_spmv.hip); -1 = refused
+    struct { std::vector<bis_mat *> *slabs = nullptr; int state = 0; double trial_ms[2] = {0.0, 0.0}; } cs; // trial_ms: the build-time trial, one pass / the K passes
     // every value of val is exactly representable in binary32: set by bis_mat_round_f32, cleared by bis_mat_scale_sym and
     // bis_mat_retune, inherited by row views (bis_mat_row_view) and by nothing else
     bool f32_exact = false;
@@ -267,6 +238,26 @@ bis_status bis_fault_check(bis_ctx *ctx);
     do {                                                                       \
         if (!(ctx)) return BIS_ERR_NO_DEVICE;                                  \
     } while (0)
+
+// Status words of the build and check kernels: the words of ctx->counters in use, each with the number of words from its index.
+// A site zeroes its words on the stream, launches, reads them back.  Words 0-31 are free, and every later word that no entry covers.
+enum bis_slot {
+    kSlotMaxRow = 32,   // 1: the longest row (bis_mat_finalize)
+    kSlotValidate = 36, // 1: bis_mat_create's check of row_ptr and col
+    kSlotDups = 38,     // 1: a row holds a column twice (bis_mat_sorted_copy)
+    kSlotXwin = 40,     // 2: some block touches too many tiles, most tiles of a block (bis_spmv_xwin.hip)
+    kSlotColpack = 44,  // 1: some block needs a window too many (bis_spmv_colpack.hip)
+    kSlotValdict = 46,  // 1: too many distinct values (bis_spmv_valdict.hip)
+    kSlotWinplan = 52,  // 6: the plans of bis_spmv_sellwin.hip and bis_spmv_win8.hip ([0] not representable, [1] largest window,
+                        //    [2] win8: the windows' sum, sellwin: a fill gave up, [3] sellwin: too many pairs, [5] most chunks of a slice)
+};
+inline int *bis_slot_ptr(bis_ctx *ctx, int slot) { return (int *)ctx->counters + slot; }
+// host == nullptr: zeroes n words from `slot` on the stream; otherwise copies them to host and synchronises the stream
+inline hipError_t bis_slot_io(bis_ctx *ctx, int slot, int n, int *host = nullptr) {
+    if (!host) return hipMemsetAsync(bis_slot_ptr(ctx, slot), 0, sizeof(int) * (size_t)n, ctx->stream);
+    const hipError_t e = hipMemcpyAsync(host, bis_slot_ptr(ctx, slot), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+    return e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
+}
 
 // operands that a kernel loads 16 bytes per lane
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -415,10 +406,7 @@ bis_status bis_mat_row_view(bis_ctx *ctx, const bis_mat *A, int64_t ra,
 bis_status bis_mat_alloc(bis_ctx *ctx, int64_t n_rows, int64_t n_cols,
                          int64_t nnz, bool rp64, bis_mat **out);
 bis_status bis_mat_finalize(bis_ctx *ctx, bis_mat *A);
-bis_status bis_spmv_build_window(bis_ctx *ctx, bis_mat *A);
-void bis_spmv_drop_packed(bis_mat *A);
-void bis_spmv_drop_valdict(bis_mat *A); // after the values of A changed in place
-bis_status bis_spmv_try_valdict(bis_ctx *ctx, bis_mat *A, bool consecutive_ok);
+// (the row-block, packed-column, dictionary and x-window forms: bis_spmv_forms.hpp)
 // x-window + sliced-ELL dictionary form (bis_spmv_sellwin.hip)
 bis_status bis_spmv_sellwin_try(bis_ctx *ctx, bis_mat *A);
 int bis_spmv_sellwin_blocks(const bis_mat *A);
@@ -448,11 +436,10 @@ bool bis_spmv_win8_implied(const bis_mat *A, int vb = 8);         // the implied
 double bis_spmv_win8_moved_bytes(const bis_mat *A, int vb = 8);  // bytes a launch moves: the form's arrays, the windows' x granules, y
 bool bis_spmv_win8_fast(const bis_mat *A, double ms, int vb = 8); // a launch of ms runs at the stream placement's fast level
 void *bis_spmv_win8_swap_stream(bis_mat *A, void *stream, int vb = 8); // returns the buffer that was in use
-// try to build the packed-column stream of table t (0 plain, 1 fused); A->pk_state[t] tells the outcome
-bis_status bis_spmv_try_pack(bis_ctx *ctx, bis_mat *A, int t);
-// free row-block tables, packed streams and window structures (not the CRS arrays)
+// free the row-block tables and every SpMV form (not the CRS arrays)
 void bis_mat_free_meta(bis_mat *A);
-// after the values of A changed in place: drops every structure derived from them (dictionaries, code streams, sweep plans)
+// after the values of A changed in place: drops every structure derived from them (dictionary, code streams, slabs, sweep
+// plans); the packed column streams and the x window depend on the pattern only and stay
 void bis_mat_values_changed(bis_mat *A);
 void bis_trsv_plan_destroy(bis_trsv_plan *p);
 void bis_trsm_plan_destroy(bis_trsm_plan *p); // bis_sptrsm.hip

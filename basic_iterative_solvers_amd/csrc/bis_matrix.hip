@@ -9,7 +9,7 @@
 // exactly as given.  col/val carry 8 elements of zero padding so that the
 // SpMV kernel's 16-byte vector loads may start 4-aligned before a block's
 // first non-zero and run past its last one.
-#include "bis_internal.hpp"
+#include "bis_spmv_forms.hpp"
 
 #include <algorithm>
 #include <utility>
@@ -376,16 +376,14 @@ __global__ __launch_bounds__(kSplitT) void split_fill_kernel(
 template <typename RP>
 bis_status finalize_t(bis_ctx *ctx, bis_mat *A) {
     const RP *rp = (const RP *)A->row_ptr;
-    int *d_max = (int *)ctx->counters + 32;
-    BIS_HIP_CHECK(ctx, hipMemsetAsync(d_max, 0, sizeof(int), ctx->stream));
+    BIS_HIP_CHECK(ctx, bis_slot_io(ctx, kSlotMaxRow, 1));
     if (A->n_rows > 0) {
         int grid = (int)std::min<int64_t>((A->n_rows + 255) / 256, 4096);
         hipLaunchKernelGGL(max_row_kernel<RP>, dim3(grid), dim3(256), 0, ctx->stream, rp,
-                           A->n_rows, d_max);
+                           A->n_rows, bis_slot_ptr(ctx, kSlotMaxRow));
     }
     int h_max = 0;
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(&h_max, d_max, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    BIS_HIP_CHECK(ctx, bis_slot_io(ctx, kSlotMaxRow, 1, &h_max));
     A->max_row_nnz = h_max;
     // Row-block tables (0: plain SpMV / triangular sweeps, 1: SpMV with the fused
     // dot epilogue of CG).  With the packed column stream both use one pass of the
@@ -420,7 +418,7 @@ bis_status finalize_t(bis_ctx *ctx, bis_mat *A) {
         BIS_HIP_CHECK(ctx, hipGetLastError());
         if (!try_single) break;
         if (bis_status st = bis_spmv_try_pack(ctx, A, 1)) return st;
-        if (A->pk_state[1] == 1) break; // packed: keep the single-pass tables
+        if (A->pk[1].state == 1) break; // packed: keep the single-pass tables
     }
     return bis_spmv_build_window(ctx, A);
 }
@@ -431,7 +429,10 @@ bis_status finalize_t(bis_ctx *ctx, bis_mat *A) {
 // bis_mat_retune): everything derived from them goes -- value dictionary and code streams, the tiled sweeps' plans (they
 // hold a copy of the values in their entry stream), the level plans (their row views carry dictionaries of their own).
 void bis_mat_values_changed(bis_mat *A) {
-    bis_spmv_drop_valdict(A);
+    bis_spmv_valdict_drop(A);
+    bis_spmv_sellwin_drop(A);
+    bis_spmv_win8_drop(A);
+    bis_spmv_colslab_drop(A);
     bis_trsv_drop(A, /*chains=*/false);
 }
 
@@ -439,11 +440,12 @@ void bis_mat_free_meta(bis_mat *A) {
     hipFree(A->blk_row); hipFree(A->blk_nnz); hipFree(A->blkf_row); hipFree(A->blkf_nnz);
     A->blk_row = A->blkf_row = nullptr;
     A->blk_nnz = A->blkf_nnz = nullptr;
-    bis_spmv_drop_packed(A);
-    bis_spmv_drop_valdict(A);
-    hipFree(A->loc); hipFree(A->tiles); hipFree(A->tile_cnt);
-    A->loc = nullptr; A->tiles = nullptr; A->tile_cnt = nullptr;
-    A->win_ok = false;
+    bis_spmv_colpack_drop(A);
+    bis_spmv_valdict_drop(A);
+    bis_spmv_sellwin_drop(A);
+    bis_spmv_win8_drop(A);
+    bis_spmv_colslab_drop(A);
+    bis_spmv_xwin_drop(A);
 }
 
 bis_status bis_mat_alloc(bis_ctx *ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, bool rp64,
@@ -598,14 +600,13 @@ static bis_status mat_create_common(bis_ctx *ctx, int64_t n_rows, int64_t n_cols
     }
     // a malformed input must be an error here, not an out-of-bounds gather in a kernel later
     if (n_rows > 0) {
-        int *status = (int *)ctx->counters + 36;
-        hipMemsetAsync(status, 0, sizeof(int), ctx->stream);
+        int *status = bis_slot_ptr(ctx, kSlotValidate);
+        bis_slot_io(ctx, kSlotValidate, 1);
         const unsigned grid = (unsigned)((n_rows + 255) / 256);
         if (rp64) hipLaunchKernelGGL(validate_kernel<int64_t>, dim3(grid), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, n_rows, n_cols, nnz, status);
         else hipLaunchKernelGGL(validate_kernel<int32_t>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, n_rows, n_cols, nnz, status);
         int h = 0;
-        e = hipMemcpyAsync(&h, status, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        e = bis_slot_io(ctx, kSlotValidate, 1, &h);
         if (e != hipSuccess) { ctx->err = std::string("bis_mat_create: ") + hipGetErrorString(e); bis_mat_destroy(ctx, A); return BIS_ERR_HIP; }
         if (h) {
             ctx->err = (h & 1) ? "bis_mat_create: row_ptr is not a monotone sequence from 0 to nnz"
@@ -698,8 +699,8 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
     };
     // the streamed arrays: values, and the packed column stream (or the 32-bit columns)
     struct Set { double *val; int32_t *col; uint16_t *pk; };
-    const int t = 1; // identical tables share stream 1 (bis_spmv.hip ensure_packed)
-    const bool packed = A->pk_state[t] == 1 && A->chunk_nnz == A->chunk_f;
+    bis_colpack *pk1 = A->pk[1].state == 1 ? A->pk[1].p : nullptr; // identical tables share stream 1 (bis_spmv.hip ensure_packed)
+    const bool packed = pk1 && A->chunk_nnz == A->chunk_f;
     const size_t n_val = (size_t)A->nnz + 8; // kPad
     size_t n_pk = 0;
     if (packed) {
@@ -707,7 +708,7 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
         hipMemcpyAsync(&ends[0], A->blkf_nnz, 8, hipMemcpyDeviceToHost, ctx->stream);
         hipMemcpyAsync(&ends[1], A->blkf_nnz + A->n_blocks_f, 8, hipMemcpyDeviceToHost, ctx->stream);
         hipStreamSynchronize(ctx->stream);
-        n_pk = (size_t)(ends[1] - A->pk_base[t]) + 16;
+        n_pk = (size_t)(ends[1] - pk1->base) + 16;
     }
     std::vector<Set> rejected;
     double best = 0.0;
@@ -752,7 +753,7 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
     }
     // the value-dictionary kernels stream a quarter of the bytes and are not HBM-bound: where their arrays lie matters
     // little, and the arrays re-allocated below (values, packed columns of the row-block tables) are not the ones they read
-    if (A->vd_state == 1) max_trials = 0;
+    if (A->vd.state == 1) max_trials = 0;
     for (int trial = 0; st == BIS_OK && trial < max_trials; ++trial) {
         Set cand{nullptr, nullptr, nullptr};
         hipError_t e = hipMalloc(&cand.val, sizeof(double) * n_val);
@@ -764,11 +765,11 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
             break;
         }
         hipMemcpyAsync(cand.val, A->val, sizeof(double) * n_val, hipMemcpyDeviceToDevice, ctx->stream);
-        if (packed) hipMemcpyAsync(cand.pk, A->pk[t], sizeof(uint16_t) * n_pk, hipMemcpyDeviceToDevice, ctx->stream);
+        if (packed) hipMemcpyAsync(cand.pk, pk1->codes, sizeof(uint16_t) * n_pk, hipMemcpyDeviceToDevice, ctx->stream);
         else hipMemcpyAsync(cand.col, A->col, sizeof(int32_t) * n_val, hipMemcpyDeviceToDevice, ctx->stream);
-        Set cur{A->val, packed ? nullptr : A->col, packed ? A->pk[t] : nullptr};
+        Set cur{A->val, packed ? nullptr : A->col, packed ? pk1->codes : nullptr};
         A->val = cand.val;
-        if (packed) A->pk[t] = cand.pk; else A->col = cand.col;
+        if (packed) pk1->codes = cand.pk; else A->col = cand.col;
         double ms = 0.0;
         st = measure(ms);
         if (st == BIS_OK && ms < best) {
@@ -776,7 +777,7 @@ BIS_API bis_status bis_mat_tune_placement(bis_ctx *ctx, bis_mat *A, int max_tria
             rejected.push_back(cur);
         } else {
             A->val = cur.val;
-            if (packed) A->pk[t] = cur.pk; else A->col = cur.col;
+            if (packed) pk1->codes = cur.pk; else A->col = cur.col;
             rejected.push_back(cand);
         }
     }

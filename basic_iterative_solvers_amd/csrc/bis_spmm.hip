@@ -5,7 +5,7 @@
 //
 // Arithmetic (the contract of include/bis_hip.h): for every row r and column j, acc = 0.0, then for the row's entries in
 // CRS storage order acc += val[e] * X[col[e]*k + j], product and addition rounded separately -- phase 2 of
-// spmv_rowblock_kernel (bis_spmv.hip), so column j of the result is bis_spmv on column j bit for bit wherever bis_spmv
+// spmv_rowblock_kernel (bis_spmv_rowblock.hip), so column j of the result is bis_spmv on column j bit for bit wherever bis_spmv
 // does not run its wave-per-row kernel.
 //
 //   spmm_rowblock_kernel<RP, K, V>   a workgroup per block of the PLAIN row-block table (blk_row / blk_nnz, nothing new is

@@ -1,7 +1,7 @@
 // bis_spmv_sellwin.hip -- CRS SpMV (kernels.hpp:22-42 of the reference), dictionary form with the block's x window in
 // LDS and the codes in a sliced-ELL stream.  gfx950 only.
 //
-// The lane-per-row dictionary kernel (bis_spmv.hip, spmv_rowmajor_vd_kernel) is bound by the texture addresser: one
+// The lane-per-row dictionary kernel (bis_spmv_valdict.hip, spmv_rowmajor_vd_kernel) is bound by the texture addresser: one
 // 8-byte gather per non-zero, plus the LDS round trip that turns the CRS-ordered code stream into per-lane order.
 // This form removes both:
 //   * window: the x entries a block of 256 consecutive rows reads are, for a banded / stencil matrix, a few
@@ -39,6 +39,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bis_winplan.hpp"
+#include "bis_spmv_forms.hpp" // bis_valdict
 
 struct bis_sellwin : bis_winplan {
     uint32_t *codes = nullptr;       // [(total_chunks + 1) * 64 * words], words = 3, 3, 2, 1 for fmt 0..3
@@ -838,18 +839,17 @@ static bis_status sw_collect_pairs(bis_ctx *ctx, bis_mat *A, SwPairs &P) {
     void *tmp = nullptr;
     const int n_waves = (int)std::min<int64_t>((A->n_rows + 63) / 64, (int64_t)ctx->n_cus * 8);
     unsigned long long *lists = nullptr;
-    int *status = (int *)ctx->counters + 52;
+    int *status = bis_slot_ptr(ctx, kSlotWinplan);
     SW_CHECK(hipMalloc(&lists, sizeof(unsigned long long) * 257 * (size_t)n_waves));
     tmp = lists;
-    SW_CHECK(hipMemsetAsync(status + 2, 0, 2 * sizeof(int), ctx->stream));
-    if (A->rp64) hipLaunchKernelGGL(sw_pairs_kernel<int64_t>, dim3(n_waves), dim3(64), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->vcode, A->vd_base, A->n_rows, A->view_row0, lists, status + 3);
-    else hipLaunchKernelGGL(sw_pairs_kernel<int32_t>, dim3(n_waves), dim3(64), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, A->vcode, A->vd_base, A->n_rows, A->view_row0, lists, status + 3);
+    SW_CHECK(bis_slot_io(ctx, kSlotWinplan + 2, 2));
+    if (A->rp64) hipLaunchKernelGGL(sw_pairs_kernel<int64_t>, dim3(n_waves), dim3(64), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->vd.p->codes, A->vd.p->base, A->n_rows, A->view_row0, lists, status + 3);
+    else hipLaunchKernelGGL(sw_pairs_kernel<int32_t>, dim3(n_waves), dim3(64), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, A->vd.p->codes, A->vd.p->base, A->n_rows, A->view_row0, lists, status + 3);
     SW_CHECK(hipGetLastError());
     std::vector<unsigned long long> h((size_t)257 * n_waves);
     int over = 0;
-    SW_CHECK(hipMemcpyAsync(&over, status + 3, sizeof over, hipMemcpyDeviceToHost, ctx->stream));
     SW_CHECK(hipMemcpyAsync(h.data(), lists, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    SW_CHECK(hipStreamSynchronize(ctx->stream));
+    SW_CHECK(bis_slot_io(ctx, kSlotWinplan + 3, 1, &over)); // (synchronises: the lists have arrived too)
     hipFree(lists); tmp = nullptr;
     if (over) return BIS_OK;
     std::vector<unsigned long long> &all = P.all;
@@ -868,7 +868,7 @@ static bis_status sw_collect_pairs(bis_ctx *ctx, bis_mat *A, SwPairs &P) {
 // apply" everything it allocated is freed and the caller goes on with another format; an out-of-memory drops the form.
 static bis_status sw_try_pairs(bis_ctx *ctx, bis_mat *A, const double *table, int pad_idx, SwPairs &P) {
     bis_sellwin *sw = A->sw;
-    int *status = (int *)ctx->counters + 52;
+    int *status = bis_slot_ptr(ctx, kSlotWinplan);
     if (!P.known) {
         if (bis_status st = sw_collect_pairs(ctx, A, P)) return st;
         if (!A->sw) return BIS_OK; // (dropped on an allocation failure)
@@ -883,7 +883,7 @@ static bis_status sw_try_pairs(bis_ctx *ctx, bis_mat *A, const double *table, in
     for (int e = 0; e < n_pairs; ++e) {
         keys[e] = all[e];
         const unsigned vc = (unsigned)(all[e] & 0xffu);
-        if (A->vd_diag && vc == 255u) {
+        if (A->vd.p->diag && vc == 255u) {
             if (diag_pair >= 0) return BIS_OK; // diagonal entries at several offsets (a row view's numbering): another format
             diag_pair = e;
         } else vals[e] = table[vc];
@@ -907,11 +907,11 @@ static bis_status sw_try_pairs(bis_ctx *ctx, bis_mat *A, const double *table, in
         if (e == hipSuccess) e = hipMalloc(&dict3, sizeof vals);
         if (e == hipSuccess) e = hipMemcpyAsync(pair_key, keys, sizeof keys, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dict3, vals, sizeof vals, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(status + 2, 0, sizeof(int), ctx->stream);
+        if (e == hipSuccess) e = bis_slot_io(ctx, kSlotWinplan + 2, 1);
         if (e == hipSuccess && !masks) e = hipMemsetAsync(codes + (size_t)total * 64, 0, sizeof(uint32_t) * 64, ctx->stream);
         if (e == hipSuccess) {
-#define SW_FILLP(RP) hipLaunchKernelGGL((sw_fill_pairs_kernel<RP>), dim3(nb), dim3(256), 0, ctx->stream, (const RP *)A->row_ptr, A->col, A->vcode, A->vd_base, A->n_rows, A->view_row0, sw->R, sw->hdr, sw->slice_chunk0, codes, pair_key, n_pairs, stride, blk_base, status)
-#define SW_FILLM(RP) hipLaunchKernelGGL((sw_fill_masks_kernel<RP>), dim3(nb), dim3(256), 0, ctx->stream, (const RP *)A->row_ptr, A->col, A->vcode, A->vd_base, A->n_rows, A->view_row0, sw->R, sw->hdr, codes, pair_key, n_pairs, stride, blk_base, status)
+#define SW_FILLP(RP) hipLaunchKernelGGL((sw_fill_pairs_kernel<RP>), dim3(nb), dim3(256), 0, ctx->stream, (const RP *)A->row_ptr, A->col, A->vd.p->codes, A->vd.p->base, A->n_rows, A->view_row0, sw->R, sw->hdr, sw->slice_chunk0, codes, pair_key, n_pairs, stride, blk_base, status)
+#define SW_FILLM(RP) hipLaunchKernelGGL((sw_fill_masks_kernel<RP>), dim3(nb), dim3(256), 0, ctx->stream, (const RP *)A->row_ptr, A->col, A->vd.p->codes, A->vd.p->base, A->n_rows, A->view_row0, sw->R, sw->hdr, codes, pair_key, n_pairs, stride, blk_base, status)
             if (masks) { if (A->rp64) SW_FILLM(int64_t); else SW_FILLM(int32_t); }
             else { if (A->rp64) SW_FILLP(int64_t); else SW_FILLP(int32_t); }
 #undef SW_FILLP
@@ -919,8 +919,7 @@ static bis_status sw_try_pairs(bis_ctx *ctx, bis_mat *A, const double *table, in
             e = hipGetLastError();
         }
         int bad = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, status + 2, sizeof bad, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream); // keys[], vals[], bad
+        if (e == hipSuccess) e = bis_slot_io(ctx, kSlotWinplan + 2, 1, &bad); // (synchronises: keys[], vals[] are read)
         if (e != hipSuccess || bad) {
             hipFree(blk_base); hipFree(pair_key); hipFree(codes); hipFree(dict3);
             if (e == hipSuccess && masks) continue; // the byte codes then
@@ -945,13 +944,13 @@ static bis_status sw_try_pairs(bis_ctx *ctx, bis_mat *A, const double *table, in
     return BIS_OK;
 }
 
-// Build the form for a matrix that has a value dictionary (A->vd_state == 1); A->sw_state tells the outcome.
+// Build the form for a matrix that has a value dictionary (A->vd.state == 1); A->sw_state tells the outcome.
 static bis_status sw_try_rows(bis_ctx *ctx, bis_mat *A, int R, SwPairs &P);
 
 bis_status bis_spmv_sellwin_try(bis_ctx *ctx, bis_mat *A) {
     if (A->sw_state != 0) return BIS_OK;
     A->sw_state = -1;
-    if (!sw_enabled() || A->vd_state != 1 || A->n_rows == 0 || A->nnz == 0 || A->n_cols >= ((int64_t)1 << 31) - 16) return BIS_OK;
+    if (!sw_enabled() || A->vd.state != 1 || A->n_rows == 0 || A->nnz == 0 || A->n_cols >= ((int64_t)1 << 31) - 16) return BIS_OK;
     int R = kSwDefaultR;
     while (R > 1 && A->n_rows < (int64_t)kSwRows * R * 1024) R >>= 1; // small matrices: more, smaller blocks
     bool big = R == 2 && A->n_rows >= (int64_t)kSwRows * 4 * 1024;
@@ -964,7 +963,7 @@ bis_status bis_spmv_sellwin_try(bis_ctx *ctx, bis_mat *A) {
     // The pairs are counted BEFORE that plan is made (one light pass over the matrix): a matrix with more than 32 of them goes to
     // the 512-row plan directly instead of building the 1024-row plan and its tables only to drop them.
     SwPairs P;
-    if (big && !A->vd_diag && bis_opts().spmv_sellwin_masks != 0 && bis_opts().spmv_sellwin_pairs != 0) {
+    if (big && !A->vd.p->diag && bis_opts().spmv_sellwin_masks != 0 && bis_opts().spmv_sellwin_pairs != 0) {
         if (bis_status st = sw_collect_pairs(ctx, A, P)) return st;
         if (P.fits && P.all.size() <= 32) {
             if (bis_status st = sw_try_rows(ctx, A, 4, P)) return st;
@@ -981,13 +980,13 @@ static bis_status sw_try_rows(bis_ctx *ctx, bis_mat *A, int R, SwPairs &P) {
     const int nb = (int)nb64;
     // the table: the matrix' dictionary and the padding value 1.0
     double table[256];
-    BIS_HIP_CHECK(ctx, hipMemcpyAsync(table, A->vdict, sizeof table, hipMemcpyDeviceToHost, ctx->stream));
+    BIS_HIP_CHECK(ctx, hipMemcpyAsync(table, A->vd.p->table, sizeof table, hipMemcpyDeviceToHost, ctx->stream));
     BIS_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    const int cap_small = A->vd_diag ? 31 : 32, cap_gen = A->vd_diag ? 255 : 256;
+    const int cap_small = A->vd.p->diag ? 31 : 32, cap_gen = A->vd.p->diag ? 255 : 256;
     int pad_idx = -1;
-    for (int i = 0; i < A->vd_n; ++i)
+    for (int i = 0; i < A->vd.p->n; ++i)
         if (table[i] == 1.0 && !std::signbit(table[i])) pad_idx = i;
-    int n_tab = A->vd_n;
+    int n_tab = A->vd.p->n;
     if (pad_idx < 0) {
         if (n_tab >= cap_gen) return BIS_OK; // no free code for the padding
         pad_idx = n_tab++;
@@ -998,15 +997,15 @@ static bis_status sw_try_rows(bis_ctx *ctx, bis_mat *A, int R, SwPairs &P) {
     sw->n_blocks = nb;
     sw->R = R;
     sw->n_slices = (int64_t)nb * 4 * R;
-    sw->diag = A->vd_diag;
+    sw->diag = A->vd.p->diag;
     // 16-bit joint codes where the table (+ the diagonal marker 7) fits 3 bits; else value bytes
-    const bool joint = n_tab <= (A->vd_diag ? 7 : 8) && bis_opts().spmv_sellwin_joint != 0;
+    const bool joint = n_tab <= (A->vd.p->diag ? 7 : 8) && bis_opts().spmv_sellwin_joint != 0;
     sw->fmt = joint ? 2 : (n_tab <= cap_small ? 1 : 0);
     sw->pad_idx = pad_idx;
-    sw->diag_idx = !A->vd_diag ? -1 : (sw->fmt == 2 ? 7 : (sw->fmt == 1 ? 31 : 255));
+    sw->diag_idx = !A->vd.p->diag ? -1 : (sw->fmt == 2 ? 7 : (sw->fmt == 1 ? 31 : 255));
     int32_t *slice_chunks = nullptr;
     void *tmp = nullptr;
-    int *status = (int *)ctx->counters + 52;
+    int *status = bis_slot_ptr(ctx, kSlotWinplan);
     SW_CHECK(hipMalloc(&sw->hdr, sizeof(int32_t) * 64 * (size_t)nb));
     SW_CHECK(hipMalloc(&sw->own_rank, sizeof(int32_t) * (size_t)nb));
     SW_CHECK(hipMemsetAsync(sw->own_rank, 0xFF, sizeof(int32_t) * (size_t)nb, ctx->stream)); // (blocks the plan leaves early: -1)
@@ -1014,8 +1013,8 @@ static bis_status sw_try_rows(bis_ctx *ctx, bis_mat *A, int R, SwPairs &P) {
     SW_CHECK(hipMalloc(&sw->slice_chunk0, sizeof(int64_t) * (size_t)(sw->n_slices + 1)));
     SW_CHECK(hipMalloc(&sw->dict, sizeof table));
     SW_CHECK(hipMemcpyAsync(sw->dict, table, sizeof table, hipMemcpyHostToDevice, ctx->stream));
-    SW_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int), ctx->stream));
-    SW_CHECK(hipMemsetAsync(status + 5, 0, sizeof(int), ctx->stream)); // most chunks of a slice
+    SW_CHECK(bis_slot_io(ctx, kSlotWinplan, 2));
+    SW_CHECK(bis_slot_io(ctx, kSlotWinplan + 5, 1)); // most chunks of a slice
     SW_CHECK(hipMemsetAsync(slice_chunks + sw->n_slices, 0, sizeof(int32_t), ctx->stream));
     if (A->rp64) hipLaunchKernelGGL(sw_plan_kernel<int64_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->n_rows, R, sw_gran_cap(R), A->view_row0, sw->hdr, slice_chunks, sw->own_rank, status);
     else hipLaunchKernelGGL(sw_plan_kernel<int32_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int32_t *)A->row_ptr, A->col, A->n_rows, R, sw_gran_cap(R), A->view_row0, sw->hdr, slice_chunks, sw->own_rank, status);
@@ -1059,7 +1058,7 @@ static bis_status sw_try_rows(bis_ctx *ctx, bis_mat *A, int R, SwPairs &P) {
     const size_t cw = sw->fmt == 2 ? 128 : 192; // 32-bit words per chunk of 64 lanes
     SW_CHECK(hipMalloc(&sw->codes, sizeof(uint32_t) * cw * (size_t)(total + 1)));
     SW_CHECK(hipMemsetAsync(sw->codes + (size_t)total * cw, 0, sizeof(uint32_t) * cw, ctx->stream));
-#define SW_FILL(RP) hipLaunchKernelGGL((sw_fill_kernel<RP>), dim3(nb), dim3(256), 0, ctx->stream, (const RP *)A->row_ptr, A->col, A->vcode, A->vd_base, A->n_rows, R, sw->fmt, sw->hdr, sw->slice_chunk0, sw->codes, sw->pad_idx, sw->diag_idx)
+#define SW_FILL(RP) hipLaunchKernelGGL((sw_fill_kernel<RP>), dim3(nb), dim3(256), 0, ctx->stream, (const RP *)A->row_ptr, A->col, A->vd.p->codes, A->vd.p->base, A->n_rows, R, sw->fmt, sw->hdr, sw->slice_chunk0, sw->codes, sw->pad_idx, sw->diag_idx)
     if (A->rp64) SW_FILL(int64_t); else SW_FILL(int32_t);
 #undef SW_FILL
     SW_CHECK(hipGetLastError());
@@ -1114,11 +1113,11 @@ bis_status bis_spmv_sellwin_launch(bis_ctx *ctx, const bis_mat *A, const double 
 #define SW_L4(MODE, DIAG, FMT, RR)                                                                                     \
     hipLaunchKernelGGL((spmv_sellwin_kernel<MODE, DIAG, FMT, RR>), dim3(grid), dim3(256), (FMT == 3 ? win_off3 : (size_t)(SwLayout<DIAG, FMT, RR>::kWinOff)) + win, \
                        ctx->stream, x, y, A->n_rows, A->n_cols, sw->n_blocks, remap_arg, w, partials, stop, sw->hdr,   \
-                       sw->slice_chunk0, sw->codes, sw->dict, A->vdiag, x_al16 | (bis_opts().spmv_sellwin_nt != 0 ? 2 : 0), sw->blk_base, sw->pair_stride, sw->n_pairs, sw->diag_pair, own, dbg)
+                       sw->slice_chunk0, sw->codes, sw->dict, A->vd.p->diag_val, x_al16 | (bis_opts().spmv_sellwin_nt != 0 ? 2 : 0), sw->blk_base, sw->pair_stride, sw->n_pairs, sw->diag_pair, own, dbg)
 #define SW_L4N(MODE, DIAG, RR, NN)                                                                                      \
     hipLaunchKernelGGL((spmv_sellwin_kernel<MODE, DIAG, 3, RR, NN>), dim3(grid), dim3(256), win_off3 + win,             \
                        ctx->stream, x, y, A->n_rows, A->n_cols, sw->n_blocks, remap_arg, w, partials, stop, sw->hdr,   \
-                       sw->slice_chunk0, sw->codes, sw->dict, A->vdiag, x_al16 | (bis_opts().spmv_sellwin_nt != 0 ? 2 : 0), sw->blk_base, sw->pair_stride, sw->n_pairs, sw->diag_pair, own, dbg)
+                       sw->slice_chunk0, sw->codes, sw->dict, A->vd.p->diag_val, x_al16 | (bis_opts().spmv_sellwin_nt != 0 ? 2 : 0), sw->blk_base, sw->pair_stride, sw->n_pairs, sw->diag_pair, own, dbg)
 #define SW_L3(MODE, DIAG, FMT) do {                                                                                    \
         if (FMT == 3 && sw->uniform_chunks == 7 && sw->R == 2) SW_L4N(MODE, DIAG, 2, 7);                               \
         else if (FMT == 3 && sw->uniform_chunks == 2 && sw->R == 2) SW_L4N(MODE, DIAG, 2, 2);                          \

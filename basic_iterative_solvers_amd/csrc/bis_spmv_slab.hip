@@ -151,7 +151,7 @@ bis_status bis_spmv_colslab_build(bis_ctx *ctx, const bis_mat *A, int K, std::ve
 #undef BIS_SL_CHECK
     for (bis_mat *B : slabs) {
         if (bis_status st = bis_mat_finalize(ctx, B)) return cleanup(st);
-        B->vd_state = -1; // arbitrary values: no dictionary scan per slab
+        B->vd.state = -1; // arbitrary values: no dictionary scan per slab
     }
     *ok = true;
     return cleanup(BIS_OK);

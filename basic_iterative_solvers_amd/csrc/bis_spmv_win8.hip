@@ -3,7 +3,7 @@
 //
 // win8: the SAME window + sliced-ELL plan as the dictionary forms' (bis_spmv_sellwin.hip; what the two share is
 // bis_winplan.hpp) for matrices with ARBITRARY values (round 5).  Per non-zero the kernel streams the
-// 8-byte CRS value and a 2-byte window slot -- 10 bytes, like the packed row-block kernel of bis_spmv.hip -- but x comes
+// 8-byte CRS value and a 2-byte window slot -- 10 bytes, like the packed row-block kernel of bis_spmv_rowblock.hip -- but x comes
 // from the block's LDS window (every entry once per block, by LDS-DMA) instead of one 8-byte gather per non-zero through
 // the texture path, a lane owns a row (no product staging in LDS, no row_ptr, no second pass), and the stream is laid out
 // in the order the lanes consume it: a chunk = 4 entries of each of the 64 rows of a slice = 2560 contiguous bytes
@@ -724,15 +724,15 @@ static bis_status w8_try_rows(bis_ctx *ctx, bis_mat *A, int R, bool *window_too_
     sw->n_slices = (int64_t)nb * 4 * R;
     int32_t *slice_chunks = nullptr;
     void *tmp = nullptr;
-    int *status = (int *)ctx->counters + 52;
+    int *status = bis_slot_ptr(ctx, kSlotWinplan);
     W8_CHECK(hipMalloc(&sw->hdr, sizeof(int32_t) * 2 * kW8Runs * (size_t)nb));
     W8_CHECK(hipMalloc(&sw->own_rank, sizeof(int32_t) * (size_t)nb));
     W8_CHECK(hipMemsetAsync(sw->own_rank, 0xFF, sizeof(int32_t) * (size_t)nb, ctx->stream)); // (blocks the plan leaves early: -1)
     W8_CHECK(hipMalloc(&sw->row_of, sizeof(uint16_t) * (size_t)nb * kSwRows * (size_t)R));
     W8_CHECK(hipMalloc(&slice_chunks, sizeof(int32_t) * (size_t)(sw->n_slices + 1)));
     W8_CHECK(hipMalloc(&sw->slice_chunk0, sizeof(int64_t) * (size_t)(sw->n_slices + 1)));
-    W8_CHECK(hipMemsetAsync(status, 0, 3 * sizeof(int), ctx->stream));
-    W8_CHECK(hipMemsetAsync(status + 5, 0, sizeof(int), ctx->stream));
+    W8_CHECK(bis_slot_io(ctx, kSlotWinplan, 3));
+    W8_CHECK(bis_slot_io(ctx, kSlotWinplan + 5, 1));
     W8_CHECK(hipMemsetAsync(slice_chunks, 0, sizeof(int32_t) * (size_t)(sw->n_slices + 1), ctx->stream));
     W8_CHECK(hipMemsetAsync(sw->hdr, 0, sizeof(int32_t) * 2 * kW8Runs * (size_t)nb, ctx->stream));
     if (A->rp64) hipLaunchKernelGGL(w8_plan_kernel<int64_t>, dim3(nb), dim3(256), 0, ctx->stream, (const int64_t *)A->row_ptr, A->col, A->n_rows, R, kSwMaxGran, A->view_row0, sw->hdr, slice_chunks, sw->own_rank, sw->row_of, status);

@@ -86,7 +86,7 @@ def _check_kernel(name, A, cfg, info):
 def test_spmv_option_paths_bit_identical(ctx, oracle, name):
     """Every row-block configuration of SPMV_CONFIGS on a catalogue matrix (tests/helpers.py): y bit-identical to the
     default configuration's y -- phase 2 is one lane per row summing the parked products left to right in CRS order
-    (bis_spmv.hip "phase 2"), so staging, chunking, remapping and packing cannot change a bit -- and every row within its
+    (bis_spmv_rowblock.hip "phase 2"), so staging, chunking, remapping and packing cannot change a bit -- and every row within its
     own bound of the exact sum (helpers.check_rows).  y is poisoned with NaN before every call; x holds Inf / NaN at
     columns no row references.  Each configuration runs on a freshly created matrix and on a matrix created under the
     default options and rebuilt with retune(): the same bits.  spmv_kernel() must name the instance targeted."""
