@@ -477,6 +477,9 @@ class Context:
     def idr(self, A, b, x, s=4):
         return IDR(self, A, b, x, s)
 
+    def lsmr(self, A, b, x, At=None, damp=0.0, col_scaling=None):
+        return LSMR(self, A, b, x, At, damp, col_scaling)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -630,6 +633,12 @@ class Mat:
         h = C.c_void_p()
         self.ctx.check(self.ctx.lib.bis_mat_transpose(self.ctx.h, self.h, C.byref(h)))
         return Mat(self.ctx, h)
+
+    def row_norms(self):
+        """The 2-norms of the rows as a new Vec (bis_mat_row_norms); the column norms of A are A.transpose().row_norms()."""
+        out = self.ctx.alloc(self.n_rows)
+        self.ctx.check(self.ctx.lib.bis_mat_row_norms(self.ctx.h, self.h, C.c_void_p(out.ptr)))
+        return out
 
     def round_f32(self):
         """Round every value to fp32 in place in the fp64 CRS array and flag the matrix fp32-exact (bis_mat_round_f32): its SpMV
@@ -863,7 +872,7 @@ def _handle_pc(pc, Ls):
 
 
 class _Solver:
-    """What the seven solver handles share; a class names its library symbols bis_<_sym>_*."""
+    """What the solver handles share; a class names its library symbols bis_<_sym>_*."""
 
     _sym = None
 
@@ -1086,6 +1095,84 @@ class IDR(_Solver):
         self.ctx.check(self.ctx.lib.bis_idr_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv),
                                                    hist.ctypes, C.c_int(hist_cap)))
         return iters.value, bool(conv.value), hist[:min(iters.value + 1, hist_cap)].copy()
+
+
+class LSMR(_Solver):
+    """LSMR on one right-hand side as a device schedule (bis_lsmr_*): min ||A x - b||^2 + damp^2 ||x||^2 for a rectangular
+    A of any shape.  `At` is A.transpose() (made and owned by the handle when None).  `col_scaling` is a Vec d of n positive
+    entries, or "norm": d = 1 / the column norms of A, computed on the device, 1 where a norm is 0; the iteration then runs
+    on A diag(d) and damping acts on x / d.  `hist` estimates the residual of the normal equations and never increases,
+    `hist_r` the norm of the (stacked) residual.  x is the iterate of the last history entry.  No preconditioner."""
+
+    _sym = "lsmr"
+    REASON = {0: "live", 1: "tol_r", 2: "tol_ar", 3: "breakdown", 4: "non-finite"}
+
+    def __init__(self, ctx, A, b, x, At=None, damp=0.0, col_scaling=None):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self._own = []
+        if b.n < A.n_rows or x.n < A.n_cols:
+            raise BisError(f"LSMR: b needs {A.n_rows} entries and x {A.n_cols}")
+        try:
+            if isinstance(col_scaling, str):
+                if col_scaling != "norm":
+                    raise BisError(f"LSMR: unknown col_scaling {col_scaling!r}")
+                if At is None:
+                    At = A.transpose()
+                    self._own.append(At)
+                col_scaling = At.row_norms()
+                self._own.append(col_scaling)
+                ctx.check(ctx.lib.bis_lsmr_scaling_from_norms(ctx.h, C.c_void_p(col_scaling.ptr), _i64(A.n_cols),
+                                                              C.c_void_p(col_scaling.ptr)))
+            elif col_scaling is not None and col_scaling.n != A.n_cols:
+                raise BisError(f"LSMR: col_scaling has {col_scaling.n} entries, A has {A.n_cols} columns")
+            self._keep = (A, At, b, x, col_scaling)
+            ctx.check(ctx.lib.bis_lsmr_create(ctx.h, A.h, At.h if At is not None else C.c_void_p(), C.c_void_p(b.ptr),
+                                               C.c_void_p(x.ptr), C.byref(self.h)))
+            if damp:
+                ctx.check(ctx.lib.bis_lsmr_set_damping(ctx.h, self.h, C.c_double(damp)))
+            if col_scaling is not None:
+                ctx.check(ctx.lib.bis_lsmr_set_col_scaling(ctx.h, self.h, C.c_void_p(col_scaling.ptr)))
+        except Exception:
+            self.free()
+            raise
+        self.col_scaling = col_scaling
+
+    def set_preconditioner(self, *args, **kwargs):
+        raise BisError("LSMR has no preconditioner (bis_lsmr_*): use col_scaling")
+
+    def set_damping(self, damp):
+        self.ctx.check(self.ctx.lib.bis_lsmr_set_damping(self.ctx.h, self.h, C.c_double(damp)))
+
+    def set_col_scaling(self, d):
+        """d: a Vec of n entries, or None to clear; before init."""
+        if d is not None and d.n != self._keep[0].n_cols:
+            raise BisError(f"LSMR: col_scaling has {d.n} entries, A has {self._keep[0].n_cols} columns")
+        self.ctx.check(self.ctx.lib.bis_lsmr_set_col_scaling(self.ctx.h, self.h, C.c_void_p(d.ptr) if d is not None else C.c_void_p()))
+        self._keep = self._keep[:4] + (d,)
+        self.col_scaling = d
+
+    def init(self, tol_r, tol_ar=None):
+        """(r0, ar0); tol_ar=None: the same value as tol_r."""
+        r0, ar0 = C.c_double(), C.c_double()
+        self.ctx.check(self.ctx.lib.bis_lsmr_init(self.ctx.h, self.h, C.c_double(tol_r), C.c_double(tol_r if tol_ar is None else tol_ar),
+                                                  C.byref(r0), C.byref(ar0)))
+        return r0.value, ar0.value
+
+    def status(self, hist_cap=4096):
+        """dict(iters, converged, reason, hist (the ar column), hist_r), histories with entries 0 .. iters."""
+        iters, conv, reason = C.c_int(), C.c_int(), C.c_int()
+        hist, hist_r = np.zeros(hist_cap), np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_lsmr_status(self.ctx.h, self.h, C.byref(iters), C.byref(conv), C.byref(reason),
+                                                    hist.ctypes, hist_r.ctypes, C.c_int(hist_cap)))
+        cnt = min(iters.value + 1, hist_cap)
+        return dict(iters=iters.value, converged=bool(conv.value), reason=reason.value, hist=hist[:cnt].copy(), hist_r=hist_r[:cnt].copy())
+
+    def free(self):
+        super().free()
+        for o in self._own:
+            o.free()
+        self._own = []
 
 
 # ---- multi-GPU (1-D row partition) -------------------------------------------

@@ -1,5 +1,5 @@
 // bis_solver.hpp -- what the device-schedule solver handles share (bis_cg, bis_mcg, bis_mbicgstab, bis_mgmres, bis_fgmres,
-// bis_minres, bis_idr, bis_stat): the state of one life cycle (create, [set_preconditioner], init, iterate ..., status,
+// bis_minres, bis_idr, bis_lsmr, bis_stat): the state of one life cycle (create, [set_preconditioner], init, iterate ..., status,
 // destroy) with its allocation, release and the two reads *_status is made of; the scope in which a solve's stop flag
 // reaches the shared launchers; the layout of a last-arriver counter set; the scalar last-arriver reduction.  The host
 // functions are implemented in bis_solver.hip.

@@ -79,7 +79,7 @@ inline int &precond_block_size() { static int b = 0; return b; }
 inline int &precond_fill_level() { static int k = 0; return k; }
 // -ids S: the dimension s of the shadow space of -idr (bis_idr_create), 1..8
 inline int &idr_shadow_dim() { static int s = 4; return s; }
-enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR }; // FGMRES, MINRES, IDR: this build's additions (-fgm, -mr, -idr)
+enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR, LSMR }; // FGMRES, MINRES, IDR, LSMR: this build's additions (-fgm, -mr, -idr, -lsmr)
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
@@ -97,6 +97,7 @@ inline std::string to_string(SolverType t) {
     static const char *n[] = {"jacobi", "gauss-seidel", "symmetric-gauss-seidel", "gmres",
                               "conjugate-gradient", "bicgstab", "fgmres", "minres"};
     if (t == SolverType::IDR) return "idr(" + std::to_string(idr_shadow_dim()) + ")";
+    if (t == SolverType::LSMR) return "lsmr";
     return n[static_cast<int>(t)];
 }
 
@@ -110,6 +111,10 @@ struct Args {
     int fill_level = 0;                    // -fill K (precond_fill_level())
     bool fill_given = false;
     bool ids_given = false;                // -ids S (idr_shadow_dim())
+    double damp = 0.0;                     // -damp L: the Tikhonov parameter of -lsmr (bis_lsmr_set_damping)
+    bool damp_given = false;
+    bool colscale = false;                 // -colscale: -lsmr runs on A D, d = 1 / the column norms of A (bis_lsmr_set_col_scaling)
+    bool precond_given = false, perm_given = false; // -p, -perm appeared (refused with -lsmr)
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

@@ -36,6 +36,7 @@ inline void summary_output(Args *, Solver *solver) {
     std::cout << "With the stopping criteria \"tol * ||Ax_0 - b||_2\" is: " << solver->stopping_criteria << std::endl;
     std::cout << "The residual of the final iteration is: ||A*x_star - b||_2 = " << std::scientific
               << solver->collected_residual_norms[solver->collected_residual_norms_count - 1] << ".\n";
+    solver->summary_extra();
 }
 
 inline void postprocessing(Args *cli_args, Solver *solver, Timers *) { summary_output(cli_args, solver); }

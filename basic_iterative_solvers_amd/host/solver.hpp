@@ -91,6 +91,7 @@ class Solver {
     }
     virtual void check_restart(Timers *) {}
     virtual void get_explicit_x() {}
+    virtual void summary_extra() {} // lines a method adds behind the summary (-lsmr)
     virtual ~Solver() {
         double *v[] = {x_star, x_0, b, tmp, work, residual, residual_0, A_D, A_D_inv, A_D_scale, L_D, U_D};
         for (auto p : v) dfree(p);
@@ -125,7 +126,7 @@ class Solver {
         }
     }
     void init_stopping_criteria() { stopping_criteria = tolerance * residual_norm; }
-    bool check_stopping_criteria() {
+    virtual bool check_stopping_criteria() { // (virtual for -lsmr, which also stops where its handle did)
         const bool norm_convergence = std::abs(residual_norm) < stopping_criteria;
         const bool over_max_iters = iter_count >= (max_iters - gmres_restart_count);
         const bool divergence = std::abs(residual_norm) > DBL_MAX || std::isnan(residual_norm);

@@ -81,7 +81,8 @@ struct MatrixCOO {
     std::vector<int> I, J;
     std::vector<double> values;
 
-    void read_from_mtx(const std::string &path) {
+    // allow_rect: a matrix with M != N is read as it is (the method -lsmr); every other caller keeps the reference's refusal
+    void read_from_mtx(const std::string &path, bool allow_rect = false) {
         FILE *f = fopen(path.c_str(), "rb");
         if (!f) throw std::runtime_error("Unable to open file: " + path);
         std::string buf;
@@ -119,8 +120,9 @@ struct MatrixCOO {
             have_size = sscanf(std::string(l, p).c_str(), "%ld %ld %ld", &M, &N, &nz) == 3;
         }
         if (!have_size) throw std::runtime_error("Error reading matrix from file: " + path);
-        if (M != N) throw std::runtime_error("Matrix must be square.");
-        if (M >= INT32_MAX) throw std::runtime_error("Matrix dimension exceeds the 32-bit column index range: " + path);
+        if (M != N && !allow_rect) throw std::runtime_error("Matrix must be square.");
+        if (M != N && symm) throw std::runtime_error("A symmetric Matrix Market banner needs a square matrix: " + path);
+        if (M >= INT32_MAX || N >= INT32_MAX) throw std::runtime_error("Matrix dimension exceeds the 32-bit column index range: " + path);
         // parse the entries: T threads on runs of whole lines
         const unsigned hw = std::thread::hardware_concurrency();
         const int T = (int)std::max(1u, std::min(16u, std::min(hw ? hw : 1u, (unsigned)((end - p) / (1 << 20)) + 1u)));

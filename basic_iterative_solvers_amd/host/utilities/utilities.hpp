@@ -13,7 +13,9 @@
 // GMRES(m) on the device schedule bis_fgmres_* (methods/fgmres.hpp), which takes every -p type, the K-cycles included; the method
 // `-mr` is MINRES for symmetric, possibly indefinite matrices on the device schedule bis_minres_* (methods/minres.hpp);
 // the method `-idr` is IDR(s) for nonsymmetric matrices on the device schedule bis_idr_* (methods/idr.hpp) and `-ids S` its s (default 4);
-// `-p bj` is block Jacobi (bis_bj_create) on blocks of `-bs N` consecutive rows (default: the dof of the grid hint).
+// `-p bj` is block Jacobi (bis_bj_create) on blocks of `-bs N` consecutive rows (default: the dof of the grid hint);
+// the method `-lsmr` is LSMR for least-squares problems on the device schedule bis_lsmr_* (methods/lsmr.hpp), the one method that
+// takes a rectangular .mtx; `-damp L` is its Tikhonov parameter and `-colscale` scales the columns of A to norm 1.
 #pragma once
 
 #include <sys/stat.h>
@@ -38,6 +40,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     else if (st == "-fgm") a->method = SolverType::FGMRES;
     else if (st == "-mr") a->method = SolverType::MINRES;
     else if (st == "-idr") a->method = SolverType::IDR;
+    else if (st == "-lsmr") a->method = SolverType::LSMR;
     else {
         printf("ERROR: parse_cli: Please choose an available solver:"
                "\n-j (Jacobi)\n-gs (Gauss-Seidel)\n-sgs (Symmetric Gauss-Seidel)"
@@ -45,7 +48,8 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                "\n-bi ([Preconditioned] BiCGSTAB)"
                "\n-fgm ([Preconditioned] flexible GMRES, right-preconditioned)"
                "\n-mr ([Preconditioned] MINRES, symmetric indefinite matrices)"
-               "\n-idr ([Preconditioned] IDR(s), nonsymmetric matrices, -ids S = 1..8)\n");
+               "\n-idr ([Preconditioned] IDR(s), nonsymmetric matrices, -ids S = 1..8)"
+               "\n-lsmr (LSMR, least-squares problems with rectangular matrices, -damp L >= 0, -colscale)\n");
         exit(EXIT_FAILURE);
     }
     for (int i = 3; i < argc; ++i) {
@@ -76,6 +80,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 exit(EXIT_FAILURE);
             }
             a->preconditioner = it->second;
+            a->precond_given = true;
         } else if (arg == "-scale" && i + 1 < argc) a->num_scale = (bool)atoi(argv[++i]);
         else if (arg == "-rl" && i + 1 < argc) a->restart_length = atoi(argv[++i]);
         else if (arg == "-inner" && i + 1 < argc) {
@@ -124,6 +129,16 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             a->ids_given = true;
             idr_shadow_dim() = sd;
         }
+        else if (arg == "-damp" && i + 1 < argc) {
+            char *end = nullptr;
+            a->damp = strtod(argv[++i], &end);
+            if (end == argv[i] || *end != '\0' || !(a->damp >= 0.0) || !std::isfinite(a->damp)) {
+                fprintf(stderr, "ERROR: -damp L: the Tikhonov parameter of -lsmr, L >= 0 and finite\n");
+                exit(EXIT_FAILURE);
+            }
+            a->damp_given = true;
+        }
+        else if (arg == "-colscale") a->colscale = true;
         else if (arg == "-mg" && i + 1 < argc) {
             bis_mg_params &p = precond_mg_params();
             std::stringstream ss(argv[++i]);
@@ -179,7 +194,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                 exit(EXIT_FAILURE);
             }
         }
-        else if (arg == "-perm" && i + 1 < argc) a->perm_mode = argv[++i];
+        else if (arg == "-perm" && i + 1 < argc) { a->perm_mode = argv[++i]; a->perm_given = true; }
         else if (arg == "-dump-perm" && i + 1 < argc) a->dump_perm = argv[++i];
         else if (arg == "-dump-x" && i + 1 < argc) a->dump_x = argv[++i];
         else if (arg == "-perm-host") a->perm_host = true;
@@ -232,6 +247,19 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     }
     if (a->method == SolverType::FGMRES && (a->unfused || a->host_scalars)) {
         fprintf(stderr, "ERROR: -fgm is a device schedule (bis_fgmres_*) and has no call-by-call form: -unfused and -hostscalars do not apply\n");
+        exit(EXIT_FAILURE);
+    }
+    if (a->method == SolverType::LSMR) {
+        // a rectangular system has no triangles to sweep, no symmetric permutation or scaling, and the handle is the only form
+        const char *flag = a->precond_given ? "-p" : a->perm_given ? "-perm" : a->unfused ? "-unfused" : a->host_scalars ? "-hostscalars"
+                           : a->num_scale ? "-scale 1" : nullptr;
+        if (flag) {
+            fprintf(stderr, "ERROR: %s does not apply to -lsmr (LSMR on the device schedule bis_lsmr_*: no preconditioner, permutation, "
+                            "symmetric scaling or call-by-call form; use -colscale and -damp L)\n", flag);
+            exit(EXIT_FAILURE);
+        }
+    } else if (a->damp_given || a->colscale) {
+        fprintf(stderr, "ERROR: %s is an option of LSMR: it needs the method -lsmr\n", a->damp_given ? "-damp L" : "-colscale");
         exit(EXIT_FAILURE);
     }
     if (a->fill_given && a->preconditioner != PrecondType::ILU0 && a->preconditioner != PrecondType::ILU0Iter) {

@@ -1449,6 +1449,130 @@ BIS_API bis_status bis_idr_status(bis_ctx *ctx, bis_idr *h, int *iters, int *con
                                   int hist_cap);
 BIS_API bis_status bis_idr_destroy(bis_ctx *ctx, bis_idr *h);
 
+/* ---- LSMR on the device (no reference counterpart) -----------------------------
+ * LSMR (Fong and Saunders, 2011) for the least-squares problem
+ *     min ||A x - b||_2^2 + lambda^2 ||x||_2^2
+ * with A of size m x n and any of m > n, m < n, m = n: over-determined,
+ * under-determined, inconsistent and rank-deficient systems, and Tikhonov-regularised
+ * ones (lambda >= 0, default 0).  It is MINRES on the normal equations without forming
+ * them: short recurrences, two m-vectors and four n-vectors at any iteration count, two
+ * products per iteration -- bis_spmv with A and bis_spmv with At, the matrix
+ * bis_mat_transpose makes (the caller passes it, or the handle makes and owns it).
+ * Both products go through the SpMV's launcher: every SpMV form applies to both.
+ * From x0 the iterates stay in x0 + range(At): with x0 = 0 and lambda = 0 the limit is
+ * the minimum-norm solution.
+ * Column scaling: with d (n entries, d > 0; bis_lsmr_set_col_scaling) the iteration
+ * runs on A D, D = diag(d), in the variable y = D^-1 x, and DAMPING ACTS ON y: the
+ * problem solved is min ||A D y - b||^2 + lambda^2 ||y||^2, x = D y.  With lambda = 0
+ * that is the problem above (the same x when A has full column rank; the solution of
+ * least ||D^-1 x|| otherwise).
+ * init: u~ = b - A x0;  beta1 = sqrt((u~, u~));  ib = 1/beta1;
+ *       p = (At u~) ib;  p = p d where a scaling is set;  alpha1 = sqrt((p, p));
+ *       ia = 1/alpha1;  v = p ia;  h = v;  hbar = 0;
+ *       zetabar = alpha1 beta1;  alphabar = alpha1;  rho = rhobar = cbar = 1;  sbar = 0;
+ *       betadd = beta1;  betad = 0;  rhodold = 1;  tautildeold = thetatilde = zeta = 0;
+ *       dsum = 0.
+ * History entry 0 is zetabar in the column `ar` and beta1 in the column `r`.
+ * Iteration k = 1, 2, ... (u~ = beta u is kept un-normalised):
+ *     t_m = A w                        w = v, or w = d v (elementwise) with a scaling
+ *     u~  = fma(-(alpha ib), u~, t_m);  beta = sqrt((u~, u~));  ib = 1/beta
+ *     t_n = At u~
+ *     p   = t_n ib;  p = p d with a scaling;  v~ = fma(-beta, v, p);
+ *     alpha = sqrt((v~, v~));  ia = 1/alpha
+ *     (chat, shat, alphahat) = rot(alphabar, lambda)
+ *     rhoold = rho;  (c, s, rho) = rot(alphahat, beta);
+ *     thetanew = s alpha;  alphabar = c alpha
+ *     rhobarold = rhobar;  zetaold = zeta;  thetabar = sbar rho;
+ *     (cbar, sbar, rhobar) = rot(cbar rho, thetanew);
+ *     zeta = cbar zetabar;  zetabar = -sbar zetabar
+ *     betaacute = chat betadd;  betacheck = -shat betadd;
+ *     betahat = c betaacute;  betadd = -s betaacute
+ *     thetatildeold = thetatilde;  (ctildeold, stildeold, rhotildeold) = rot(rhodold, thetabar);
+ *     thetatilde = stildeold rhobar;  rhodold = ctildeold rhobar;
+ *     betad = -stildeold betad + ctildeold betahat
+ *     tautildeold = (zetaold - thetatildeold tautildeold) / rhotildeold
+ *     taud = (zeta - thetatilde tautildeold) / rhodold
+ *     dsum = dsum + betacheck^2
+ *     ar[k] = |zetabar|;  r[k] = sqrt(dsum + (betad - taud)^2 + betadd^2);  stop test
+ *     v = v~ ia
+ *     hbar = fma(-thetabar rho / (rhoold rhobarold), hbar, h)
+ *     x    = fma(zeta / (rho rhobar), hbar, x)      with a scaling: fma(..., d hbar, x)
+ *     h    = fma(-thetanew / rho, h, v)
+ *     w    = d v                                    with a scaling
+ * rot(a, b): den = sqrt(a^2 + b^2), c = a/den, s = b/den; den = 0 gives c = 1, s = 0.
+ * The next iteration's alpha ib is formed (one product) in the same place.  Every
+ * scalar operation is rounded separately; a division whose divisor is 0 gives 0.
+ * What the two history columns estimate, with Abar = A D (D = I without a scaling),
+ * y = D^-1 x and rbar = [b - A x; -lambda y]:
+ *     ar[k] ~ ||Abar^T (b - A x_k) - lambda^2 y_k||_2, the residual of the normal
+ *             equations of the (scaled, damped) problem; it never increases;
+ *     r[k]  ~ ||rbar_k|| = sqrt(||b - A x_k||^2 + lambda^2 ||y_k||^2).
+ * So with a scaling ar measures the gradient in the scaled variable, D A^T r, not
+ * A^T r, and with damping r is not ||b - A x|| but the norm of the stacked residual.
+ * Both are recurrences, not explicit norms; entry 0 of each is explicit.
+ * Stop: ar[k] < tol_ar ar[0] (reason 2), r[k] < tol_r r[0] (reason 1), or a non-finite
+ * entry (reason 4, not converged).  A tolerance of 0 never fires.  r is tested before
+ * ar, a non-finite entry and a breakdown before both.
+ * Breakdown (reason 3, converged): beta = 0 or alpha = 0 in an iteration ends the
+ * solve in that iteration with ar entry 0; the reciprocal of zero is never formed, 0
+ * stands for it.  ar[0] = 0 -- x0 is a least-squares solution already (b = 0 with
+ * x0 = 0 is one case) -- is the same breakdown at alpha1: bis_lsmr_init marks the
+ * solve stopped and converged with 0 iterations, and x is never written.
+ * Schedule per iteration: SpMV A, pass U (the u~ line with its sum fused, the last
+ * workgroup forms beta and ib), SpMV At, pass V (the p and v~ lines with the sum
+ * fused; v~ lives in t_n; the last workgroup's lane 0 does every scalar line, the
+ * history and the stop test), pass H (v, hbar, x, h and w in one pass).  Beside the two
+ * products that is 24 bytes per row of A and 88 per column (U 24; V 24; H 64), with a
+ * scaling 24 + 112.  All on 16-byte accesses with a scalar path for an odd tail, on
+ * the grids of the BLAS-1 layer.  The sums are bis_dot's: its grid, index map, two fma
+ * chains per lane and its order of the block and partial sums, which the workgroup
+ * that arrives last adds (no floating-point atomics, no waiting): two runs give the
+ * same bits.  Scalars, history and the stop flag stay on the device; bis_lsmr_iterate
+ * reads nothing back.  After the stop every launch returns at once except pass H of
+ * the stopping iteration: x is the iterate of the last history entry at every step
+ * (there is no pending combine), and no later call changes x, the histories or the
+ * status.
+ * Memory: u~ and t_m (m doubles each), v, h, hbar, t_n (n each), w with a scaling (m
+ * and n rounded up to even), At when the handle made it, the two history columns.
+ * There is no set_preconditioner: a left or right M^-1 on a rectangular problem is not
+ * what bis_apply_preconditioner provides (its operators are square, of A's size); the
+ * diagonal right scaling above is the one conditioning device, and bis_mat_row_norms of
+ * At (the column norms of A) with bis_lsmr_scaling_from_norms gives the usual choice.
+ * No tuning option.
+ * Errors: a null context: BIS_ERR_NO_DEVICE, the out-parameters are left alone.  Null
+ * arguments or a null handle, an At that is not n x m with A's number of entries, b,
+ * x or d off a 16-byte boundary, lambda negative or not finite, a setter after
+ * bis_lsmr_init, bis_lsmr_iterate before it: BIS_ERR_INVALID with a message naming the
+ * call.  m = 0 or n = 0: BIS_OK, nothing is launched.  *out is written on success only. */
+typedef struct bis_lsmr bis_lsmr;
+/* At: A^T as bis_mat_transpose makes it, or NULL: the handle makes it and owns it */
+BIS_API bis_status bis_lsmr_create(bis_ctx *ctx, const bis_mat *A, const bis_mat *At, const double *b /* m */,
+                                   double *x /* n, in/out */, bis_lsmr **out);
+/* before bis_lsmr_init; lambda >= 0 and finite */
+BIS_API bis_status bis_lsmr_set_damping(bis_ctx *ctx, bis_lsmr *h, double lambda);
+/* before bis_lsmr_init; d: n entries on the device, read at every iteration (the caller keeps it alive); NULL clears */
+BIS_API bis_status bis_lsmr_set_col_scaling(bis_ctx *ctx, bis_lsmr *h, const double *d);
+/* Reuse: bis_lsmr_init may be called again at any time (after a failed bis_lsmr_iterate it must be).  It reads b and x
+ * as they are at that call and discards every earlier state: v, h, hbar, w, the scalars, the count, both history
+ * columns and the flags, NaN included; damping, scaling and At stay.  The solve that follows is, bit for bit, that of
+ * a new handle.  The setters stay refused (BIS_ERR_INVALID) once bis_lsmr_init has run. */
+/* blocking; r0_host and ar0_host (each may be NULL) receive beta1 and zetabar = alpha1 beta1 */
+BIS_API bis_status bis_lsmr_init(bis_ctx *ctx, bis_lsmr *h, double tol_r, double tol_ar, double *r0_host, double *ar0_host);
+/* non-blocking: enqueues n_iters iterations */
+BIS_API bis_status bis_lsmr_iterate(bis_ctx *ctx, bis_lsmr *h, int n_iters);
+/* blocking: iterations, converged flag, reason (0 live, 1 tol_r, 2 tol_ar, 3 breakdown, 4 non-finite) and entries
+ * 0 .. iterations of the two history columns (at most hist_cap of each; each pointer may be NULL) */
+BIS_API bis_status bis_lsmr_status(bis_ctx *ctx, bis_lsmr *h, int *iters, int *converged, int *reason,
+                                   double *hist_ar_host, double *hist_r_host, int hist_cap);
+BIS_API bis_status bis_lsmr_destroy(bis_ctx *ctx, bis_lsmr *h);
+/* out[i] = sqrt(sum_k a_ik^2) for the n_rows rows of A (out on the device): one fma chain per row over its entries in
+ * CRS order, from 0; an empty row gives 0; no atomics.  The column norms of A are the row norms of its transpose.
+ * Non-blocking. */
+BIS_API bis_status bis_mat_row_norms(bis_ctx *ctx, const bis_mat *A, double *out);
+/* d[i] = 1 / norms[i], and 1 where norms[i] is 0 (n entries, both on the device; d may be norms): the column scaling
+ * that gives A D columns of norm 1.  Non-blocking. */
+BIS_API bis_status bis_lsmr_scaling_from_norms(bis_ctx *ctx, const double *norms, int64_t n, double *d);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
