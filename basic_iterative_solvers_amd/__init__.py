@@ -480,6 +480,9 @@ class Context:
     def lsmr(self, A, b, x, At=None, damp=0.0, col_scaling=None):
         return LSMR(self, A, b, x, At, damp, col_scaling)
 
+    def eigs(self, A, k=4, which="SA", ncv=None, tol=1e-10, v0=None, n=None):
+        return Eigs(self, A, k, which, ncv, tol, v0, n)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -1173,6 +1176,101 @@ class LSMR(_Solver):
         for o in self._own:
             o.free()
         self._own = []
+
+
+class Eigs(_Solver):
+    """Thick-restart Lanczos with full re-orthogonalisation as a device schedule (bis_eigs_*): the k smallest ("SA"),
+    largest ("LA") or largest in magnitude ("LM") eigenpairs of a symmetric matrix.  `ncv` is the basis size, k < ncv <=
+    min(n, 64) (None: min(n, 64, max(2k + 1, 20))); `v0` a Vec of n entries (None: column 0 of IDR's hashed shadow space).
+    A=None with n= is the caller-applied mode: `iterate` is refused, every product is the caller's, between `op_begin()` and
+    `op_end()` on the context's stream (shift-and-invert with a MINRES handle).  No preconditioner."""
+
+    _sym = "eigs"
+    WHICH = {"SA": 0, "LA": 1, "LM": 2}
+    REASON = {0: "live", 1: "converged", 2: "invariant", 3: "jacobi", 4: "bad_start"}
+
+    def __init__(self, ctx, A, k=4, which="SA", ncv=None, tol=1e-10, v0=None, n=None):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        if which not in self.WHICH:
+            raise BisError(f"Eigs: which must be one of SA, LA, LM, not {which!r}")
+        if A is None and n is None:
+            raise BisError("Eigs: the caller-applied mode (A=None) needs n=")
+        self.n = int(A.n_rows if A is not None else n)
+        self.k, self.which, self.tol = int(k), which, float(tol)
+        self._keep = (A, v0)
+        ctx.check(ctx.lib.bis_eigs_create(ctx.h, A.h if A is not None else C.c_void_p(), _i64(self.n), C.c_int(self.k),
+                                          C.c_int(0 if ncv is None else int(ncv)), C.c_int(self.WHICH[which]), C.byref(self.h)))
+        self.ncv = int(ncv) if ncv is not None else min(self.n, 64, max(2 * self.k + 1, 20))
+        if v0 is not None:
+            try:
+                self.set_start(v0)
+            except Exception:
+                self.free()
+                raise
+
+    def set_preconditioner(self, *args, **kwargs):
+        raise BisError("Eigs has no preconditioner (bis_eigs_*)")
+
+    def set_start(self, v0):
+        """v0: a Vec of n entries, or None for the default; before init."""
+        if v0 is not None and v0.n < self.n:
+            raise BisError(f"Eigs: v0 has {v0.n} entries, the operator has {self.n} rows")
+        self.ctx.check(self.ctx.lib.bis_eigs_set_start(self.ctx.h, self.h, C.c_void_p(v0.ptr) if v0 is not None else C.c_void_p()))
+        self._keep = (self._keep[0], v0)
+
+    def init(self, tol=None):
+        if tol is not None:
+            self.tol = float(tol)
+        self.ctx.check(self.ctx.lib.bis_eigs_init(self.ctx.h, self.h, C.c_double(self.tol)))
+
+    def iterate(self, cycles=1):
+        self.ctx.check(self.ctx.lib.bis_eigs_iterate(self.ctx.h, self.h, C.c_int(int(cycles))))
+
+    def op_begin(self):
+        """(inp, out): two Vec views of n entries; enqueue out = OP inp on the context's stream, then call op_end()."""
+        inp, out = C.c_void_p(), C.c_void_p()
+        self.ctx.check(self.ctx.lib.bis_eigs_op_begin(self.ctx.h, self.h, C.byref(inp), C.byref(out)))
+        return Vec(self.ctx, inp.value, self.n, False), Vec(self.ctx, out.value, self.n, False)
+
+    def op_end(self):
+        self.ctx.check(self.ctx.lib.bis_eigs_op_end(self.ctx.h, self.h))
+
+    def status(self, hist_cap=4096):
+        """dict(products, restarts, stopped, converged, reason, nconv, values, est, hist, hist_nconv): values and estimates of
+        the last restart in rank order, the histories with one entry per restart."""
+        prod, rest, stop, conv, reason, nconv = (C.c_int() for _ in range(6))
+        values, est = np.zeros(self.k), np.zeros(self.k)
+        hist, hist_n = np.zeros(hist_cap), np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_eigs_status(self.ctx.h, self.h, C.byref(prod), C.byref(rest), C.byref(stop), C.byref(conv),
+                                                    C.byref(reason), C.byref(nconv), values.ctypes, est.ctypes, hist.ctypes,
+                                                    hist_n.ctypes, C.c_int(hist_cap)))
+        cnt = min(rest.value, hist_cap)
+        return dict(products=prod.value, restarts=rest.value, stopped=bool(stop.value), converged=bool(conv.value),
+                    reason=reason.value, nconv=nconv.value, values=values, est=est, hist=hist[:cnt].copy(),
+                    hist_nconv=hist_n[:cnt].astype(np.int64))
+
+    def vectors(self):
+        """The Ritz vectors of the last restart in rank order as a host n x k array."""
+        X = self.ctx.alloc(self.n * self.k)
+        try:
+            self.ctx.check(self.ctx.lib.bis_eigs_vectors(self.ctx.h, self.h, C.c_void_p(X.ptr), _i64(self.n)))
+            return X.to_host().reshape(self.k, self.n).T.copy()
+        finally:
+            X.free()
+
+    def solve(self, max_cycles=100, batch=4):
+        """init, then iterate in batches of `batch` cycles and poll until the solve stops or max_cycles are enqueued; status()."""
+        self.init()
+        done = 0
+        while done < max_cycles:
+            step = min(batch, max_cycles - done)
+            self.iterate(step)
+            done += step
+            st = self.status()
+            if st["stopped"]:
+                return st
+        return self.status()
 
 
 # ---- multi-GPU (1-D row partition) -------------------------------------------

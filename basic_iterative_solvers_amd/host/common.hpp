@@ -79,7 +79,12 @@ inline int &precond_block_size() { static int b = 0; return b; }
 inline int &precond_fill_level() { static int k = 0; return k; }
 // -ids S: the dimension s of the shadow space of -idr (bis_idr_create), 1..8
 inline int &idr_shadow_dim() { static int s = 4; return s; }
-enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR, LSMR }; // FGMRES, MINRES, IDR, LSMR: this build's additions (-fgm, -mr, -idr, -lsmr)
+// -eig K [-which sa|la|lm] [-ncv M]: the wanted pairs, the end of the spectrum (BIS_EIGS_SA / _LA / _LM) and the basis size
+// (0: the handle's default, filled in once the handle is made) of bis_eigs_create
+inline int &eigs_k() { static int k = 0; return k; }
+inline int &eigs_which() { static int w = 0; return w; }
+inline int &eigs_ncv() { static int m = 0; return m; }
+enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR, LSMR, Eigs }; // FGMRES, MINRES, IDR, LSMR, Eigs: this build's additions (-fgm, -mr, -idr, -lsmr, -eig K)
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
@@ -98,6 +103,10 @@ inline std::string to_string(SolverType t) {
                               "conjugate-gradient", "bicgstab", "fgmres", "minres"};
     if (t == SolverType::IDR) return "idr(" + std::to_string(idr_shadow_dim()) + ")";
     if (t == SolverType::LSMR) return "lsmr";
+    if (t == SolverType::Eigs) {
+        static const char *w[] = {"sa", "la", "lm"};
+        return "lanczos(" + std::to_string(eigs_k()) + ", ncv=" + std::to_string(eigs_ncv()) + ", " + w[eigs_which()] + ")";
+    }
     return n[static_cast<int>(t)];
 }
 
@@ -114,7 +123,8 @@ struct Args {
     double damp = 0.0;                     // -damp L: the Tikhonov parameter of -lsmr (bis_lsmr_set_damping)
     bool damp_given = false;
     bool colscale = false;                 // -colscale: -lsmr runs on A D, d = 1 / the column norms of A (bis_lsmr_set_col_scaling)
-    bool precond_given = false, perm_given = false; // -p, -perm appeared (refused with -lsmr)
+    bool precond_given = false, perm_given = false; // -p, -perm appeared (refused with -lsmr and -eig)
+    bool which_given = false, ncv_given = false, scale_given = false; // -which, -ncv (options of -eig), -scale appeared
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

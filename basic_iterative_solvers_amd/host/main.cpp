@@ -1,12 +1,13 @@
 // main.cpp -- CLI driver of the MI355X build; same command line and the same
 // stdout (residual table, summary, timer tree) as the reference's main.cpp.
-//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-idr [-ids S]|-bi|-lsmr [-damp L] [-colscale]>
+//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-idr [-ids S]|-bi|-lsmr [-damp L] [-colscale]|-eig K [-which sa|la|lm] [-ncv M]>
 //        [-p j|gs|bgs|sgs|2st|s2st|ilu0|ilu0it|fsai|mg|bj] [-mg KEY=VALUE,... (nu, cs, limit, levels, scale, omega, coarsening, cycle=v|w|k|kgcr, klev, smooth=0|1, pomega, smoother=jacobi|cheb, degree, ratio, est, safety)] [-bs N] [-fill K (level-of-fill of ilu0 / ilu0it, 0..16)] [-inner K] [-pprec 32|64] [-scale 0|1] [-rl N] [-unfused] [-dev K]
 #include <chrono>
 
 #include "common.hpp"
 #include "methods/bicgstab.hpp"
 #include "methods/cg.hpp"
+#include "methods/eigs.hpp"
 #include "methods/fgmres.hpp"
 #include "methods/gauss_seidel.hpp"
 #include "methods/gmres.hpp"
@@ -34,6 +35,7 @@ static void run(Args *cli_args, Timers *timers) {
     case SolverType::MINRES: solver = new MINRESSolver(cli_args); break;
     case SolverType::IDR: solver = new IDRSolver(cli_args); break;
     case SolverType::LSMR: solver = new LSMRSolver(cli_args); break;
+    case SolverType::Eigs: solver = new EigsSolver(cli_args); break;
     }
     auto A = std::make_unique<MatrixCRS>();
     if (!make_generated_matrix(cli_args->matrix_file_name, A.get())) {

@@ -15,7 +15,9 @@
 // the method `-idr` is IDR(s) for nonsymmetric matrices on the device schedule bis_idr_* (methods/idr.hpp) and `-ids S` its s (default 4);
 // `-p bj` is block Jacobi (bis_bj_create) on blocks of `-bs N` consecutive rows (default: the dof of the grid hint);
 // the method `-lsmr` is LSMR for least-squares problems on the device schedule bis_lsmr_* (methods/lsmr.hpp), the one method that
-// takes a rectangular .mtx; `-damp L` is its Tikhonov parameter and `-colscale` scales the columns of A to norm 1.
+// takes a rectangular .mtx; `-damp L` is its Tikhonov parameter and `-colscale` scales the columns of A to norm 1;
+// the method `-eig K` is the thick-restart Lanczos eigensolver on the device schedule bis_eigs_* (methods/eigs.hpp): the K smallest
+// (`-which sa`, the default), largest (`la`) or largest in magnitude (`lm`) eigenpairs of a symmetric matrix with a basis of `-ncv M`.
 #pragma once
 
 #include <sys/stat.h>
@@ -41,6 +43,16 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
     else if (st == "-mr") a->method = SolverType::MINRES;
     else if (st == "-idr") a->method = SolverType::IDR;
     else if (st == "-lsmr") a->method = SolverType::LSMR;
+    else if (st == "-eig") {
+        a->method = SolverType::Eigs;
+        char *end = nullptr;
+        const long kk = argc > 3 ? strtol(argv[3], &end, 10) : 0;
+        if (argc <= 3 || end == argv[3] || *end != '\0' || kk < 1 || kk > 63) {
+            fprintf(stderr, "ERROR: -eig K: the number of wanted eigenpairs, 1 <= K <= 63\n");
+            exit(EXIT_FAILURE);
+        }
+        eigs_k() = (int)kk;
+    }
     else {
         printf("ERROR: parse_cli: Please choose an available solver:"
                "\n-j (Jacobi)\n-gs (Gauss-Seidel)\n-sgs (Symmetric Gauss-Seidel)"
@@ -49,10 +61,11 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                "\n-fgm ([Preconditioned] flexible GMRES, right-preconditioned)"
                "\n-mr ([Preconditioned] MINRES, symmetric indefinite matrices)"
                "\n-idr ([Preconditioned] IDR(s), nonsymmetric matrices, -ids S = 1..8)"
-               "\n-lsmr (LSMR, least-squares problems with rectangular matrices, -damp L >= 0, -colscale)\n");
+               "\n-lsmr (LSMR, least-squares problems with rectangular matrices, -damp L >= 0, -colscale)"
+               "\n-eig K (thick-restart Lanczos, the K extreme eigenpairs of a symmetric matrix, -which sa|la|lm, -ncv M)\n");
         exit(EXIT_FAILURE);
     }
-    for (int i = 3; i < argc; ++i) {
+    for (int i = a->method == SolverType::Eigs ? 4 : 3; i < argc; ++i) { // (-eig K: argv[3] is K)
         const std::string arg = argv[i];
         if (arg == "-p") {
             if (i + 1 >= argc) {
@@ -81,7 +94,7 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             }
             a->preconditioner = it->second;
             a->precond_given = true;
-        } else if (arg == "-scale" && i + 1 < argc) a->num_scale = (bool)atoi(argv[++i]);
+        } else if (arg == "-scale" && i + 1 < argc) { a->num_scale = (bool)atoi(argv[++i]); a->scale_given = true; }
         else if (arg == "-rl" && i + 1 < argc) a->restart_length = atoi(argv[++i]);
         else if (arg == "-inner" && i + 1 < argc) {
             a->inner_iters = atoi(argv[++i]);
@@ -139,6 +152,25 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
             a->damp_given = true;
         }
         else if (arg == "-colscale") a->colscale = true;
+        else if (arg == "-which" && i + 1 < argc) {
+            const std::string w = argv[++i];
+            if (w != "sa" && w != "la" && w != "lm") {
+                fprintf(stderr, "ERROR: -which sa|la|lm: the end of the spectrum -eig K looks for (smallest, largest, largest in magnitude)\n");
+                exit(EXIT_FAILURE);
+            }
+            eigs_which() = w == "sa" ? BIS_EIGS_SA : w == "la" ? BIS_EIGS_LA : BIS_EIGS_LM;
+            a->which_given = true;
+        }
+        else if (arg == "-ncv" && i + 1 < argc) {
+            char *end = nullptr;
+            const long m = strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end != '\0' || m < 2 || m > 64) {
+                fprintf(stderr, "ERROR: -ncv M: the basis size of -eig K, K < M <= min(n, 64)\n");
+                exit(EXIT_FAILURE);
+            }
+            eigs_ncv() = (int)m;
+            a->ncv_given = true;
+        }
         else if (arg == "-mg" && i + 1 < argc) {
             bis_mg_params &p = precond_mg_params();
             std::stringstream ss(argv[++i]);
@@ -260,6 +292,24 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         }
     } else if (a->damp_given || a->colscale) {
         fprintf(stderr, "ERROR: %s is an option of LSMR: it needs the method -lsmr\n", a->damp_given ? "-damp L" : "-colscale");
+        exit(EXIT_FAILURE);
+    }
+    if (a->method == SolverType::Eigs) {
+        // an eigenproblem has no right-hand side to precondition, the permutation and the scaling would change the vectors, and
+        // the handle is the only form
+        const char *flag = a->precond_given ? "-p" : a->perm_given ? "-perm" : a->scale_given ? "-scale" : a->unfused ? "-unfused"
+                           : a->host_scalars ? "-hostscalars" : nullptr;
+        if (flag) {
+            fprintf(stderr, "ERROR: %s does not apply to -eig K (thick-restart Lanczos on the device schedule bis_eigs_*: no preconditioner, "
+                            "permutation, scaling or call-by-call form; use -which sa|la|lm and -ncv M)\n", flag);
+            exit(EXIT_FAILURE);
+        }
+        if (a->ncv_given && eigs_ncv() <= eigs_k()) {
+            fprintf(stderr, "ERROR: -ncv M: the basis size of -eig K must exceed K\n");
+            exit(EXIT_FAILURE);
+        }
+    } else if (a->which_given || a->ncv_given) {
+        fprintf(stderr, "ERROR: %s is an option of the eigensolver: it needs the method -eig K\n", a->which_given ? "-which" : "-ncv M");
         exit(EXIT_FAILURE);
     }
     if (a->fill_given && a->preconditioner != PrecondType::ILU0 && a->preconditioner != PrecondType::ILU0Iter) {

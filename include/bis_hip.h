@@ -1573,6 +1573,123 @@ BIS_API bis_status bis_mat_row_norms(bis_ctx *ctx, const bis_mat *A, double *out
  * that gives A D columns of norm 1.  Non-blocking. */
 BIS_API bis_status bis_lsmr_scaling_from_norms(bis_ctx *ctx, const double *norms, int64_t n, double *d);
 
+/* ---- thick-restart Lanczos eigensolver on the device (no reference counterpart) ----
+ * The k extreme eigenpairs A x = lambda x of a symmetric matrix (symmetry is the
+ * caller's promise, as for bis_minres_*): the smallest (BIS_EIGS_SA), the largest
+ * (BIS_EIGS_LA) or the largest in magnitude (BIS_EIGS_LM), by thick-restart Lanczos (Wu
+ * and Simon, 2000) with full re-orthogonalisation, as a device schedule: nothing is read
+ * back inside bis_eigs_iterate.
+ * Parameters: k wanted pairs; m = ncv the basis size, 1 <= k < m <= min(n, 64) (64 is
+ * one wave: the restart runs in one); ncv = 0 asks for min(n, 64, max(2k + 1, 20));
+ * tol the convergence tolerance.  OP is A, or whatever the caller applies between
+ * bis_eigs_op_begin and bis_eigs_op_end (shift-and-invert: OP = (A - sigma I)^-1 by a
+ * bis_minres_* solve, lambda = sigma + 1 / theta).
+ * Storage: V_0 .. V_m, m + 1 basis blocks ld = n rounded up to even apart; the work
+ * vector W; the small state alpha (m), beta (m) and, after a restart, theta (l) and
+ * the coupling s (l).  Memory: (m + 2) n-vectors.
+ * Start: V_0 = v0 / ||v0||, v0 the caller's vector (bis_eigs_set_start) or column 0 of
+ * the hashed shadow space of bis_idr_*: v0[i] = (h + 0.5) 2^-31 - 1,
+ * h = hash32(hash32(i) ^ 0x9e3779b9).  l = 0.  A zero or non-finite ||v0|| stops the
+ * solve in bis_eigs_init, not converged, reason BAD_START.
+ * Step j (l <= j < m), one product each:
+ *     1. W = OP V_j
+ *     2. h = V_{0..j}^T W
+ *     3. W = W - V_{0..j} h        one fma per element and block, ascending block index
+ *     4. c = V_{0..j}^T W
+ *     5. W = W - V_{0..j} c        the same, with (W, W) in the same pass
+ *     6. alpha_j = h_j + c_j ;  beta_j = sqrt((W, W))
+ *     7. V_{j+1} = W / beta_j
+ * Two classical Gram-Schmidt passes always: there is no data-dependent second pass.
+ * Of h and c only alpha_j and beta_j are kept; the other entries are the known
+ * structure (s at j = l, beta_{j-1} otherwise) up to rounding.
+ * Breakdown: beta_j <= eps ||OP V_j||_2 (the norm is summed with the first group of
+ * line 2) is an invariant subspace: beta_j is set to 0 and no reciprocal is formed.
+ * The cycle closes with m_eff = j + 1 (the restart below on the leading m_eff rows and
+ * columns), every estimate is 0 and the solve stops, reason INVARIANT: converged when
+ * m_eff >= k, otherwise not converged with nconv = m_eff values.  The test is not
+ * beta_j == 0: in floating point the two passes leave rounding noise of the order
+ * eps^2 ||OP V_j|| of a beta_j that is 0 in exact arithmetic, its normalisation is a
+ * unit vector inside the subspace that is not orthogonal to the basis, and the Ritz
+ * values that follow are wrong (diag(1..6) from e_1 + e_2 returned -29 and -21 with
+ * estimates below 1e-10).  A beta_j that is not 0 in exact arithmetic and yet below
+ * eps ||OP V_j|| could not be told from that noise either.  With ncv = n the last
+ * step of the first cycle always ends this way.
+ * Restart, after step m - 1, in one wave:
+ *     1. T (m x m): diag(theta_0 .. theta_{l-1}); row and column l hold s; from (l, l)
+ *        on the tridiagonal of alpha_l .. alpha_{m-1} and beta_l .. beta_{m-2}.
+ *     2. T = Y diag(theta) Y^T by cyclic Jacobi: sweeps over (p, q), p < q, in row
+ *        order; tau = (t_qq - t_pp) / (2 t_pq); t = 1 / (tau + sign(tau) sqrt(1 + tau^2))
+ *        with sign(0) = +1; c = 1 / sqrt(1 + t^2); s = t c; t_pp -= t t_pq;
+ *        t_qq += t t_pq; rows and columns p, q of T and columns p, q of Y are rotated,
+ *        (x_p, x_q) <- (c x_p - s x_q, s x_p + c x_q), in Rutishauser's form
+ *        (x_p - s (x_q + rho x_p), x_q + s (x_p - rho x_q)), rho = s / (1 + c): the
+ *        rounding errors are those of a correction, not of a product (Y^T Y - I stays
+ *        at 5 eps where the plain form reaches 84 eps at m = 64); t_pq is set to 0
+ *        exactly.  An entry that is 0 already is skipped.  Before each sweep off(T), the root of the
+ *        sum of the squares of the off-diagonal entries themselves (never
+ *        ||T||_F^2 - sum t_ii^2), is tested: off(T) <= eps ||T||_F ends the sweeps.
+ *        30 sweeps without that stop the solve, not converged, reason JACOBI.
+ *     3. theta sorted ascending (stable), then ranked: SA as sorted, LA descending, LM
+ *        descending |theta| (stable on the sorted list).
+ *     4. est_i = |beta_{m-1} Y[m-1, i]| for the first k in rank order; pair i has
+ *        converged when est_i <= tol max(|theta_i|, eps^(2/3)) (ARPACK's test).
+ *     5. History entry `restart`: max_{i<k} est_i, and in the second column how many of
+ *        the k have converged.  All k: stop, converged (reason CONVERGED).
+ *     6. Otherwise keep l = min(k + (m - k) / 2, m - 1) pairs in rank order (a constant
+ *        of the handle): theta <- theta_keep, s_i = beta_{m-1} Y[m-1, keep_i], and
+ *        V_{0..l) <- V_{0..m) Y_keep, V_l <- V_m, in place (a lane reads its row of
+ *        all m blocks, then writes l blocks; one fma per block from 0, ascending).
+ * The same compression, with the first k (min(k, m_eff)) ranked columns, runs at a
+ * stop: after any restart the first basis blocks are the Ritz vectors in rank order,
+ * which is what bis_eigs_vectors copies.
+ * Single-vector Lanczos finds one vector per distinct eigenvalue: of a multiple
+ * eigenvalue it returns one copy, the others appear late or never (block Lanczos is
+ * not part of this handle).
+ * Schedule per step: the product; per group of at most 8 basis blocks one multi-dot
+ * launch (W read once per group); one update launch; the same again with (W, W) fused,
+ * whose last workgroup's lane 0 does line 6; the scaling; then the one-wave Ritz launch
+ * and the compression, which return at once unless the cycle closes or a breakdown was
+ * met.  Beside the product that is four reads of the j + 1 basis blocks and
+ * 2 ceil((j + 1) / 8) + 6 passes over W.  The vector passes walk 16 bytes per lane in
+ * grid-stride loops on the grids of the BLAS-1 layer with one lane for an odd last
+ * element (the compression: 8 bytes, a lane holds a row of up to 64 blocks).  No kernel
+ * waits for another workgroup; partial sums are added in index order: two runs give
+ * the same bits.  After a stop every launch returns at once.
+ * Errors: a null context: BIS_ERR_NO_DEVICE, the out-parameters are left alone.  n < 2,
+ * k < 1, ncv <= k, ncv > min(n, 64), a rectangular A, a null handle, bis_eigs_iterate on
+ * a handle without a matrix, bis_eigs_op_end without bis_eigs_op_begin (or two begins),
+ * bis_eigs_vectors before the first restart, bis_eigs_set_start after bis_eigs_init:
+ * BIS_ERR_INVALID with a message naming the call and the argument. */
+typedef struct bis_eigs bis_eigs;
+enum { BIS_EIGS_SA = 0, BIS_EIGS_LA = 1, BIS_EIGS_LM = 2 };
+/* the stop reasons of bis_eigs_status */
+enum { BIS_EIGS_LIVE = 0, BIS_EIGS_CONVERGED = 1, BIS_EIGS_INVARIANT = 2, BIS_EIGS_JACOBI = 3, BIS_EIGS_BAD_START = 4 };
+/* A: square, or NULL: the caller applies the operator (n is then the size; with A it must be A's); ncv = 0: the default */
+BIS_API bis_status bis_eigs_create(bis_ctx *ctx, const bis_mat *A, int64_t n, int k, int ncv, int which, bis_eigs **out);
+/* before bis_eigs_init; v0_dev: n entries on the device, read by bis_eigs_init (the caller keeps it alive); NULL: the default */
+BIS_API bis_status bis_eigs_set_start(bis_ctx *ctx, bis_eigs *h, const double *v0_dev);
+/* blocking.  It may be called again at any time: every earlier state (basis, scalars, counts, history, flags) is
+ * discarded and the solve that follows is, bit for bit, that of a new handle. */
+BIS_API bis_status bis_eigs_init(bis_ctx *ctx, bis_eigs *h, double tol);
+/* non-blocking: enqueues n_cycles whole cycles (the first has m products, later ones m - l); BIS_ERR_INVALID on a handle
+ * without a matrix.  It is a loop of bis_eigs_op_begin, bis_spmv, bis_eigs_op_end. */
+BIS_API bis_status bis_eigs_iterate(bis_ctx *ctx, bis_eigs *h, int n_cycles);
+/* One product of the caller's, on any handle: between the two calls the caller enqueues out = OP in on the context's
+ * stream (n entries each; in is a basis block, out the work vector).  bis_eigs_op_end enqueues the rest of the step, and
+ * the restart when the cycle closes.  Both non-blocking. */
+BIS_API bis_status bis_eigs_op_begin(bis_ctx *ctx, bis_eigs *h, const double **in_dev, double **out_dev);
+BIS_API bis_status bis_eigs_op_end(bis_ctx *ctx, bis_eigs *h);
+/* blocking; every pointer may be NULL.  values_host and est_host (k entries each): the Ritz values and residual estimates
+ * of the last restart in rank order; hist_host and hist_nconv_host: entries 0 .. restarts - 1 of the two history columns
+ * (at most hist_cap of each). */
+BIS_API bis_status bis_eigs_status(bis_ctx *ctx, bis_eigs *h, int *products, int *restarts, int *stopped, int *converged,
+                                   int *reason, int *nconv, double *values_host, double *est_host, double *hist_host,
+                                   double *hist_nconv_host, int hist_cap);
+/* X_dev[i + ldx c] = Ritz vector c (c < k) in rank order: the first k basis blocks.  Valid after at least one restart,
+ * refused before; at a live solve they are the kept vectors of the last restart. */
+BIS_API bis_status bis_eigs_vectors(bis_ctx *ctx, bis_eigs *h, double *X_dev, int64_t ldx);
+BIS_API bis_status bis_eigs_destroy(bis_ctx *ctx, bis_eigs *h);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
