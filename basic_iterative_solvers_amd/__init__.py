@@ -483,6 +483,9 @@ class Context:
     def eigs(self, A, k=4, which="SA", ncv=None, tol=1e-10, v0=None, n=None):
         return Eigs(self, A, k, which, ncv, tol, v0, n)
 
+    def svds(self, A, k=4, which="LM", ncv=None, tol=1e-10, v0=None, At=None, shape=None):
+        return SVDS(self, A, k, which, ncv, tol, v0, At, shape)
+
     # ---- measurement ---------------------------------------------------------
     def stat(self, kind, A, D, b, x, Ls=None, Us=None):
         return Stat(self, kind, A, D, b, x, Ls, Us)
@@ -1258,6 +1261,109 @@ class Eigs(_Solver):
             return X.to_host().reshape(self.k, self.n).T.copy()
         finally:
             X.free()
+
+    def solve(self, max_cycles=100, batch=4):
+        """init, then iterate in batches of `batch` cycles and poll until the solve stops or max_cycles are enqueued; status()."""
+        self.init()
+        done = 0
+        while done < max_cycles:
+            step = min(batch, max_cycles - done)
+            self.iterate(step)
+            done += step
+            st = self.status()
+            if st["stopped"]:
+                return st
+        return self.status()
+
+
+class SVDS(_Solver):
+    """Golub-Kahan-Lanczos bidiagonalisation with thick restart as a device schedule (bis_svds_*): the k largest ("LM") or
+    smallest ("SM") singular triplets of a rows x cols matrix of any shape.  `ncv` is the basis size, k < ncv <=
+    min(rows, cols, 64) (None: min(rows, cols, 64, max(2k + 1, 20))); `v0` a Vec of min(rows, cols) entries (None: column 0 of
+    IDR's hashed shadow space); `At` is A.transpose() (made and owned by the handle when None).  A=None with shape=(rows,
+    cols) is the caller-applied mode: `iterate` is refused, every product is the caller's, between `op_begin()` and
+    `op_end()` on the context's stream.  SM uses plain Ritz values: slow on ill-conditioned matrices.  No preconditioner."""
+
+    _sym = "svds"
+    WHICH = {"LM": 0, "SM": 1}
+    REASON = {0: "live", 1: "converged", 2: "invariant", 3: "jacobi", 4: "bad_start"}
+
+    def __init__(self, ctx, A, k=4, which="LM", ncv=None, tol=1e-10, v0=None, At=None, shape=None):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        if which not in self.WHICH:
+            raise BisError(f"SVDS: which must be one of LM, SM, not {which!r}")
+        if A is None and shape is None:
+            raise BisError("SVDS: the caller-applied mode (A=None) needs shape=(rows, cols)")
+        self.rows, self.cols = (int(A.n_rows), int(A.n_cols)) if A is not None else (int(shape[0]), int(shape[1]))
+        self.ns = min(self.rows, self.cols)
+        self.k, self.which, self.tol = int(k), which, float(tol)
+        self._keep = (A, At, v0)
+        ctx.check(ctx.lib.bis_svds_create(ctx.h, A.h if A is not None else C.c_void_p(), At.h if At is not None else C.c_void_p(),
+                                          _i64(self.rows), _i64(self.cols), C.c_int(self.k), C.c_int(0 if ncv is None else int(ncv)),
+                                          C.c_int(self.WHICH[which]), C.byref(self.h)))
+        self.ncv = int(ncv) if ncv is not None else min(self.ns, 64, max(2 * self.k + 1, 20))
+        if v0 is not None:
+            try:
+                self.set_start(v0)
+            except Exception:
+                self.free()
+                raise
+
+    def set_preconditioner(self, *args, **kwargs):
+        raise BisError("SVDS has no preconditioner (bis_svds_*)")
+
+    def set_start(self, v0):
+        """v0: a Vec of min(rows, cols) entries, or None for the default; before init."""
+        if v0 is not None and v0.n < self.ns:
+            raise BisError(f"SVDS: v0 has {v0.n} entries, the short side of the operator has {self.ns}")
+        self.ctx.check(self.ctx.lib.bis_svds_set_start(self.ctx.h, self.h, C.c_void_p(v0.ptr) if v0 is not None else C.c_void_p()))
+        self._keep = self._keep[:2] + (v0,)
+
+    def init(self, tol=None):
+        if tol is not None:
+            self.tol = float(tol)
+        self.ctx.check(self.ctx.lib.bis_svds_init(self.ctx.h, self.h, C.c_double(self.tol)))
+
+    def iterate(self, cycles=1):
+        self.ctx.check(self.ctx.lib.bis_svds_iterate(self.ctx.h, self.h, C.c_int(int(cycles))))
+
+    def op_begin(self):
+        """(inp, out, transposed): two Vec views; enqueue out = A inp (transposed False) or out = A^T inp (True) on the
+        context's stream, then call op_end()."""
+        inp, out, tr = C.c_void_p(), C.c_void_p(), C.c_int()
+        self.ctx.check(self.ctx.lib.bis_svds_op_begin(self.ctx.h, self.h, C.byref(inp), C.byref(out), C.byref(tr)))
+        n_in, n_out = (self.rows, self.cols) if tr.value else (self.cols, self.rows)
+        return Vec(self.ctx, inp.value, n_in, False), Vec(self.ctx, out.value, n_out, False), bool(tr.value)
+
+    def op_end(self):
+        self.ctx.check(self.ctx.lib.bis_svds_op_end(self.ctx.h, self.h))
+
+    def status(self, hist_cap=4096):
+        """dict(products, restarts, stopped, converged, reason, nconv, sigma_ref, values, est, hist, hist_nconv): values and
+        estimates of the last restart in rank order, the histories with one entry per restart."""
+        prod, rest, stop, conv, reason, nconv = (C.c_int() for _ in range(6))
+        sref = C.c_double()
+        values, est = np.zeros(self.k), np.zeros(self.k)
+        hist, hist_n = np.zeros(hist_cap), np.zeros(hist_cap)
+        self.ctx.check(self.ctx.lib.bis_svds_status(self.ctx.h, self.h, C.byref(prod), C.byref(rest), C.byref(stop), C.byref(conv),
+                                                    C.byref(reason), C.byref(nconv), C.byref(sref), values.ctypes, est.ctypes,
+                                                    hist.ctypes, hist_n.ctypes, C.c_int(hist_cap)))
+        cnt = min(rest.value, hist_cap)
+        return dict(products=prod.value, restarts=rest.value, stopped=bool(stop.value), converged=bool(conv.value),
+                    reason=reason.value, nconv=nconv.value, sigma_ref=sref.value, values=values, est=est, hist=hist[:cnt].copy(),
+                    hist_nconv=hist_n[:cnt].astype(np.int64))
+
+    def vectors(self):
+        """(U, V): the left (rows x k) and right (cols x k) singular vectors of the last restart in rank order, on the host."""
+        U, V = self.ctx.alloc(self.rows * self.k), self.ctx.alloc(self.cols * self.k)
+        try:
+            self.ctx.check(self.ctx.lib.bis_svds_vectors(self.ctx.h, self.h, C.c_void_p(U.ptr), _i64(self.rows), C.c_void_p(V.ptr),
+                                                         _i64(self.cols)))
+            return U.to_host().reshape(self.k, self.rows).T.copy(), V.to_host().reshape(self.k, self.cols).T.copy()
+        finally:
+            U.free()
+            V.free()
 
     def solve(self, max_cycles=100, batch=4):
         """init, then iterate in batches of `batch` cycles and poll until the solve stops or max_cycles are enqueued; status()."""

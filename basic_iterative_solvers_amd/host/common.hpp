@@ -84,7 +84,12 @@ inline int &idr_shadow_dim() { static int s = 4; return s; }
 inline int &eigs_k() { static int k = 0; return k; }
 inline int &eigs_which() { static int w = 0; return w; }
 inline int &eigs_ncv() { static int m = 0; return m; }
-enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR, LSMR, Eigs }; // FGMRES, MINRES, IDR, LSMR, Eigs: this build's additions (-fgm, -mr, -idr, -lsmr, -eig K)
+// -svd K [-which lm|sm] [-ncv M]: the wanted triplets, the end of the spectrum (BIS_SVDS_LM / _SM) and the basis size (0: the
+// handle's default, filled in once the handle is made) of bis_svds_create
+inline int &svds_k() { static int k = 0; return k; }
+inline int &svds_which() { static int w = 0; return w; }
+inline int &svds_ncv() { static int m = 0; return m; }
+enum class SolverType { Jacobi, GaussSeidel, SymmetricGaussSeidel, GMRES, ConjugateGradient, BiCGSTAB, FGMRES, MINRES, IDR, LSMR, Eigs, SVDS }; // FGMRES, MINRES, IDR, LSMR, Eigs, SVDS: this build's additions (-fgm, -mr, -idr, -lsmr, -eig K, -svd K)
 
 inline std::string to_string(PrecondType t) {
     static const char *n[] = {"none", "jacobi", "gauss-seidel", "backwards-gauss-seidel",
@@ -107,6 +112,10 @@ inline std::string to_string(SolverType t) {
         static const char *w[] = {"sa", "la", "lm"};
         return "lanczos(" + std::to_string(eigs_k()) + ", ncv=" + std::to_string(eigs_ncv()) + ", " + w[eigs_which()] + ")";
     }
+    if (t == SolverType::SVDS) {
+        static const char *w[] = {"lm", "sm"};
+        return "lanczos-svd(" + std::to_string(svds_k()) + ", ncv=" + std::to_string(svds_ncv()) + ", " + w[svds_which()] + ")";
+    }
     return n[static_cast<int>(t)];
 }
 
@@ -124,7 +133,7 @@ struct Args {
     bool damp_given = false;
     bool colscale = false;                 // -colscale: -lsmr runs on A D, d = 1 / the column norms of A (bis_lsmr_set_col_scaling)
     bool precond_given = false, perm_given = false; // -p, -perm appeared (refused with -lsmr and -eig)
-    bool which_given = false, ncv_given = false, scale_given = false; // -which, -ncv (options of -eig), -scale appeared
+    bool which_given = false, ncv_given = false, scale_given = false; // -which, -ncv (options of -eig and -svd), -scale appeared
     bool num_scale = false;
     bool unfused = false; // -unfused: CG / Jacobi / GS / SGS run the reference's kernel-by-kernel schedule (blocking reductions) instead of the device schedules
     bool host_scalars = false; // -hostscalars: GMRES / BiCGSTAB return every dot product to the host like the reference

@@ -1,6 +1,6 @@
 // main.cpp -- CLI driver of the MI355X build; same command line and the same
 // stdout (residual table, summary, timer tree) as the reference's main.cpp.
-//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-idr [-ids S]|-bi|-lsmr [-damp L] [-colscale]|-eig K [-which sa|la|lm] [-ncv M]>
+//   ./basic_iterative_solvers <matrix.mtx | generator> <-j|-gs|-sgs|-cg|-gm|-fgm|-mr|-idr [-ids S]|-bi|-lsmr [-damp L] [-colscale]|-eig K [-which sa|la|lm] [-ncv M]|-svd K [-which lm|sm] [-ncv M]>
 //        [-p j|gs|bgs|sgs|2st|s2st|ilu0|ilu0it|fsai|mg|bj] [-mg KEY=VALUE,... (nu, cs, limit, levels, scale, omega, coarsening, cycle=v|w|k|kgcr, klev, smooth=0|1, pomega, smoother=jacobi|cheb, degree, ratio, est, safety)] [-bs N] [-fill K (level-of-fill of ilu0 / ilu0it, 0..16)] [-inner K] [-pprec 32|64] [-scale 0|1] [-rl N] [-unfused] [-dev K]
 #include <chrono>
 
@@ -15,6 +15,7 @@
 #include "methods/jacobi.hpp"
 #include "methods/lsmr.hpp"
 #include "methods/minres.hpp"
+#include "methods/svds.hpp"
 #include "postprocessing.hpp"
 #include "preprocessing.hpp"
 #include "solver_harness.hpp"
@@ -36,6 +37,7 @@ static void run(Args *cli_args, Timers *timers) {
     case SolverType::IDR: solver = new IDRSolver(cli_args); break;
     case SolverType::LSMR: solver = new LSMRSolver(cli_args); break;
     case SolverType::Eigs: solver = new EigsSolver(cli_args); break;
+    case SolverType::SVDS: solver = new SVDSSolver(cli_args); break;
     }
     auto A = std::make_unique<MatrixCRS>();
     if (!make_generated_matrix(cli_args->matrix_file_name, A.get())) {
@@ -52,7 +54,7 @@ static void run(Args *cli_args, Timers *timers) {
             MatrixCOO mtx;
             t0 = now();
             try {
-                mtx.read_from_mtx(cli_args->matrix_file_name, cli_args->method == SolverType::LSMR);
+                mtx.read_from_mtx(cli_args->matrix_file_name, cli_args->method == SolverType::LSMR || cli_args->method == SolverType::SVDS);
             } catch (const std::exception &e) {
                 fprintf(stderr, "ERROR: %s\n", e.what());
                 exit(EXIT_FAILURE);

@@ -298,9 +298,9 @@ inline void preprocessing(Args *cli_args, Solver *solver, Timers *timers, std::u
     solver->L_strict = std::make_unique<MatrixCRS>();
     solver->U = std::make_unique<MatrixCRS>();
     solver->U_strict = std::make_unique<MatrixCRS>();
-    // -lsmr: A may be rectangular and has no triangles or diagonal to split off (the method takes no preconditioner); -eig K
-    // takes none either
-    if (solver->method != SolverType::LSMR && solver->method != SolverType::Eigs) TIME(timers, "preprocessing_factor", factor_LU(solver))
+    // -lsmr, -svd K: A may be rectangular and has no triangles or diagonal to split off (the methods take no preconditioner);
+    // -eig K takes none either
+    if (solver->method != SolverType::LSMR && solver->method != SolverType::Eigs && solver->method != SolverType::SVDS) TIME(timers, "preprocessing_factor", factor_LU(solver))
 
     (*timers)["preprocessing_init"].start();
     solver->init_residual();

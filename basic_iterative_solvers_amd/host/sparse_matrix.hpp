@@ -81,7 +81,7 @@ struct MatrixCOO {
     std::vector<int> I, J;
     std::vector<double> values;
 
-    // allow_rect: a matrix with M != N is read as it is (the method -lsmr); every other caller keeps the reference's refusal
+    // allow_rect: a matrix with M != N is read as it is (the methods -lsmr and -svd K); every other caller keeps the reference's refusal
     void read_from_mtx(const std::string &path, bool allow_rect = false) {
         FILE *f = fopen(path.c_str(), "rb");
         if (!f) throw std::runtime_error("Unable to open file: " + path);

@@ -17,7 +17,9 @@
 // the method `-lsmr` is LSMR for least-squares problems on the device schedule bis_lsmr_* (methods/lsmr.hpp), the one method that
 // takes a rectangular .mtx; `-damp L` is its Tikhonov parameter and `-colscale` scales the columns of A to norm 1;
 // the method `-eig K` is the thick-restart Lanczos eigensolver on the device schedule bis_eigs_* (methods/eigs.hpp): the K smallest
-// (`-which sa`, the default), largest (`la`) or largest in magnitude (`lm`) eigenpairs of a symmetric matrix with a basis of `-ncv M`.
+// (`-which sa`, the default), largest (`la`) or largest in magnitude (`lm`) eigenpairs of a symmetric matrix with a basis of `-ncv M`;
+// the method `-svd K` is thick-restart Lanczos bidiagonalisation on the device schedule bis_svds_* (methods/svds.hpp): the K largest
+// (`-which lm`, the default) or smallest (`sm`) singular triplets of a matrix of any shape (a rectangular .mtx is read as for -lsmr).
 #pragma once
 
 #include <sys/stat.h>
@@ -53,6 +55,16 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         }
         eigs_k() = (int)kk;
     }
+    else if (st == "-svd") {
+        a->method = SolverType::SVDS;
+        char *end = nullptr;
+        const long kk = argc > 3 ? strtol(argv[3], &end, 10) : 0;
+        if (argc <= 3 || end == argv[3] || *end != '\0' || kk < 1 || kk > 63) {
+            fprintf(stderr, "ERROR: -svd K: the number of wanted singular triplets, 1 <= K <= 63\n");
+            exit(EXIT_FAILURE);
+        }
+        svds_k() = (int)kk;
+    }
     else {
         printf("ERROR: parse_cli: Please choose an available solver:"
                "\n-j (Jacobi)\n-gs (Gauss-Seidel)\n-sgs (Symmetric Gauss-Seidel)"
@@ -62,10 +74,11 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
                "\n-mr ([Preconditioned] MINRES, symmetric indefinite matrices)"
                "\n-idr ([Preconditioned] IDR(s), nonsymmetric matrices, -ids S = 1..8)"
                "\n-lsmr (LSMR, least-squares problems with rectangular matrices, -damp L >= 0, -colscale)"
-               "\n-eig K (thick-restart Lanczos, the K extreme eigenpairs of a symmetric matrix, -which sa|la|lm, -ncv M)\n");
+               "\n-eig K (thick-restart Lanczos, the K extreme eigenpairs of a symmetric matrix, -which sa|la|lm, -ncv M)"
+               "\n-svd K (thick-restart Lanczos bidiagonalisation, the K largest or smallest singular triplets of a matrix of any shape, -which lm|sm, -ncv M)\n");
         exit(EXIT_FAILURE);
     }
-    for (int i = a->method == SolverType::Eigs ? 4 : 3; i < argc; ++i) { // (-eig K: argv[3] is K)
+    for (int i = a->method == SolverType::Eigs || a->method == SolverType::SVDS ? 4 : 3; i < argc; ++i) { // (-eig K, -svd K: argv[3] is K)
         const std::string arg = argv[i];
         if (arg == "-p") {
             if (i + 1 >= argc) {
@@ -154,21 +167,28 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         else if (arg == "-colscale") a->colscale = true;
         else if (arg == "-which" && i + 1 < argc) {
             const std::string w = argv[++i];
-            if (w != "sa" && w != "la" && w != "lm") {
+            if (a->method == SolverType::SVDS) {
+                if (w != "lm" && w != "sm") {
+                    fprintf(stderr, "ERROR: -which lm|sm: the end of the spectrum -svd K looks for (largest, smallest)\n");
+                    exit(EXIT_FAILURE);
+                }
+                svds_which() = w == "lm" ? BIS_SVDS_LM : BIS_SVDS_SM;
+            } else if (w != "sa" && w != "la" && w != "lm") {
                 fprintf(stderr, "ERROR: -which sa|la|lm: the end of the spectrum -eig K looks for (smallest, largest, largest in magnitude)\n");
                 exit(EXIT_FAILURE);
             }
-            eigs_which() = w == "sa" ? BIS_EIGS_SA : w == "la" ? BIS_EIGS_LA : BIS_EIGS_LM;
+            if (a->method != SolverType::SVDS) eigs_which() = w == "sa" ? BIS_EIGS_SA : w == "la" ? BIS_EIGS_LA : BIS_EIGS_LM;
             a->which_given = true;
         }
         else if (arg == "-ncv" && i + 1 < argc) {
             char *end = nullptr;
             const long m = strtol(argv[++i], &end, 10);
             if (end == argv[i] || *end != '\0' || m < 2 || m > 64) {
-                fprintf(stderr, "ERROR: -ncv M: the basis size of -eig K, K < M <= min(n, 64)\n");
+                if (a->method == SolverType::SVDS) fprintf(stderr, "ERROR: -ncv M: the basis size of -svd K, K < M <= min(rows, cols, 64)\n");
+                else fprintf(stderr, "ERROR: -ncv M: the basis size of -eig K, K < M <= min(n, 64)\n");
                 exit(EXIT_FAILURE);
             }
-            eigs_ncv() = (int)m;
+            (a->method == SolverType::SVDS ? svds_ncv() : eigs_ncv()) = (int)m;
             a->ncv_given = true;
         }
         else if (arg == "-mg" && i + 1 < argc) {
@@ -306,6 +326,20 @@ inline void parse_cli(Args *a, int argc, char *argv[]) {
         }
         if (a->ncv_given && eigs_ncv() <= eigs_k()) {
             fprintf(stderr, "ERROR: -ncv M: the basis size of -eig K must exceed K\n");
+            exit(EXIT_FAILURE);
+        }
+    } else if (a->method == SolverType::SVDS) {
+        // singular triplets have no right-hand side to precondition, the permutation and the scaling would change the vectors,
+        // and the handle is the only form
+        const char *flag = a->precond_given ? "-p" : a->perm_given ? "-perm" : a->scale_given ? "-scale" : a->unfused ? "-unfused"
+                           : a->host_scalars ? "-hostscalars" : nullptr;
+        if (flag) {
+            fprintf(stderr, "ERROR: %s does not apply to -svd K (thick-restart Lanczos bidiagonalisation on the device schedule bis_svds_*: no "
+                            "preconditioner, permutation, scaling or call-by-call form; use -which lm|sm and -ncv M)\n", flag);
+            exit(EXIT_FAILURE);
+        }
+        if (a->ncv_given && svds_ncv() <= svds_k()) {
+            fprintf(stderr, "ERROR: -ncv M: the basis size of -svd K must exceed K\n");
             exit(EXIT_FAILURE);
         }
     } else if (a->which_given || a->ncv_given) {

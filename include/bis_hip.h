@@ -1690,6 +1690,158 @@ BIS_API bis_status bis_eigs_status(bis_ctx *ctx, bis_eigs *h, int *products, int
 BIS_API bis_status bis_eigs_vectors(bis_ctx *ctx, bis_eigs *h, double *X_dev, int64_t ldx);
 BIS_API bis_status bis_eigs_destroy(bis_ctx *ctx, bis_eigs *h);
 
+/* ---- thick-restart Lanczos bidiagonalisation for singular triplets (no reference counterpart) ----
+ * The k largest (BIS_SVDS_LM) or smallest (BIS_SVDS_SM) singular triplets
+ * A v = sigma u, A^T u = sigma v of a rows x cols matrix of any shape, by Golub-Kahan-
+ * Lanczos bidiagonalisation with thick restart (Baglama and Reichel 2005; Hernandez,
+ * Roman and Tomas 2008) and full re-orthogonalisation of both bases, as a device
+ * schedule: nothing is read back inside bis_svds_iterate.  It works on A and A^T
+ * directly: A^T A is never formed (it would lose every sigma below sqrt(eps) sigma_max),
+ * nor the augmented matrix (twice the vectors, every sigma twice).
+ * Orientation: ns = min(rows, cols), nl = max(rows, cols).  The handle bidiagonalises
+ * the tall orientation: F = A, F^T = A^T when rows >= cols, F = A^T, F^T = A otherwise,
+ * so the start vector and the basis P live in the ns-dimensional space, where a
+ * generic vector has no null-space component.  Of a triplet (sigma, q, p) of F, with q
+ * of nl and p of ns entries, the caller gets u = q, v = p when rows >= cols and u = p,
+ * v = q otherwise.  A^T is a bis_mat the caller passes (as bis_mat_transpose makes it)
+ * or one the handle makes and owns; both products go through the SpMV launcher.
+ * Parameters: k wanted triplets; m = ncv, 1 <= k < m <= min(ns, 64) (64 is one wave);
+ * ncv = 0 asks for min(ns, 64, max(2k + 1, 20)); tol; ns >= 2.
+ * Storage: P_0 .. P_m of ns entries and Q_0 .. Q_{m-1} of nl entries, each basis with
+ * its own leading dimension (the length rounded up to even).  A product writes into
+ * its destination block, which is orthogonalised and scaled in place: there is no
+ * work vector.  Memory: (m + 1) ns + m nl doubles.  The small state: alpha (m), beta
+ * (m), after a restart sigma (l) and the coupling s (l), and sigma_ref.
+ * Start: P_0 = v0 / ||v0||, v0 the caller's vector of ns entries (bis_svds_set_start)
+ * or column 0 of the hashed shadow space of bis_idr_* (the default of bis_eigs_*).
+ * l = 0, sigma_ref = 0.  A zero or non-finite ||v0|| stops the solve in bis_svds_init,
+ * not converged, reason BAD_START.
+ * Step j (l <= j < m), two products:
+ *   left half
+ *     1. Q_j = F P_j
+ *     2. twice, when j > 0:  h = Q_{0..j-1}^T Q_j;  Q_j = Q_j - Q_{0..j-1} h
+ *     3. alpha_j = ||Q_j||_2 (summed in the second update's pass; with j = 0 in a pass
+ *        of its own);  Q_j = Q_j / alpha_j
+ *   right half
+ *     4. P_{j+1} = F^T Q_j
+ *     5. twice:  h = P_{0..j}^T P_{j+1};  P_{j+1} = P_{j+1} - P_{0..j} h
+ *     6. beta_j = ||P_{j+1}||_2;  P_{j+1} = P_{j+1} / beta_j
+ * Two classical Gram-Schmidt passes always, no data-dependent branch; one fma per
+ * element and block in ascending block index.  The coefficients h are discarded: the
+ * entries of B = Q^T F P are the two norms and the known structure (s in column l,
+ * beta above the diagonal).
+ * Breakdown.  beta_j <= eps ||F^T Q_j||_2 (the norm before the passes, summed with
+ * the first group of dots): span(P_0..P_j) is an invariant subspace of F^T F;
+ * beta_j is set to 0 and no reciprocal is formed; the cycle closes with m_eff = j + 1,
+ * every estimate is 0 and the solve stops, reason INVARIANT: converged when m_eff >= k,
+ * otherwise not converged with nconv = m_eff values.  With ncv = ns the first cycle
+ * always ends this way.  alpha_j <= eps ||F P_j||_2: F maps span(P_0..P_j) into
+ * span(Q_0..Q_{j-1}); alpha_j and beta_j are set to 0, Q_j counts as 0, m_eff = j + 1,
+ * estimates 0, reason INVARIANT.  The singular value 0 that this exposes has a zero
+ * vector on the long side (u when rows >= cols, v otherwise): only its short-side
+ * vector, a null vector of F, means anything.  The test is "<= eps times the norm before
+ * the passes", not "== 0", for the reason given with bis_eigs_*.
+ * Restart, after step m - 1 or at a breakdown, in one wave:
+ *     1. B (m_eff x m_eff): rows i < l hold sigma_i on the diagonal and s_i in column
+ *        l; from (l, l) on alpha_i on the diagonal and beta_i at (i, i + 1).
+ *     2. B = X Sigma Y^T by one-sided (Hestenes) Jacobi: G = B, Y = I; a rotation of
+ *        the columns p < q of G and of Y makes g_p^T g_q = 0:
+ *        a = g_p^T g_p, b = g_q^T g_q, c = g_p^T g_q, each summed in row order from 0,
+ *        every operation rounded separately; the pair is skipped when c = 0, when
+ *        |c| <= sqrt(m_eff) eps sqrt(a) sqrt(b), or when sqrt(a) or sqrt(b) is at most
+ *        eps ||B||_F (||B||_F^2: the column sums in row order, added in column order):
+ *        such a column is the rounding noise of a zero singular value, every rotation
+ *        renews the noise, and a singular B (an alpha breakdown leaves its last row 0)
+ *        would rotate for ever.  Otherwise zeta = (b - a) / (2 c),
+ *        t = 1 / (zeta + sqrt(1 + zeta^2)) for zeta >= 0 and 1 / (zeta - sqrt(1 + zeta^2))
+ *        otherwise, cs = 1 / sqrt(1 + t^2), sn = t cs,
+ *        (x_p, x_q) <- (cs x_p - sn x_q, sn x_p + cs x_q).
+ *        Order of the pairs: round-robin.  With n2 = m_eff rounded up to even, a sweep is
+ *        n2 - 1 rounds r = 0 .. n2 - 2 of n2 / 2 disjoint pairs, one lane per pair:
+ *        lane 0 holds {n2 - 1, r}, lane i > 0 holds {(r + i) mod (n2 - 1),
+ *        (r - i) mod (n2 - 1)}; p is the smaller index; a pair with an index >= m_eff
+ *        (the bye of an odd m_eff) does nothing.  A sweep without a rotation ends the
+ *        iteration; 30 sweeps that all rotated stop the solve, not converged, reason
+ *        JACOBI.  (With a threshold of eps alone a 30-sweep limit was met; with
+ *        sqrt(m_eff) eps the restatement needs at most 11.)  Then
+ *        sigma_i = ||g_i||_2, set to 0 when it is at most eps ||B||_F, and
+ *        x_i = g_i / sigma_i; a zero column gives a zero x_i.
+ *     3. sigma sorted ascending (stable), then ranked: SM as sorted, LM descending
+ *        (stable on the sorted list).
+ *     4. sigma_ref = the largest sigma of any restart so far, this one included: an
+ *        estimate of ||A||_2 that SM, which discards the large values, keeps.
+ *     5. est_i = |beta_{m_eff-1} X[m_eff-1, i]| for the first k in rank order; triplet
+ *        i has converged when est_i <= tol sigma_ref: the backward error relative to
+ *        ||A||_2 (a test relative to sigma_i cannot be met for small sigma_i).
+ *     6. History entry `restart`: max_{i<k} est_i, and in the second column how many of
+ *        the k have converged.  All k: stop, converged (reason CONVERGED).
+ *     7. Otherwise keep l = min(k + (m - k) / 2, m - 1) triplets in rank order (a
+ *        constant of the handle): sigma <- sigma_keep, s_i = beta_{m-1} X[m-1, keep_i],
+ *        P_{0..l) <- P_{0..m) Y_keep, P_l <- P_m, Q_{0..l) <- Q_{0..m) X_keep, each
+ *        basis once, in place, row by row (a lane reads its row of all m blocks, then
+ *        writes l; one fma per block from 0, ascending).  The next cycle starts at
+ *        j = l: F P_l is orthogonalised against the kept Q, which is where the s_i live.
+ *     8. The same compression with the first min(k, m_eff) ranked columns runs at a
+ *        stop: after any restart the leading blocks are the singular vectors in rank
+ *        order, which is what bis_svds_vectors copies.
+ * Products: 2m in the first cycle, 2(m - l) in later ones.
+ * Schedule per half step: the product; per group of at most 8 basis blocks one
+ * multi-dot launch (the new vector read once per group); one update launch; the same
+ * again with the norm fused, whose last workgroup's lane 0 forms alpha_j or beta_j,
+ * the product count and the breakdown test; the in-place scaling; then the one-wave
+ * launch and the two compressions, which return at once unless the cycle closes or a
+ * breakdown was met.  The vector passes walk 16 bytes per lane in grid-stride loops on
+ * the grids of the BLAS-1 layer with one lane for an odd last element (the compression:
+ * 8 bytes, a lane holds a row of up to 64 blocks).  Scalars, B's entries, histories and
+ * flags stay on the device.  No kernel waits for another workgroup; partial sums are
+ * added in index order: two runs give the same bits.  After a stop every launch returns
+ * at once.
+ * Limitation: SM uses plain, not harmonic, Ritz values.  It converges on
+ * well-conditioned matrices and is slow on ill-conditioned ones (on a 1301 x 700 matrix
+ * of condition 1.3e4 the restatement did not converge in 2000 restarts for SM, where
+ * LM took 2); a harmonic restart is not part of this handle.  Of a multiple singular
+ * value one copy is found, as with bis_eigs_*.
+ * Errors: a null context: BIS_ERR_NO_DEVICE, the out-parameters are left alone.
+ * k < 1, ncv <= k, ncv > min(ns, 64), ns < 2, an At whose shape is not that of A^T, a
+ * null handle, bis_svds_iterate on a handle without a matrix, bis_svds_op_end without
+ * bis_svds_op_begin (or two begins), bis_svds_vectors before the first restart,
+ * bis_svds_set_start after bis_svds_init: BIS_ERR_INVALID with a message naming the
+ * call and the argument. */
+typedef struct bis_svds bis_svds;
+enum { BIS_SVDS_LM = 0, BIS_SVDS_SM = 1 };
+/* the stop reasons of bis_svds_status */
+enum { BIS_SVDS_LIVE = 0, BIS_SVDS_CONVERGED = 1, BIS_SVDS_INVARIANT = 2, BIS_SVDS_JACOBI = 3, BIS_SVDS_BAD_START = 4 };
+/* A: rows x cols, or NULL: the caller applies both products (rows and cols are then the shape; with A they must be A's).
+ * At: A^T, or NULL: the handle makes it with bis_mat_transpose and owns it.  ncv = 0: the default */
+BIS_API bis_status bis_svds_create(bis_ctx *ctx, const bis_mat *A, const bis_mat *At, int64_t rows, int64_t cols, int k, int ncv,
+                                   int which, bis_svds **out);
+/* before bis_svds_init; v0_dev: min(rows, cols) entries on the device, read by bis_svds_init (the caller keeps it alive);
+ * NULL: the default */
+BIS_API bis_status bis_svds_set_start(bis_ctx *ctx, bis_svds *h, const double *v0_dev);
+/* blocking.  It may be called again at any time: every earlier state (bases, scalars, sigma_ref, counts, history, flags)
+ * is discarded and the solve that follows is, bit for bit, that of a new handle. */
+BIS_API bis_status bis_svds_init(bis_ctx *ctx, bis_svds *h, double tol);
+/* non-blocking: enqueues n_cycles whole cycles; BIS_ERR_INVALID on a handle without a matrix.  It is a loop of
+ * bis_svds_op_begin, bis_spmv (with A or At as *transposed says), bis_svds_op_end. */
+BIS_API bis_status bis_svds_iterate(bis_ctx *ctx, bis_svds *h, int n_cycles);
+/* One product of the caller's, on any handle: between the two calls the caller enqueues out = A in (*transposed = 0: in has
+ * cols entries, out rows) or out = A^T in (*transposed = 1: in has rows entries, out cols) on the context's stream, in terms
+ * of the caller's A, not of F.  in and out are basis blocks.  bis_svds_op_end enqueues the rest of the half step, and the
+ * restart when the cycle closes.  Both non-blocking. */
+BIS_API bis_status bis_svds_op_begin(bis_ctx *ctx, bis_svds *h, const double **in_dev, double **out_dev, int *transposed);
+BIS_API bis_status bis_svds_op_end(bis_ctx *ctx, bis_svds *h);
+/* blocking; every pointer may be NULL.  values_host and est_host (k entries each): the singular values and residual
+ * estimates of the last restart in rank order; hist_host and hist_nconv_host: entries 0 .. restarts - 1 of the two history
+ * columns (at most hist_cap of each). */
+BIS_API bis_status bis_svds_status(bis_ctx *ctx, bis_svds *h, int *products, int *restarts, int *stopped, int *converged,
+                                   int *reason, int *nconv, double *sigma_ref, double *values_host, double *est_host,
+                                   double *hist_host, double *hist_nconv_host, int hist_cap);
+/* U_dev[i + ldu c] = left vector c (rows entries), V_dev[i + ldv c] = right vector c (cols entries), c < k in rank order:
+ * the leading blocks of the two bases.  Either pointer may be NULL.  Valid after at least one restart, refused before; at
+ * a live solve they are the kept vectors of the last restart. */
+BIS_API bis_status bis_svds_vectors(bis_ctx *ctx, bis_svds *h, double *U_dev, int64_t ldu, double *V_dev, int64_t ldv);
+BIS_API bis_status bis_svds_destroy(bis_ctx *ctx, bis_svds *h);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* HIP-event timing of the kernels launched on the context's stream.  While
  * enabled, each bis_spmv launch (and the SpMV inside bis_cg_iterate) is
