@@ -12,8 +12,10 @@ pytestmark = pytest.mark.gpu
 KTOL = 1e-13  # kernel-level relative tolerance (tests/test_gpu_kernels.py)
 MATS = ["hpcg_4x6x5", "FDM-2d-16", "fem444"]
 KS = (2, 5, 8)
-# (type, inner): the types the dispatcher serves
-TYPES = [("none", 0), ("j", 0), ("gs", 0), ("bgs", 0), ("sgs", 0), ("ilu0", 0), ("ilu0it", 0), ("ilu0it", 1), ("ilu0it", 3)]
+# (type, inner): the types the dispatcher serves; for "bj" the second entry is the block size (5: no power of two)
+TYPES = [("none", 0), ("j", 0), ("gs", 0), ("bgs", 0), ("sgs", 0), ("ilu0", 0), ("ilu0it", 0), ("ilu0it", 1), ("ilu0it", 3),
+         ("fsai", 0), ("bj", 4), ("bj", 5)]
+NO_ORACLE = ("ilu0it", "fsai", "bj")  # the types the oracle does not have
 
 
 @pytest.fixture(scope="module")
@@ -46,14 +48,21 @@ def setups(ctx):
         iUinv = ctx.alloc(n)
         ctx.elemwise_div_vectors(iUinv, iLD, iUD)
         ones = ctx.upload(np.ones(n))
+        G, Gt, _ = ctx.fsai(dA)
+        bj = {bs: ctx.bjacobi(dA, block_size=bs) for bs in (4, 5)}
         out[name] = dict(n=n, dA=dA, Ls=Ls, Us=Us, D=D, Dinv=Dinv, iLs=iLs, iLD=iLD, iUs=iUs, iUD=iUD, iUinv=iUinv, ones=ones,
+                         G=G, Gt=Gt, bj=bj,
                          h=dict(Ls=host(Ls), Us=host(Us), D=D.to_host(), Dinv=Dinv.to_host(), iLs=host(iLs), iUs=host(iUs),
                                 iLD=iLD.to_host(), iUD=iUD.to_host()))
     return out
 
 
-def operands(s, pc):
+def operands(s, pc, block_size=0):
     """(Ls, Us, A_D, A_D_inv, L_D, U_D) as bis_apply_preconditioner takes them for this type"""
+    if pc == "fsai":  # G and Gt; the diagonal arguments are not read
+        return s["G"], s["Gt"], None, None, None, None
+    if pc == "bj":  # the handle's operand; nothing else is read
+        return s["bj"][block_size].operand, None, None, None, None, None
     if pc == "ilu0":
         return s["iLs"], s["iUs"], s["D"], s["Dinv"], s["iLD"], s["iUD"]
     if pc == "ilu0it":
@@ -74,7 +83,10 @@ def block(n, k, seed):
 def test_columns_equal_the_single_vector_apply(ctx, setups, name, pc, inner):
     s = setups[name]
     n = s["n"]
-    ops = operands(s, pc)
+    ops = operands(s, pc, inner)
+    if pc == "bj":
+        assert s["bj"][inner].max_block == inner
+        inner = 0
     orc = Oracle()
     h = s["h"]
     for k in KS:
@@ -94,12 +106,18 @@ def test_columns_equal_the_single_vector_apply(ctx, setups, name, pc, inner):
         assert same_bits(IN.to_host().reshape(n, k), V), "IN was written"
         ctx.mapply_preconditioner(pc, n, k, *ops, IN, IN, TMP, WORK, inner=inner)  # OUT aliasing IN
         got_alias = IN.to_host().reshape(n, k)
+        if pc == "fsai":  # TMP holds G IN between the two bis_spmm: it must be distinct from OUT and from IN
+            from basic_iterative_solvers_amd import BisError
+            for out_, in_, tmp_ in ((OUT, IN, OUT), (OUT, IN, IN), (IN, IN, IN)):
+                with pytest.raises(BisError, match="status 2"):
+                    ctx.mapply_preconditioner(pc, n, k, *ops, out_, in_, tmp_, WORK, inner=inner)
+            assert same_bits(IN.to_host().reshape(n, k), got_alias), "a refused call wrote"
         for v in (IN, OUT, TMP, WORK):
             v.free()
         for j in range(k):
             assert same_bits(got[:, j], ref[:, j]), (name, pc, inner, k, j, int(np.sum(got[:, j] != ref[:, j])))
             assert same_bits(got_alias[:, j], ref[:, j]), (name, pc, inner, k, j, "in place")
-        if pc != "ilu0it":  # the oracle has every other type
+        if pc not in NO_ORACLE:  # the oracle has every other type
             hops = ((h["iLs"], h["iUs"], h["D"], h["Dinv"], h["iLD"], h["iUD"]) if pc == "ilu0" else
                     (h["Ls"], h["Us"], h["D"], h["Dinv"], None, None))
             for j in range(k):
