@@ -57,18 +57,12 @@ constexpr unsigned kCounterSet = bis_counter_set_words(kMaxReduceBlocks); // eve
 // state: scalars, then c, alpha, f (kMaxS each) and the lower triangle M, row i at S_M + kMaxS i
 enum { S_OMEGA = 0, S_NORM /* || r || */, S_STOP, S_BETA, S_C = 8, S_ALPHA = 16, S_F = 24, S_M = 32, S_COUNT = 96 };
 
-// the header's hash32 (the MIS key's)
-__host__ __device__ __forceinline__ uint32_t idr_hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
 // P[i][j] = (h + 0.5) 2^-31 - 1, h = hash32(hash32(i) ^ (j + 1) 0x9e3779b9): exact in fp64.  The padding row of an odd n is 0.
 __global__ __launch_bounds__(kT) void idr_shadow_kernel(double *P, int64_t n, int64_t ld, int s) {
     const int64_t total = ld * s;
     for (int64_t idx = (int64_t)blockIdx.x * kT + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kT) {
         const int64_t i = idx % ld, j = idx / ld;
-        const uint32_t h = idr_hash32(idr_hash32((uint32_t)i) ^ ((uint32_t)(j + 1) * 0x9e3779b9u));
+        const uint32_t h = bis_hash32(bis_hash32((uint32_t)i) ^ ((uint32_t)(j + 1) * 0x9e3779b9u));
         P[idx] = i < n ? ((double)h + 0.5) * 0x1p-31 - 1.0 : 0.0;
     }
 }

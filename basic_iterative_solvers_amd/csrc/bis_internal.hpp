@@ -262,6 +262,13 @@ inline hipError_t bis_slot_io(bis_ctx *ctx, int slot, int n, int *host = nullptr
 // operands that a kernel loads 16 bytes per lane
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the header's hash32: two multiply-xorshift rounds.  The MIS key and the power iteration's start (bis_mg.hip), IDR's shadow
+// space (bis_idr.hip), the start vector of the Lanczos handles (bis_lanczos.hpp)
+__host__ __device__ __forceinline__ uint32_t bis_hash32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
 // `count` device words, zeroed on the stream: a handle's flags and arrival counters
 template <class T>
 inline bis_status bis_alloc_zeroed(bis_ctx *ctx, T **out, size_t count) {

@@ -275,7 +275,6 @@ __global__ __launch_bounds__(kT) void scaling_kernel(int64_t n, const double *no
     for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < n; i += gs) d[i] = norms[i] == 0.0 ? 1.0 : 1.0 / norms[i];
 }
 
-inline int lane_grid(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + kT - 1) / kT, 1), kMaxEwBlocks); }
 inline bool lsmr_empty(const bis_lsmr *s) { return s->m == 0 || s->n == 0; }
 
 } // namespace

@@ -433,16 +433,8 @@ bis_status launch_kdots(bis_ctx *ctx, const bis_mg *mg, const double *p, const d
 }
 
 // ---- setup kernels -----------------------------------------------------------------------------------------------------
-// 32-bit mixing hash of the MIS key (include/bis_hip.h): two multiply-xorshift rounds
-__host__ __device__ __forceinline__ uint32_t mg_hash32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ unsigned long long mg_key(int32_t i) { return ((unsigned long long)mg_hash32((uint32_t)i) << 32) | (uint32_t)i; }
+// the MIS key (include/bis_hip.h): (hash32(i), i)
+__device__ __forceinline__ unsigned long long mg_key(int32_t i) { return ((unsigned long long)bis_hash32((uint32_t)i) << 32) | (uint32_t)i; }
 
 enum { MG_AUX_BAD_DIAG, MG_AUX_UNDECIDED, MG_AUX_COUNT };
 
@@ -1151,7 +1143,7 @@ __global__ __launch_bounds__(kMgT) void mg_max_kernel(const double *__restrict__
 // the power iteration's start: v_i = hash32(i) / 2^32 - 0.5 (exact)
 __global__ __launch_bounds__(kMgT) void mg_hash_vector_kernel(double *v, int64_t n) {
     const int64_t stride = (int64_t)gridDim.x * kMgT;
-    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) v[i] = (double)mg_hash32((uint32_t)i) * 0x1p-32 - 0.5;
+    for (int64_t i = (int64_t)blockIdx.x * kMgT + threadIdx.x; i < n; i += stride) v[i] = (double)bis_hash32((uint32_t)i) * 0x1p-32 - 0.5;
 }
 #define MG_SM_CHECK(call)                                                                                              \
     do {                                                                                                               \

@@ -1,5 +1,5 @@
 // bis_solver.hpp -- what the device-schedule solver handles share (bis_cg, bis_mcg, bis_mbicgstab, bis_mgmres, bis_fgmres,
-// bis_minres, bis_idr, bis_lsmr, bis_stat): the state of one life cycle (create, [set_preconditioner], init, iterate ..., status,
+// bis_minres, bis_idr, bis_lsmr, bis_eigs, bis_svds, bis_stat): the state of one life cycle (create, [set_preconditioner], init, iterate ..., status,
 // destroy) with its allocation, release and the two reads *_status is made of; the scope in which a solve's stop flag
 // reaches the shared launchers; the layout of a last-arriver counter set; the scalar last-arriver reduction.  The host
 // functions are implemented in bis_solver.hip.
@@ -52,6 +52,10 @@ constexpr int kSolverT = 256; // threads per workgroup of the handles' passes
 inline int bis_pair_grid(int64_t n, int cap) {
     const int64_t g = ((n >> 1) + kSolverT - 1) / kSolverT;
     return (int)std::min<int64_t>(std::max<int64_t>(g, 1), cap);
+}
+// one lane per entry, for elementwise passes that walk 8 bytes per lane
+inline int lane_grid(int64_t n) {
+    return (int)std::min<int64_t>(std::max<int64_t>((n + kSolverT - 1) / kSolverT, 1), kMaxEwBlocks);
 }
 
 // ---- one last-arriver counter set ------------------------------------------------------------------------------------
